@@ -15,6 +15,9 @@ shard of that size.  Prints ONE JSON line on rank 0.
   --gpus N                                    N > 1 without a torchrun environment: bench.py starts its own ranks
                                               (python -m torch.distributed.run --nproc-per-node N on 127.0.0.1) and relays rank 0's line
   --dry-run                                   launcher / collective check without a GPU (gloo, synthetic result records)
+  --dump-outputs DIR                          after the timed steps, the results of the last one as DIR/<name>.npy (config* and realign;
+                                              at most 64 MB, a fixed seeded sample of the rows beyond that; +-inf saturated to the
+                                              largest finite float64, NaN written as 0 with a <name>_nan mask), to compare two builds
 """
 import argparse
 import ctypes as C
@@ -90,6 +93,37 @@ def _gen_pairs(args):
     from varlociraptor_amd import realign_synth
     pb, _ = realign_synth.generate(n_reads, seed=seed, window=window)
     return pb.x, pb.y, pb.q, pb.band
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: write `arrays` (name -> array, one row per locus / pair) as out_dir/<name>.npy — floats and 32-bit integers as
+    float64, 8/16-bit codes as float32 (both exact).  Every value written is finite: +-inf (ln posterior of a posterior that is exactly
+    0) becomes the largest finite float64 of its sign, far from any result, and NaN (no value, e.g. map_vaf without a MAP estimate)
+    becomes 0 with its positions in out_dir/<name>_nan.npy (1 = NaN).  Above DUMP_BYTES in all, every array keeps the same fixed,
+    seeded sample of rows, whose indices go to out_dir/sample_rows.npy."""
+    conv = {}
+    for name, v in arrays.items():
+        a = np.asarray(v)
+        a = a.astype(np.float32 if a.dtype.kind in "iu" and a.dtype.itemsize <= 2 else np.float64)
+        nan = np.isnan(a)
+        if nan.any():
+            conv[name + "_nan"] = nan.astype(np.float32)
+        big = np.finfo(a.dtype).max
+        conv[name] = np.nan_to_num(a, nan=0.0, posinf=big, neginf=-big)
+    arrays = conv
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // max(1, n) for a in arrays.values())
+    if row_bytes * n > DUMP_BYTES:
+        k = (DUMP_BYTES - 256 * (len(arrays) + 1)) // (row_bytes + 8)  # room for the .npy headers
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def traffic_for(workload, n_units, build_id):
@@ -232,6 +266,8 @@ def bench_realign(args, rank, world, local_rank, dev):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"ln_prob": dp.out.cpu().numpy()})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -506,7 +542,13 @@ def main():
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive and observation-BCF -> calls-BCF legs of the default line")
     ap.add_argument("--mode", default="exact", choices=["exact", "fast", "homopolymer"], help="realign workload: --pairhmm-mode of the reference (cli.rs:912-947)")
     ap.add_argument("--read-window", type=int, default=64, help="realign workload: realignment window; read windows are window..2*window bases (32: short reads, two pairs per wave)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's results) as DIR/<name>.npy, float32/float64, at most "
+                         "64 MB (a fixed, seeded sample of the rows beyond that); all values finite (+-inf saturated, NaN as 0 with a <name>_nan mask); "
+                         "config* and realign workloads")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry_run or args.workload in ("cli", "ingest")):
+        ap.error("--dump-outputs: the cli and ingest workloads and --dry-run have no result arrays to write")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -591,6 +633,9 @@ def main():
     # (the last launch's events; all launches process the same batch)
     last_ms = plan.last_kernel_ms()
     n_eval, n_terms = plan.work_counters()
+    if args.dump_outputs and rank == 0:  # before the legs below launch anything else
+        r = out.to_host()
+        dump_outputs(args.dump_outputs, {f: getattr(r, f) for f in ("ln_posterior", "ln_marginal", "map_vaf", "map_bias", "best_event", "status")})
 
     with_afd = None
     if args.afd:
