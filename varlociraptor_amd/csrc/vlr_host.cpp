@@ -937,11 +937,31 @@ int vlr_plan_set_max_obs(vlr_plan* plan, int max_obs_per_locus) {
     return VLR_OK;
 }
 
+// Bytes of the deep launch's pool (default 512 MiB = 22 M observations per batch; VLR_DEEP_POOL_MB, 0 = no deep launch: loci above
+// the LDS budget stay flagged VLR_LOCUS_TOO_DEEP), allocated in slot k unless it is there already.  Optional: no room, no pool.
+static void grow_deep_pool(vlr_plan* plan, int k) {
+    size_t pool = (size_t)512 << 20;
+    if (const char* ev = getenv("VLR_DEEP_POOL_MB")) pool = (size_t)std::max(0L, atol(ev)) << 20;
+    if (pool == 0 || plan->deep_pool_bytes[k] >= pool + 128) return;
+    if (plan->deep_pool[k]) (void)hipFree(plan->deep_pool[k]);
+    plan->deep_pool[k] = nullptr; plan->deep_pool_bytes[k] = 0;
+    if (hipMalloc(&plan->deep_pool[k], pool + 128) != hipSuccess) {
+        (void)hipGetLastError();
+        plan->deep_pool[k] = nullptr;
+        return;
+    }
+    plan->deep_pool_bytes[k] = pool + 128;
+}
+
 // LDS budget for a batch whose pileups the caller knows (host offsets): the deepest locus — or, where a slightly smaller budget lets
 // SIXTEEN workgroups share a CU (the launcher then runs the 4-wave build: +11..13 % on shallow tumor-normal batches,
 // tools/waves4_lds_probe.py), at most 0.5 % of the loci exceed it and the batch is large enough to pay for the deep launch behind the
-// call launch (one locus' latency, ~1 ms: tools/budget_probe.py), that budget.
-static int fit_budget(vlr_plan* plan, const uint32_t* off, int64_t l0, int64_t l1, int S, int cap_budget) {
+// call launch (one locus' latency, ~1 ms: tools/budget_probe.py), that budget.  The loci above it are then evaluated by the deep
+// launch alone, so it is only taken when the deep pool holds all of them — the pool of the chunk's slot (plan->slot), or with
+// `both_slots` of both slots (a budget set on the plan by vlr_plan_fit_max_obs also serves vlr_batch_run_host, whose chunks alternate
+// between the slots).  The pool is allocated here, not later in ensure_buffers, because that allocation may fail silently and the
+// budget could no longer be undone for a caller that has sized its buffers with it (vlr_plan_fit_max_obs + vlr_plan_reserve).
+static int fit_budget(vlr_plan* plan, const uint32_t* off, int64_t l0, int64_t l1, int S, int cap_budget, bool both_slots) {
     uint32_t mx = 1;
     for (int64_t l = l0; l < l1; ++l) mx = std::max(mx, off[(l + 1) * S] - off[l * S]);
     int best = std::min<int>(cap_budget, (int)mx);
@@ -956,8 +976,19 @@ static int fit_budget(vlr_plan* plan, const uint32_t* off, int64_t l0, int64_t l
     const int m16 = (int)((vlr::kLdsWg16 - b0) / 16) & ~3;   // largest budget with 16 workgroups per CU (the launch rounds budgets up to a multiple of four)
     if (m16 < 1 || m16 >= best) return best;
     int64_t over = 0;
-    for (int64_t l = l0; l < l1; ++l) over += (off[(l + 1) * S] - off[l * S]) > (uint32_t)m16;
-    return (over * 200 <= (l1 - l0) && (over == 0 || l1 - l0 >= 100000)) ? m16 : best;
+    size_t need = 0;   // pool doubles of the deep launch (the kernel's: 3 per kept observation + 2 S; all observations bound the kept ones)
+    for (int64_t l = l0; l < l1; ++l) {
+        const uint32_t n = off[(l + 1) * S] - off[l * S];
+        if (n > (uint32_t)m16) { ++over; need += 3 * (size_t)n + 2 * (size_t)S; }
+    }
+    if (over * 200 > (l1 - l0) || (over > 0 && l1 - l0 < 100000)) return best;
+    if (over == 0) return m16;
+    const int k0 = both_slots ? 0 : (plan->slot & 1), k1 = both_slots ? 1 : k0;
+    for (int k = k0; k <= k1; ++k) {
+        grow_deep_pool(plan, k);
+        if (!plan->deep_pool[k] || (plan->deep_pool_bytes[k] - 128) / sizeof(double) < need) return best;
+    }
+    return m16;
 }
 
 int vlr_plan_fit_max_obs(vlr_plan* plan, const uint32_t* obs_offset_host, int64_t n_loci) {
@@ -966,7 +997,7 @@ int vlr_plan_fit_max_obs(vlr_plan* plan, const uint32_t* obs_offset_host, int64_
     (void)hipGetDevice(&dev_before);
     (void)hipSetDevice(plan->device);
     const int S = plan->host.S;
-    const int b = fit_budget(plan, obs_offset_host, 0, n_loci, S, 7680);
+    const int b = fit_budget(plan, obs_offset_host, 0, n_loci, S, 7680, true);
     (void)hipSetDevice(dev_before);
     const int rc = vlr_plan_set_max_obs(plan, std::max(1, b));
     return rc != VLR_OK ? rc : std::max(1, b);
@@ -993,12 +1024,8 @@ static int ensure_buffers(vlr_plan* plan, int64_t n_loci, int max_obs, bool want
     // (+ 2 S doubles per locus in front of every row: the all-ones products, DevResults::escratch)
     int rc = grow(&plan->escratch[k], &plan->escratch_bytes[k], L * ((size_t)max_obs + 2 * (size_t)plan->host.S) * sizeof(double), false);
     if (rc != VLR_OK) return rc;
-    {   // pool of the deep launch: 24 B per kept observation of the loci above the LDS budget (default 512 MiB = 22 M observations
-        // per batch; VLR_DEEP_POOL_MB, 0 = no deep launch: such loci stay flagged VLR_LOCUS_TOO_DEEP).  Optional: no room, no fallback.
-        size_t pool = (size_t)512 << 20;
-        if (const char* ev = getenv("VLR_DEEP_POOL_MB")) pool = (size_t)std::max(0L, atol(ev)) << 20;
-        if (pool > 0 && plan->deep_hint != 0) (void)grow(&plan->deep_pool[k], &plan->deep_pool_bytes[k], pool + 128, true);
-    }
+    // pool of the deep launch: 24 B per kept observation of the loci above the LDS budget (grow_deep_pool)
+    if (plan->deep_hint != 0) grow_deep_pool(plan, k);
     if (want_afd) {
         rc = grow(&plan->afd_scratch[k], &plan->afd_scratch_bytes[k], 2 * L + 8 * L + 4 * L + 64, false);
         if (rc != VLR_OK) return rc;
@@ -1343,15 +1370,15 @@ static int host_chunk_start(vlr_plan* plan, const vlr_batch* in, vlr_results* ou
     dr.afd_lnprob = want_afd ? (double*)(base + r_al) : nullptr;
     // size the LDS coefficient area to this chunk (never above the configured budget)
     int saved_max_obs = plan->max_obs;
+    plan->slot = k;   // (before fit_budget: the 16-workgroup budget needs this slot's deep pool)
     {
         int budget = plan->max_obs > 0 ? plan->max_obs : plan->max_depth_per_sample * S;
         uint32_t mx = 1;
         for (int64_t l = l0; l < l1; ++l) mx = std::max(mx, h_off[(l + 1) * S] - h_off[l * S]);
-        plan->max_obs = fit_budget(plan, h_off, l0, l1, S, budget);   // (the deepest locus, or the 16-workgroup budget: see fit_budget)
+        plan->max_obs = fit_budget(plan, h_off, l0, l1, S, budget, false);   // (the deepest locus, or the 16-workgroup budget: see fit_budget)
         // the LDS-resident kernel holds at most 7 680 kept observations of a locus; the launcher's own limit is the budget
         plan->deep_hint = ((int)mx > std::min(plan->max_obs, 7680)) ? 1 : 0;
     }
-    plan->slot = k;
     int rc = vlr_batch_run(plan, &db, &dr, (void*)st);
     plan->max_obs = saved_max_obs;
     plan->deep_hint = -1;

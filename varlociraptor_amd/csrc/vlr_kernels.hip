@@ -36,6 +36,11 @@
 
 namespace vlr {
 
+// Internal status bit, never returned: set (with VLR_LOCUS_TOO_DEEP) by the deep call launch of an AFD batch on every locus it
+// evaluated, consumed by the deep replay launch.  The replay bump-allocates from the same pool after a counter reset, so without it a
+// locus that got no pool room in the call pass could get room in the replay and lose its flag with nothing evaluated.
+constexpr unsigned kDeepEvaluated = 1u << 31;
+
 // optional per-phase cycle accounting (build with -DVLR_PROFILE): wall cycles of the wave spent per phase
 #if defined(VLR_PROFILE) && defined(VLR_PROFILE_VALU)
 // Per-region VALU INSTRUCTION counts instead of cycles: tools/valu_profile.sh rewrites the kernel's assembly so that every basic
@@ -3964,6 +3969,9 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
 #endif
     if (locus >= batch.n_loci) return;   // (plans above kLdsSamples samples: the host launches the wide build)
     if (VLR_DEEP && !(out.status[locus] & VLR_LOCUS_TOO_DEEP)) return;  // deep launch: only what the LDS-resident kernel could not hold
+    // deep replay: only what the deep call launch evaluated (the others keep their flag).  These loci held pool room in the call pass
+    // and need the same room again, so together they fit the pool whatever the order of their allocations.
+    if (VLR_DEEP && out.replay && !(out.status[locus] & kDeepEvaluated)) return;
     // replay launch next to an AFD log: only the loci whose log region overflowed are re-evaluated
     if (!VLR_DEEP && out.replay && out.afd_log && __double_as_longlong(out.afd_log[(size_t)locus * (size_t)out.afd_log_stride]) >= 0) return;
     const int S = p.S;
@@ -4295,7 +4303,8 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
         bool art = false;
         if (out.map_bias) for (int i = 0; i < VLR_N_BIAS; ++i) art = art || out.map_bias[locus * VLR_N_BIAS + i] != 0;
         if (!have || art || too_deep) {
-            if (VLR_DEEP && !too_deep && lane == 0) out.status[locus] &= ~VLR_LOCUS_TOO_DEEP;  // no lists to make: done
+            // no lists to make: done (no pool room, which the gate above rules out: the flag stays)
+            if (VLR_DEEP && lane == 0) out.status[locus] &= too_deep ? ~kDeepEvaluated : ~(VLR_LOCUS_TOO_DEEP | kDeepEvaluated);
             return;
         }
         VLR_SYNC();
@@ -4694,7 +4703,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
     PROF_ADD(c, 3);  // walk remainder (everything in the event loop not attributed below)
     if (c.replay) {
         afd_finish(c);
-        if (VLR_DEEP && lane == 0) out.status[locus] &= ~VLR_LOCUS_TOO_DEEP;  // evaluated by the deep call launch, lists done
+        if (VLR_DEEP && lane == 0) out.status[locus] &= ~(VLR_LOCUS_TOO_DEEP | kDeepEvaluated);  // evaluated by the deep call launch, lists done
         return;
     }
     // ============================ phase C: posteriors + MAP ============================
@@ -4806,8 +4815,8 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
         c.lg[0] = __longlong_as_double((long long)c.lg_pos);
         c.lg[1] = __longlong_as_double((long long)c.lg_nrec);
     }
-    // deep launch with AFD lists: the deep replay launch still has to find this locus
-    if (VLR_DEEP && out.afd_count && !(c.status & VLR_LOCUS_TOO_DEEP)) c.status |= VLR_LOCUS_TOO_DEEP;
+    // deep launch with AFD lists: the deep replay launch still has to find this locus (kDeepEvaluated: it was evaluated here)
+    if (VLR_DEEP && out.afd_count && !(c.status & VLR_LOCUS_TOO_DEEP)) c.status |= VLR_LOCUS_TOO_DEEP | kDeepEvaluated;
     if (lane == 0) {
         out.status[locus] = c.status;
         if (out.work) {
