@@ -34,10 +34,11 @@
 extern "C" {
 #endif
 
-#define VLR_ABI_VERSION 6   /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
+#define VLR_ABI_VERSION 7   /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
                              * 5: sharded device reader, calls-file parts, vlr_ingest_device_trim, CRC32 of BGZF members checked by both readers;
                              * 6: calls emission on the device — vlr_results.afd_text (FORMAT/AFD text), OBS text in the observation summaries,
-                             *    vlr_obs_table_summaries */
+                             *    vlr_obs_table_summaries;
+                             * 7: vlr_contamination_posterior (`estimate contamination`) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -437,6 +438,36 @@ int vlr_edit_distance_batch_host(int device, const vlr_realign_batch_desc* pairs
  * VLR_FDR_NONE (no admissible entry: None).  The filtering pass (utils/mod.rs:288-374) stays with the caller. */
 enum { VLR_FDR_EMPTY = 0, VLR_FDR_VALUE = 1, VLR_FDR_LN_ONE = 2, VLR_FDR_NONE = 3 };
 int vlr_fdr_threshold(int device, const double* ln_prob, int64_t n, int smart, double alpha_ln, double* threshold, int* status);
+
+/* ------------------------------------------------------------------------------------------------
+ * Contamination estimation: the posterior grid of `estimate contamination` (estimation/contamination.rs:160-224).
+ * Events: maximum somatic VAF mv_m in (0.25, 0.5, 0.75, 1.0) x contamination c_i = 0.0 + 0.01 i (i = 0..100, linspace);
+ * ln_joint[m * 101 + i] = ln_prior[i] + sum over the observations o of term(o, m, i), where, with purity = 1.0 - c_i,
+ *   purity == 0 (i = 100): term = ln(1 - e^ln_prob_denovo[o])       (LogProb::ln_one_minus_exp);
+ *   otherwise:             term = pdf_o((mv_m * purity) * (map_vaf[o] / max_vaf))   (left to right, no FMA),
+ * pdf_o(x) over the list of o (list_vaf / list_lnprob[list_offset[o] .. list_offset[o + 1]], VAF strictly ascending):
+ *   a key equal to x: its value; x strictly between two keys x_a < x < x_b with values a, b: linear interpolation of the
+ *   densities in probability space, a.ln_add_exp(ln((e^b - e^a) / (x_b - x_a)) + ln(x - x_a)) on rising and flat segments
+ *   (the reference's formula) and a.ln_sub_exp(ln|slope| + ln(x - x_a)) on falling ones (e^b < e^a; the reference takes the ln
+ *   of a negative number there, NaN: a deliberate deviation; should rounding put the subtrahend at or above a,
+ *   the value is b); x left of the first key, right of the last, in an empty list, or NaN (max_vaf = 0): -inf.
+ * Summation order (fixed: independent of the launch geometry, the scheduling and of how the caller split its input): the
+ *   observations in blocks of VLR_CONTAM_BLOCK consecutive ones, each block summed sequentially in record order starting from
+ *   0.0, the block sums added sequentially in block order starting from 0.0, then ln_prior[i] added.  The same input gives the
+ *   same bits.  n_obs = 0 is legal: every likelihood is 0 (ln_joint = ln_prior).
+ * NaN / -inf: a -inf term makes its event's sum -inf (IEEE addition: a NaN term, or -inf next to +inf, gives NaN); inputs are
+ *   not checked for NaN other than the keys (a NaN key or keys out of order = VLR_ERR_INVALID_ARGUMENT, as are offsets that
+ *   do not start at 0 or decrease).
+ * *ln_marginal (contamination.rs:196-224, host side): per mv_m ln_simpsons_integrate_exp over the 101 joints (weights 1, 4, 2,
+ *   ..., 4, 1; + ln(1 - 0) - ln 100 - ln 3), then ln_sum_exp of the four integrals (bio semantics).
+ *   The posterior of an event is ln_joint - *ln_marginal.  ln_prior: [101], tabulated by the caller (ln 1 without an estimate).
+ * All pointers are host pointers; the function uploads, launches on `device` and copies back (synchronous). */
+#define VLR_CONTAM_BLOCK 128
+#define VLR_CONTAM_N_C   101
+#define VLR_CONTAM_N_MV  4
+int vlr_contamination_posterior(int device, int64_t n_obs, const int64_t* list_offset, const double* list_vaf, const double* list_lnprob,
+                                const double* map_vaf, const double* ln_prob_denovo, double max_vaf, const double* ln_prior,
+                                double* ln_joint, double* ln_marginal);
 
 /* The whole of `varlociraptor filter-calls control-fdr` (/root/reference/src/filtration/fdr.rs:36-158, record typing
  * src/utils/collect_variants.rs:44-304, probability sums and the filtering pass src/utils/mod.rs:169-374): read the calls BCF

@@ -1,4 +1,5 @@
 """`python -m varlociraptor_amd call variants generic --scenario S.yaml --obs name=path.vcf ... [> calls.vcf]`
+(also `filter-calls control-fdr` and `estimate contamination`, contamination.py)
 
 Mirror of the reference's `call variants` surface (src/cli.rs:684-735) for text observation VCFs (format v15):
 `generic` with a scenario YAML (grammar/mod.rs:129-144) and `tumor-normal --tumor --normal --purity`
@@ -756,6 +757,16 @@ def main(argv=None):
     cf.add_argument("--maxlen", type=int)
     cf.add_argument("--device", default="cpu")
     cf.add_argument("--output", "-o", help="BCF file for the kept records (default: a CHROM/POS/ID/REF/ALT table on stdout)")
+    est = sub.add_parser("estimate").add_subparsers(dest="what", required=True)
+    ec = est.add_parser("contamination", help="estimate the contamination of a sample by a contaminant (cli.rs:460-497)")
+    ec.add_argument("--sample", required=True, help="observations of the presumably contaminated sample")
+    ec.add_argument("--contaminant", required=True, help="observations of the presumably contaminating sample")
+    ec.add_argument("--prior-estimate", type=float, help="prior estimate of the contamination (1 - purity); needs --prior-considered-cells")
+    ec.add_argument("--prior-considered-cells", type=int, help="number of cells the prior estimate was made from")
+    ec.add_argument("--output", help="posterior table (TSV; default stdout)")
+    ec.add_argument("--output-plot", help="vega-lite plot of the prior and posterior densities of purity (JSON)")
+    ec.add_argument("--output-max-vaf-variants", help="chrom,pos of the observations at the maximum MAP VAF (CSV)")
+    ec.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     import os
     if a.cmd == "call" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -767,6 +778,15 @@ def main(argv=None):
         a.device = local % max(torch.cuda.device_count(), 1)
         torch.cuda.set_device(a.device)
         tdist.init_process_group(backend, **({"device_id": torch.device("cuda", a.device)} if backend == "nccl" else {}))
+    if a.cmd == "estimate":
+        # cli.rs:1292-1298: both prior options or neither, and at least one cell
+        if (a.prior_estimate is None) != (a.prior_considered_cells is None) or (a.prior_considered_cells is not None and a.prior_considered_cells <= 0):
+            ap.error("invalid prior contamination estimate: give --prior-estimate together with --prior-considered-cells > 0")
+        from . import contamination
+        prior = (a.prior_estimate, a.prior_considered_cells) if a.prior_estimate is not None else None
+        contamination.estimate_contamination(a.sample, a.contaminant, output=a.output, output_plot=a.output_plot,
+                                             output_max_vaf_variants=a.output_max_vaf_variants, prior_estimate=prior, device=a.device)
+        return
     if a.cmd == "filter-calls":
         from . import fdr
         vartype = None
