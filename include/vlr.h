@@ -34,11 +34,12 @@
 extern "C" {
 #endif
 
-#define VLR_ABI_VERSION 7   /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
+#define VLR_ABI_VERSION 8   /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
                              * 5: sharded device reader, calls-file parts, vlr_ingest_device_trim, CRC32 of BGZF members checked by both readers;
                              * 6: calls emission on the device — vlr_results.afd_text (FORMAT/AFD text), OBS text in the observation summaries,
                              *    vlr_obs_table_summaries;
-                             * 7: vlr_contamination_posterior (`estimate contamination`) */
+                             * 7: vlr_contamination_posterior (`estimate contamination`);
+                             * 8: vlr_bamstats_* (`estimate alignment-properties`) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -468,6 +469,43 @@ int vlr_fdr_threshold(int device, const double* ln_prob, int64_t n, int smart, d
 int vlr_contamination_posterior(int device, int64_t n_obs, const int64_t* list_offset, const double* list_vaf, const double* list_lnprob,
                                 const double* map_vaf, const double* ln_prob_denovo, double max_vaf, const double* ln_prior,
                                 double* ln_joint, double* ln_marginal);
+
+/* ------------------------------------------------------------------------------------------------
+ * Alignment properties: the per-record pass of `estimate alignment-properties` (estimation/alignment_properties.rs:148-463 with
+ * cigar_stats :693-861; omit_insert_size = false, as the CLI calls it).  The BAM files given to vlr_bamstats_add_bam, in that order,
+ * are streamed through the device reader (BGZF members inflated on the device, BAM records split there); the first max_records
+ * records that pass the skip rule (mapq 0, duplicate, QC fail, unmapped, empty SEQ: skipped; secondary / supplementary kept) are
+ * analysed against the reference at fasta_path (its .fai is required; only the contigs the analysed records lie on are read and
+ * uploaded, case preserved).  window_bytes: inflated bytes per split (0: 64 MiB; tests force small windows).
+ * vlr_bamstats_result fills a vlr_bamstats_counts with the integer counts: transitions[from * 16 + to] over the states MatchA..T (0-3), GapX 4, GapY 5,
+ *   HopAX 6, HopAY 7, ..., HopTY 13, Other 14; the maxima (max_del / max_ins -1 = none; has_softclip = 0: frac_max_softclip none);
+ *   the flag counters of the reference's warning (over the analysed records); n_skipped: records in front of the cap the skip rule
+ *   dropped.  seconds: [0] file read, [1] upload + inflate of the feeds, [2] record split, [3] take + select kernels, [4] reference
+ *   upload, [5] statistics kernel, [6] insert sizes back to the host, [7] total, [8] inflate kernels alone, [9] splits that fell back to the serial walk.
+ * vlr_bamstats_read then copies the homopolymer-run counters (CigarStats::hop_counts) in ascending key order, key = raw base byte
+ *   << 56 | k0 << 28 | k1, and the insert sizes (|TLEN| of a paired first-in-template record with its mate on the same contig, or
+ *   end - pos of an unpaired record whose first EF aux tag is an integer 1; records with an I, D, S or H operation give none) in
+ *   record order.  The finishing math (percentiles, parameters, model, JSON) is the caller's (varlociraptor_amd/alignprops.py).
+ * Errors (VLR_ERR_INVALID_ARGUMENT, the message names the file and the record number): a malformed or truncated record, a corrupt
+ *   BGZF member, a CIGAR that runs past its contig or its read where the reference would index out of bounds, a reference id out of
+ *   range, a contig missing from the FASTA, a homopolymer key >= 2^28 - 1.  Counts are sums of integers: bit-reproducible whatever
+ *   the window size or the launch geometry. */
+typedef struct vlr_bamstats vlr_bamstats;
+typedef struct {
+    uint64_t transitions[256];
+    int64_t  n_taken, n_skipped, n_not_usable, n_softclips;
+    int64_t  n_not_paired, n_not_first, n_mate_unmapped, n_tid_mismatch;
+    int64_t  max_del, max_ins, max_read_len, max_mapq;
+    double   frac_max_softclip;
+    int64_t  has_softclip;
+    int64_t  n_hop_keys, n_insert_sizes;
+    double   seconds[10];
+} vlr_bamstats_counts;
+int  vlr_bamstats_open(int device, const char* fasta_path, int64_t max_records, int64_t window_bytes, vlr_bamstats** out);
+int  vlr_bamstats_add_bam(vlr_bamstats* s, const char* bam_path);
+int  vlr_bamstats_result(vlr_bamstats* s, vlr_bamstats_counts* out);
+int  vlr_bamstats_read(vlr_bamstats* s, uint64_t* hop_keys, uint64_t* hop_counts, int64_t n_hop, int64_t* insert_sizes, int64_t n_insert);
+void vlr_bamstats_close(vlr_bamstats* s);
 
 /* The whole of `varlociraptor filter-calls control-fdr` (/root/reference/src/filtration/fdr.rs:36-158, record typing
  * src/utils/collect_variants.rs:44-304, probability sums and the filtering pass src/utils/mod.rs:169-374): read the calls BCF

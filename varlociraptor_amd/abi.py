@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_SAMPLES = 16
 N_BIAS = 6
 
@@ -137,3 +137,13 @@ def pack_flags(strand, orientation, readpos_major, softclipped, paired, max_mapq
         f = f | np.where(valid, F_HP_LEN_VALID, 0).astype(np.uint32)
         f = f | np.where(valid, (hp.astype(np.int8).view(np.uint8).astype(np.uint32)) << F_HP_LEN_SHIFT, 0).astype(np.uint32)
     return f.astype(np.uint32)
+
+
+class BamStatsResult(C.Structure):
+    """vlr_bamstats_counts (estimate alignment-properties, ABI 8)."""
+    _fields_ = [("transitions", C.c_uint64 * 256),
+                ("n_taken", C.c_int64), ("n_skipped", C.c_int64), ("n_not_usable", C.c_int64), ("n_softclips", C.c_int64),
+                ("n_not_paired", C.c_int64), ("n_not_first", C.c_int64), ("n_mate_unmapped", C.c_int64), ("n_tid_mismatch", C.c_int64),
+                ("max_del", C.c_int64), ("max_ins", C.c_int64), ("max_read_len", C.c_int64), ("max_mapq", C.c_int64),
+                ("frac_max_softclip", C.c_double), ("has_softclip", C.c_int64),
+                ("n_hop_keys", C.c_int64), ("n_insert_sizes", C.c_int64), ("seconds", C.c_double * 10)]

@@ -758,6 +758,12 @@ def main(argv=None):
     cf.add_argument("--device", default="cpu")
     cf.add_argument("--output", "-o", help="BCF file for the kept records (default: a CHROM/POS/ID/REF/ALT table on stdout)")
     est = sub.add_parser("estimate").add_subparsers(dest="what", required=True)
+    ea = est.add_parser("alignment-properties", help="estimate insert size, CIGAR maxima, gap / homopolymer parameters and the wildtype "
+                        "homopolymer error model of a sample (cli.rs:423-448)")
+    ea.add_argument("reference", help="FASTA file of the reference genome (indexed with samtools faidx)")
+    ea.add_argument("--bams", nargs="+", required=True, help="BAM files of one sample (or of samples prepared the same way)")
+    ea.add_argument("--num-records", type=int, help="number of records to sample (default: from the BAM indices, which are then required)")
+    ea.add_argument("--device", default="0", help="HIP device index, or 'cpu' for the pure-Python restatement")
     ec = est.add_parser("contamination", help="estimate the contamination of a sample by a contaminant (cli.rs:460-497)")
     ec.add_argument("--sample", required=True, help="observations of the presumably contaminated sample")
     ec.add_argument("--contaminant", required=True, help="observations of the presumably contaminating sample")
@@ -778,6 +784,14 @@ def main(argv=None):
         a.device = local % max(torch.cuda.device_count(), 1)
         torch.cuda.set_device(a.device)
         tdist.init_process_group(backend, **({"device_id": torch.device("cuda", a.device)} if backend == "nccl" else {}))
+    if a.cmd == "estimate" and a.what == "alignment-properties":
+        from . import alignprops
+        if a.num_records is not None and a.num_records < 0:
+            ap.error("--num-records must not be negative")
+        rc = alignprops.run_cli(a.reference, a.bams, a.num_records, "cpu" if a.device == "cpu" else int(a.device))
+        if rc:
+            sys.exit(rc)
+        return
     if a.cmd == "estimate":
         # cli.rs:1292-1298: both prior options or neither, and at least one cell
         if (a.prior_estimate is None) != (a.prior_considered_cells is None) or (a.prior_considered_cells is not None and a.prior_considered_cells <= 0):

@@ -1007,6 +1007,97 @@ __global__ __launch_bounds__(64) void afd_write_kernel(const int32_t* __restrict
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------ BAM record split (vlr_bamstats.hip)
+// The same anchor / verified walk / serial fallback as the BCF split above, over BAM records (SAM spec 4.2.1): a u32 block_size in
+// front of the 32-byte fixed head, the next record at o + 4 + block_size.
+__device__ __forceinline__ bool bam_head_plausible(const uint8_t* base, uint64_t o, uint64_t avail, int n_refs) {
+    if (o + 36 > avail) return false;
+    const uint8_t* p = base + o;
+    const uint32_t bs = ld32(p);
+    if (bs < 32 || bs >= (1u << 28)) return false;
+    const int32_t tid = (int32_t)ld32(p + 4), pos = (int32_t)ld32(p + 8), mtid = (int32_t)ld32(p + 24), mpos = (int32_t)ld32(p + 28);
+    if (tid < -1 || tid >= n_refs || mtid < -1 || mtid >= n_refs || pos < -1 || mpos < -1) return false;
+    const uint32_t l_rn = p[12], n_cig = ld16(p + 16);
+    const int32_t l_seq = (int32_t)ld32(p + 20);
+    if (l_rn < 1 || l_seq < 0) return false;
+    if (32ull + l_rn + 4ull * n_cig + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq > bs) return false;
+    if (o + 36 + l_rn <= avail && p[36 + l_rn - 1] != 0) return false;   // the read name ends in NUL
+    // bin = reg2bin(pos, end) (SAM spec 4.2.1, 5.3): one of the bins that contain pos (pos -1: 4680).  A writer that leaves bin 0 or
+    // another value only costs the serial walk: the guess is verified either way
+    const uint32_t bin = ld16(p + 14);
+    return bin == (uint32_t)(4681 + (pos >> 14)) || bin == (uint32_t)(585 + (pos >> 17)) || bin == (uint32_t)(73 + (pos >> 20)) ||
+           bin == (uint32_t)(9 + (pos >> 23)) || bin == (uint32_t)(1 + (pos >> 26)) || bin == 0;
+}
+__device__ __forceinline__ uint64_t bam_next(const uint8_t* base, uint64_t o) { return o + 4 + (uint64_t)ld32(base + o); }
+
+__global__ __launch_bounds__(64) void bam_anchor_kernel(const uint8_t* __restrict__ base, uint64_t avail, int n_seg, int n_refs, uint64_t* __restrict__ anchor) {
+    const int seg = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (seg >= n_seg) return;
+    if (seg == 0) { if (lane == 0) anchor[0] = 0; return; }
+    uint64_t found = kNone;
+    for (uint64_t o0 = (uint64_t)seg * kSeg; o0 + 36 <= avail; o0 += 64) {
+        const uint64_t o = o0 + (uint64_t)lane;
+        bool ok = bam_head_plausible(base, o, avail, n_refs);
+        if (ok) {
+            const uint64_t nxt = bam_next(base, o);
+            if (nxt + 36 <= avail) ok = bam_head_plausible(base, nxt, avail, n_refs);
+        }
+        const unsigned long long m = __ballot(ok);
+        if (m != 0) { found = o0 + (uint64_t)(__ffsll((long long)m) - 1); break; }
+    }
+    if (lane == 0) anchor[seg] = found;
+}
+
+__global__ void bam_walk_kernel(const uint8_t* __restrict__ base, uint64_t avail, int n_seg, const uint64_t* __restrict__ anchor,
+                                uint32_t* __restrict__ count, uint64_t* __restrict__ landing, uint8_t* __restrict__ land_complete) {
+    const int seg = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (seg >= n_seg) return;
+    uint64_t o = anchor[seg];
+    const uint64_t lim = (uint64_t)(seg + 1) * kSeg;
+    uint32_t c = 0;
+    bool complete = false;
+    if (o != kNone) {
+        for (;;) {
+            complete = false;
+            if (o + 4 > avail) break;
+            const uint64_t nxt = bam_next(base, o);
+            if (nxt > avail) break;
+            complete = true;
+            if (o >= lim) break;
+            c += 1;
+            o = nxt;
+        }
+    }
+    count[seg] = c; landing[seg] = o; land_complete[seg] = complete ? 1 : 0;
+}
+
+__global__ void bam_starts_kernel(const uint8_t* __restrict__ base, int n_seg, const uint64_t* __restrict__ anchor, const uint64_t* __restrict__ seg_base,
+                                  const uint32_t* __restrict__ count, uint64_t n_keep, uint64_t* __restrict__ starts) {
+    const int seg = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (seg >= n_seg) return;
+    uint64_t o = anchor[seg];
+    const uint64_t b = seg_base[seg];
+    const uint32_t c = count[seg];
+    for (uint32_t j = 0; j <= c; ++j) {
+        if (b + j <= n_keep && (j < c || b + j == n_keep)) starts[b + j] = o;
+        if (j < c) o = bam_next(base, o);
+    }
+}
+
+__global__ void bam_walk_serial_kernel(const uint8_t* __restrict__ base, uint64_t avail, uint64_t max_records, uint64_t* __restrict__ starts, uint64_t* __restrict__ n_out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    uint64_t o = 0, n = 0;
+    while (n < max_records && o + 4 <= avail) {
+        const uint64_t nxt = bam_next(base, o);
+        if (nxt > avail) break;
+        starts[n++] = o;
+        o = nxt;
+    }
+    starts[n] = o;
+    *n_out = n;
+}
+
 }  // namespace
 }  // namespace vlr
 
@@ -1569,6 +1660,93 @@ void vlr_dev_slab_free(int device, void* d, void* h) {
     (void)hipSetDevice(device);
     if (d) (void)hipFree(d);
     if (h) (void)hipHostFree(h);
+}
+
+// BAM twin of vlr_dev_file_split (vlr_gpuio.h): record starts only, no INFO scan
+int vlr_dev_file_split_bam(vlr_dev_file* f, int64_t max_records, int n_refs, int64_t* n_records, int* used_serial_walk) {
+    VLR_HIP_OK(hipSetDevice(f->device));
+    { const int rcw = vlr_dev_file_wait_ready(f, 4); if (rcw != VLR_OK) return rcw; }
+    *n_records = 0;
+    if (used_serial_walk) *used_serial_walk = 0;
+    f->n_split = 0;
+    const uint64_t avail = f->ready - f->rd;
+    if (avail < 4 || max_records <= 0) return VLR_OK;
+    if (f->compact_pending) {
+        VLR_HIP_OK(hipStreamWaitEvent(f->stream, f->ev_compact, 0));
+        f->compact_pending = false;
+    }
+    const uint8_t* base = f->buf + f->rd;
+    const int n_seg = (int)((avail + vlr::kSeg - 1) / vlr::kSeg);
+    int rc;
+    if ((size_t)n_seg > f->seg_cap) {
+        VLR_HIP_OK(hipStreamSynchronize(f->stream));
+        size_t c[5] = {f->seg_cap, f->seg_cap, f->seg_cap, f->seg_cap, f->seg_cap};
+        if ((rc = dev_grow(f->d_anchor, c[0], (size_t)n_seg)) || (rc = dev_grow(f->d_landing, c[1], (size_t)n_seg)) || (rc = dev_grow(f->d_segbase, c[2], (size_t)n_seg)) ||
+            (rc = dev_grow(f->d_count, c[3], (size_t)n_seg)) || (rc = dev_grow(f->d_landc, c[4], (size_t)n_seg))) return rc;
+        f->seg_cap = c[0];
+    }
+    if ((size_t)max_records + 1 > f->rec_cap) {
+        VLR_HIP_OK(hipStreamSynchronize(f->stream));
+        size_t c[3] = {f->rec_cap, f->rec_cap, f->rec_cap};
+        if ((rc = dev_grow(f->d_starts, c[0], (size_t)max_records + 1)) || (rc = dev_grow(f->d_desc, c[1], (size_t)max_records + 1)) || (rc = dev_grow(f->d_host, c[2], (size_t)max_records + 1))) return rc;
+        f->rec_cap = c[0];
+    }
+    if (!f->d_nout) VLR_HIP_OK(hipMalloc(&f->d_nout, 16));
+    hipLaunchKernelGGL(vlr::bam_anchor_kernel, dim3((unsigned)n_seg), dim3(64), 0, f->stream, base, avail, n_seg, n_refs, f->d_anchor);
+    hipLaunchKernelGGL(vlr::bam_walk_kernel, dim3((unsigned)((n_seg + 63) / 64)), dim3(64), 0, f->stream, base, avail, n_seg, f->d_anchor, f->d_count, f->d_landing, f->d_landc);
+    std::vector<uint64_t> anchor((size_t)n_seg), landing((size_t)n_seg), segbase((size_t)n_seg);
+    std::vector<uint32_t> count((size_t)n_seg);
+    std::vector<uint8_t> landc((size_t)n_seg);
+    VLR_HIP_OK(hipMemcpyAsync(anchor.data(), f->d_anchor, (size_t)n_seg * 8, hipMemcpyDeviceToHost, f->stream));
+    VLR_HIP_OK(hipMemcpyAsync(landing.data(), f->d_landing, (size_t)n_seg * 8, hipMemcpyDeviceToHost, f->stream));
+    VLR_HIP_OK(hipMemcpyAsync(count.data(), f->d_count, (size_t)n_seg * 4, hipMemcpyDeviceToHost, f->stream));
+    VLR_HIP_OK(hipMemcpyAsync(landc.data(), f->d_landc, (size_t)n_seg, hipMemcpyDeviceToHost, f->stream));
+    VLR_HIP_OK(hipStreamSynchronize(f->stream));
+    bool verified = true;
+    uint64_t total = 0;
+    int last_seg = -1;
+    for (int i = 0; i < n_seg; ++i) {
+        if (i > 0 && anchor[(size_t)i] != landing[(size_t)i - 1]) {
+            if (!landc[(size_t)i - 1]) break;
+            verified = false;
+            break;
+        }
+        segbase[(size_t)i] = total;
+        total += count[(size_t)i];
+        last_seg = i;
+        if (total >= (uint64_t)max_records) break;
+    }
+    const char* force = getenv("VLR_INGEST_SERIAL_WALK");
+    if (force && atoi(force) != 0) verified = false;
+    uint64_t n = 0;
+    if (verified) {
+        n = total < (uint64_t)max_records ? total : (uint64_t)max_records;
+        const int used = last_seg + 1;
+        if (n > 0) {
+            VLR_HIP_OK(hipMemcpyAsync(f->d_segbase, segbase.data(), (size_t)used * 8, hipMemcpyHostToDevice, f->stream));
+            hipLaunchKernelGGL(vlr::bam_starts_kernel, dim3((unsigned)((used + 63) / 64)), dim3(64), 0, f->stream, base, used, f->d_anchor, f->d_segbase, f->d_count, n, f->d_starts);
+        }
+    } else {
+        if (used_serial_walk) *used_serial_walk = 1;
+        hipLaunchKernelGGL(vlr::bam_walk_serial_kernel, dim3(1), dim3(64), 0, f->stream, base, avail, (uint64_t)max_records, f->d_starts, f->d_nout);
+        VLR_HIP_OK(hipMemcpyAsync(&n, f->d_nout, 8, hipMemcpyDeviceToHost, f->stream));
+        VLR_HIP_OK(hipStreamSynchronize(f->stream));
+    }
+    if (n == 0) return VLR_OK;
+    f->h_starts.resize((size_t)n + 1);
+    VLR_HIP_OK(hipMemcpyAsync(f->h_starts.data(), f->d_starts, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, f->stream));
+    VLR_HIP_OK(hipStreamSynchronize(f->stream));
+    VLR_HIP_OK(hipGetLastError());
+    f->n_split = (int64_t)n;
+    *n_records = (int64_t)n;
+    return VLR_OK;
+}
+
+int vlr_dev_file_split_view(vlr_dev_file* f, const uint8_t** d_base, const uint64_t** d_starts) {
+    if (!f || !d_base || !d_starts) return dfail(VLR_ERR_INVALID_ARGUMENT, "vlr_dev_file_split_view: null");
+    *d_base = f->buf + f->rd;
+    *d_starts = f->d_starts;
+    return VLR_OK;
 }
 
 int vlr_dev_file_consume(vlr_dev_file* f, int64_t n) {

@@ -111,6 +111,11 @@ int vlr_dev_file_skip(vlr_dev_file* f, uint64_t bytes);
 // rec_host[0..n) (array owned by the object, valid until the next split) their counts.  Synchronises the file's stream.
 int vlr_dev_file_split(vlr_dev_file* f, int64_t max_records, int n_contigs, int n_hdr_samples, const int8_t* field_of_key, int n_keys, int64_t* n_records,
                        const vlr::RecHost** rec_host, int* used_serial_walk);
+// the BAM twin (vlr_bamstats.hip): split the buffered bytes into BAM records (SAM spec 4.2.1; plausibility of the fixed 32-byte head,
+// the same anchor / verified walk / serial fallback), no INFO scan; n_refs bounds the reference ids of a plausible head
+int vlr_dev_file_split_bam(vlr_dev_file* f, int64_t max_records, int n_refs, int64_t* n_records, int* used_serial_walk);
+// device pointers of the last split: the read position and the n + 1 record starts relative to it (valid until the next feed / split)
+int vlr_dev_file_split_view(vlr_dev_file* f, const uint8_t** d_base, const uint64_t** d_starts);
 // a shard's window begins inside a record: read position to the first record start (a guess the split's verified walk confirms)
 int vlr_dev_file_anchor_first(vlr_dev_file* f, int n_contigs, int n_hdr_samples, uint64_t* skipped);
 // record starts of the last split: n + 1 offsets from the read position (host copy, valid until the next split)
