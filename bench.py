@@ -6,11 +6,21 @@ loci + the all-gather of the full result records when N > 1.  Workload at N=1: B
 (tumor-normal with contamination, SNV+indel, 100x, 1M loci); weak scaling: every rank gets its own
 shard of that size.  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line (value, ms_per_step, the
+roofline of the timed launches).  Everything that takes runs or checks of its own comes with --full only.
+
+  --full                                      also the legs beyond the headline: the step with AFD lists (`with_afd`), host buffers
+                                              in and out (`pcie_inclusive`), observation BCFs -> calls BCF (`end_to_end`), the CPU
+                                              baselines and parity against the oracle, posterior normalisation and status counts of
+                                              the results; realign: the edit-distance pre-filter, CPU baseline and parity; ingest:
+                                              the host reader's rate.  --afd / --no-afd, --no-cpu-baseline, --cpu-loci and
+                                              --no-end-to-end select among these legs
+
   --workload config2|config3|config4|config5   BASELINE configs[1..4] (locus counts of the config, or --loci)
   --workload realign                          second hot path: read-vs-allele pair HMM, pairs/s
   --workload cli                              end to end through the process boundary: observation BCFs -> call variants -> calls BCF
-  --afd / --no-afd                            (default on) additionally time the step WITH the AFD lists (the reference always
-                                              computes AFD, calling.rs:889-928) and report it as `with_afd` in the same line;
+  --afd / --no-afd                            (default on) with --full, additionally time the step WITH the AFD lists (the reference
+                                              always computes AFD, calling.rs:889-928) and report it as `with_afd` in the same line;
                                               `value` stays the BASELINE metric (plain step), the roofline is the plain kernel's
   --gpus N                                    N > 1 without a torchrun environment: bench.py starts its own ranks
                                               (python -m torch.distributed.run --nproc-per-node N on 127.0.0.1) and relays rank 0's line
@@ -272,24 +282,27 @@ def bench_realign(args, rank, world, local_rank, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # the edit-distance pre-filter of the same pairs (calc_best_hit): its kernel time, and that the band it yields is the one the
-    # synthetic batch carries (host routine)
-    band_host = dp.t[5].clone()
-    dp.band_from_hits(local_rank, stream)
-    ev2, ev3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev2.record()
-    for _ in range(args.steps):
+    edit = None
+    if args.full:
+        # the edit-distance pre-filter of the same pairs (calc_best_hit): its kernel time, and that the band it yields is the one the
+        # synthetic batch carries (host routine)
+        band_host = dp.t[5].clone()
         dp.band_from_hits(local_rank, stream)
-    ev3.record()
-    torch.cuda.synchronize()
-    edit_ms = ev2.elapsed_time(ev3) / args.steps
-    bands_equal = bool(torch.equal(band_host, dp.t[5]))
+        ev2, ev3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev2.record()
+        for _ in range(args.steps):
+            dp.band_from_hits(local_rank, stream)
+        ev3.record()
+        torch.cuda.synchronize()
+        edit_ms = ev2.elapsed_time(ev3) / args.steps
+        edit = {"kernel_ms": edit_ms, "pairs_per_s": len(pb) / (edit_ms * 1e-3), "bands_equal_host_routine": bool(torch.equal(band_host, dp.t[5])),
+                "note": "vlr_edit_distance_batch + band update on the resident pairs, not part of `value`"}
     if rank != 0:
         return None
-    got = dp.out.cpu().numpy()
     n_pairs = len(pb)
     parity = cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
+        got = dp.out.cpu().numpy()
         from oracle import oracle
         cores = effective_cpus()
         n_cpu = min(len(base), args.cpu_loci or 40 * cores)
@@ -311,7 +324,7 @@ def bench_realign(args, rank, world, local_rank, dev):
                "sample": "first %d pairs of the same batch, %d threads, %.1f s" % (n_cpu, cores if mode == "exact" else 1, t_cpu)}
     achieved = dp.bytes / (kernel_ms * 1e-3) / 1e9
     cells = dp.cells
-    return {
+    line = {
         "metric": "read-allele pairs/sec (pair HMM, whole node)" if mode == "exact" else "read-allele pairs/sec (pair HMM mode %s, whole node)" % mode, "value": n_pairs * world * args.steps / elapsed, "unit": "pairs/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -323,10 +336,11 @@ def bench_realign(args, rank, world, local_rank, dev):
                      "valu": {"cells_per_s": cells / (kernel_ms * 1e-3), "flop_per_cell": FLOP_PER_CELL,
                               "achieved_tflops": cells * FLOP_PER_CELL / (kernel_ms * 1e-3) / 1e12, "peak_tflops": F64_VALU_PEAK_TFLOPS,
                               "frac": cells * FLOP_PER_CELL / (kernel_ms * 1e-3) / 1e12 / F64_VALU_PEAK_TFLOPS}},
-        "edit_distance_prefilter": {"kernel_ms": edit_ms, "pairs_per_s": n_pairs / (edit_ms * 1e-3), "bands_equal_host_routine": bands_equal,
-                                    "note": "vlr_edit_distance_batch + band update on the resident pairs, not part of `value`"},
-        "cpu_baseline": cpu, "parity": parity, "build_id": engine.build_id(),
+        "build_id": engine.build_id(),
     }
+    if args.full:
+        line.update({"edit_distance_prefilter": edit, "cpu_baseline": cpu, "parity": parity})
+    return line
 
 
 def self_launch(argv, n):
@@ -500,7 +514,7 @@ def bench_ingest(args, rank, world, local_rank, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     host = None
-    if rank == 0 and not args.no_cpu_baseline:   # the host reader on the same files and cores (product code, not the oracle): one pass
+    if rank == 0 and args.full and not args.no_cpu_baseline:   # the host reader on the same files and cores (product code, not the oracle): one pass
         th = time.perf_counter()
         one_pass(None)
         host = n_loci / (time.perf_counter() - th)
@@ -533,13 +547,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="config3", choices=["config2", "config3", "config4", "config5", "realign", "cli", "ingest"])
     ap.add_argument("--loci", type=int, default=None, help="loci per GPU (default: the config's size); realign: pairs per GPU")
-    ap.add_argument("--afd", dest="afd", action="store_true", default=True, help="(default) also time the step with the AFD lists")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the headline figure: with-AFD step, PCIe-inclusive and end-to-end rates, CPU baselines, parity "
+                         "and the checks on the results (realign: edit-distance pre-filter, CPU baseline, parity; ingest: host reader)")
+    ap.add_argument("--afd", dest="afd", action="store_true", default=True, help="(default) with --full, also time the step with the AFD lists")
     ap.add_argument("--no-afd", dest="afd", action="store_false", help="only the plain step")
     ap.add_argument("--dry-run", action="store_true", help="launcher and collective check without a GPU (gloo)")
     ap.add_argument("--afd-capacity", type=int, default=96)
     ap.add_argument("--cpu-loci", type=int, default=None, help="loci of the bounded CPU-baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive and observation-BCF -> calls-BCF legs of the default line")
+    ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive and observation-BCF -> calls-BCF legs of the --full line")
     ap.add_argument("--mode", default="exact", choices=["exact", "fast", "homopolymer"], help="realign workload: --pairhmm-mode of the reference (cli.rs:912-947)")
     ap.add_argument("--read-window", type=int, default=64, help="realign workload: realignment window; read windows are window..2*window bases (32: short reads, two pairs per wave)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -638,7 +655,7 @@ def main():
         dump_outputs(args.dump_outputs, {f: getattr(r, f) for f in ("ln_posterior", "ln_marginal", "map_vaf", "map_bias", "best_event", "status")})
 
     with_afd = None
-    if args.afd:
+    if args.full and args.afd:
         out_afd = engine.DeviceResults(batch.n_loci, plan.n_out, plan.n_samples, dev, afd_capacity=args.afd_capacity)
         step(out_afd)
         el_afd = timed(lambda: step(out_afd))
@@ -654,7 +671,7 @@ def main():
     # (calling.rs:889-928): host buffers in and out through vlr_batch_run_host (page-locked arrays, staging pipelined with the
     # kernels), without and with AFD lists; and the whole process boundary (observation BCFs -> call variants -> calls BCF)
     pcie = e2e = None
-    if world == 1 and not force_dist and args.workload == "config3" and not args.no_end_to_end:
+    if args.full and world == 1 and not force_dist and args.workload == "config3" and not args.no_end_to_end:
         import types
         pb = engine.pin_batch(batch)
         from varlociraptor_amd.batch import CallResults
@@ -686,15 +703,15 @@ def main():
         except Exception as ex:  # the front door must not take the kernel line down
             e2e = {"value": None, "note": "end-to-end leg failed: %r" % (ex,)}
 
-    res = out.to_host()
     line = None
     if rank == 0:
-        alg_bytes = dbatch.algorithmic_bytes() + res.ln_posterior.nbytes + res.map_vaf.nbytes + res.status.nbytes
+        alg_bytes = dbatch.algorithmic_bytes() + out.ln_posterior.nbytes + out.map_vaf.nbytes + out.status.nbytes
         achieved = alg_bytes / (last_ms * 1e-3) / 1e9
+        res = out.to_host() if args.full else None
         # ---- parity + CPU baseline on a bounded sample of the same workload (rank 0, N = 1 only)
         parity = None
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle
             from parity import compare
             cores = effective_cpus()
@@ -755,10 +772,6 @@ def main():
                 cpu["reference_binary"] = reference_binary_baseline(cfg, sub, n_cpu, cores)
             except Exception as ex:  # a probe must not take the bench line down
                 cpu["reference_binary"] = {"value": None, "note": "probe failed: %r" % (ex,)}
-        # posteriors must be normalised at full size (size-independent property)
-        ps = np.exp(res.ln_posterior)
-        ok = (res.status & 0xF) == 0
-        norm_err = float(np.abs(ps[ok].sum(axis=1) - 1.0).max()) if ok.any() else None
         terms_per_launch = n_terms / max(1, args.steps)
         tflops = terms_per_launch * FLOP_PER_TERM / (last_ms * 1e-3) / 1e12
         vstamp = valu_for(args.workload, engine.build_id(), n_loci, last_ms) or {}
@@ -784,15 +797,21 @@ def main():
                          "valu": {"pileup_evals_per_launch": n_eval // max(1, args.steps), "obs_terms_per_launch": int(terms_per_launch),
                                   "terms_per_s": terms_per_launch / (last_ms * 1e-3), "flop_per_term": FLOP_PER_TERM,
                                   "achieved_tflops": tflops, "peak_tflops": F64_VALU_PEAK_TFLOPS, "frac": tflops / F64_VALU_PEAK_TFLOPS}},
-            "with_afd": with_afd, "pcie_inclusive": pcie, "end_to_end": e2e,
-            "cpu_baseline": cpu if world == 1 else {"value": None, "note": "N=1 only (rank 0 times the CPU restatement on a bounded sample of the same workload)"},
-            "parity": parity if world == 1 else {"value": None, "note": "N=1 only (the sample compared with the oracle is taken at N=1; the N>1 path is covered by tests/test_distributed_cpu.py and tests/test_gpu_node.py)"},
-            "posterior_normalisation_max_err": norm_err,
-            "n1_only": None if world == 1 else "cpu_baseline, parity, pcie_inclusive and end_to_end are measured at N=1 only (rank 0, a bounded sample): null here by design; this line carries the whole-job rate, the per-rank kernel roofline and the collective",
-            "status_counts": {str(k): int(v) for k, v in zip(*np.unique(res.status, return_counts=True))},
             "collective": ("rccl all_gather_into_tensor, world size %d" % world) if (world > 1 or force_dist) else None,
             "build_id": engine.build_id(),
         }
+        if args.full:
+            # posteriors must be normalised at full size (size-independent property)
+            ps = np.exp(res.ln_posterior)
+            ok = (res.status & 0xF) == 0
+            line.update({
+                "with_afd": with_afd, "pcie_inclusive": pcie, "end_to_end": e2e,
+                "cpu_baseline": cpu if world == 1 else {"value": None, "note": "N=1 only (rank 0 times the CPU restatement on a bounded sample of the same workload)"},
+                "parity": parity if world == 1 else {"value": None, "note": "N=1 only (the sample compared with the oracle is taken at N=1; the N>1 path is covered by tests/test_distributed_cpu.py and tests/test_gpu_node.py)"},
+                "posterior_normalisation_max_err": float(np.abs(ps[ok].sum(axis=1) - 1.0).max()) if ok.any() else None,
+                "n1_only": None if world == 1 else "cpu_baseline, parity, pcie_inclusive and end_to_end are measured at N=1 only (rank 0, a bounded sample): null here by design; this line carries the whole-job rate, the per-rank kernel roofline and the collective",
+                "status_counts": {str(k): int(v) for k, v in zip(*np.unique(res.status, return_counts=True))},
+            })
         print(json.dumps(line))
     if world > 1 or force_dist:
         dist.destroy_process_group()

@@ -371,7 +371,7 @@ def test_bench_step_through_rccl_on_one_gpu(tmp_path):
     env = dict(os.environ, PYTHONPATH=root, VLR_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "1", "--loci", "20000", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-afd"], capture_output=True, text=True, cwd=root, env=env, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-afd"], capture_output=True, text=True, cwd=root, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["collective"].startswith("rccl") and line["n_gpus"] == 1 and line["value"] > 0

@@ -42,7 +42,7 @@ j = line("bench_config3_afd.json")
 if j and j.get("with_afd"):
     shutil.copy(os.path.join(O, "bench_config3_afd.json"), os.path.join(P, "%s_bench_config3_afd.json" % tag))
     a = j["with_afd"]
-    md += ["", "With AFD lists (`bench.py --afd`, capacity %d): %.3f M loci/s = %.0f %% of the plain rate (%.1f ms for call pass + log filter + replay of overflowed loci), mean %.1f points per sample list, %d truncated lists."
+    md += ["", "With AFD lists (`bench.py --full --afd`, capacity %d): %.3f M loci/s = %.0f %% of the plain rate (%.1f ms for call pass + log filter + replay of overflowed loci), mean %.1f points per sample list, %d truncated lists."
            % (a["afd_capacity"], a["value"] / 1e6, 100 * a["ratio_to_plain"], a["kernel_ms_both_launches"], a["mean_afd_points_per_sample"], a["truncated_lists"])]
 j = line("bench_cli.json")
 if j:
@@ -69,8 +69,8 @@ if os.path.exists(pi):
 if os.path.exists(os.path.join(O, "cpu_probe.txt")):
     shutil.copy(os.path.join(O, "cpu_probe.txt"), os.path.join(P, "%s_cpu_probe.txt" % tag))
 md += ["", "## rocprofv3 --kernel-trace --stats of `python bench.py --no-cpu-baseline` (config3, 1 M loci per launch)", "", rocpd("stats_config3"),
-       "## … of `python bench.py --afd --no-cpu-baseline`", "", rocpd("stats_config3_afd"),
-       "## … of `python bench.py --workload realign --no-cpu-baseline`", "", rocpd("stats_realign")]
+       "## … of `python bench.py --full --afd --no-cpu-baseline`", "", rocpd("stats_config3_afd"),
+       "## … of `python bench.py --workload realign --full --no-cpu-baseline`", "", rocpd("stats_realign")]
 sc = os.path.join(O, "stats_cli.md")
 if os.path.exists(sc):
     md += ["## … of `python bench.py --workload cli --steps 3 --warmup 1` (the whole pipeline: reader, evaluation, emission kernels on their streams; durations of kernels on the low-priority feed stream include the time they wait for CUs) and the union of the kernel intervals over the timed steps (`tools/timeline_busy.py`)", "", open(sc).read().rstrip(), ""]
