@@ -34,12 +34,14 @@
 extern "C" {
 #endif
 
-#define VLR_ABI_VERSION 8   /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
+#define VLR_ABI_VERSION 9   /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
                              * 5: sharded device reader, calls-file parts, vlr_ingest_device_trim, CRC32 of BGZF members checked by both readers;
                              * 6: calls emission on the device — vlr_results.afd_text (FORMAT/AFD text), OBS text in the observation summaries,
                              *    vlr_obs_table_summaries;
                              * 7: vlr_contamination_posterior (`estimate contamination`);
-                             * 8: vlr_bamstats_* (`estimate alignment-properties`) */
+                             * 8: vlr_bamstats_* (`estimate alignment-properties`);
+                             * 9: vlr_posterior_odds_keep, vlr_range_group_lse, vlr_calls_filter_odds, vlr_calls_mutational_burden
+                             *    (`filter-calls posterior-odds`, `estimate mutational-burden`) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -518,6 +520,76 @@ void vlr_bamstats_close(vlr_bamstats* s);
 enum { VLR_FDR_MODE_LOCAL = 1, VLR_FDR_MODE_SMART = 2, VLR_FDR_MODE_RETAIN_ARTIFACTS = 4 };
 int vlr_calls_filter_fdr(const char* in_path, const char* out_path, int n_events, const char* const* events, double alpha, uint32_t mode,
                          const char* vartype, int64_t minlen, int64_t maxlen, int device, int n_threads, int64_t* n_kept, int64_t* n_total);
+
+/* ------------------------------------------------------------------------------------------------
+ * Posterior odds (filtration/posterior_odds.rs:62-79): one decision per allele.  ln_target[i]: ln-sum over the PROB_* tags of
+ * the chosen events, ln_other[i]: ln-sum over every other PROB_* INFO tag of the header (both as utils::tags_prob_sum(.., None),
+ * utils/mod.rs:177-212); valid[i]: bit 0 = ln_target is a value, bit 1 = ln_other is a value (a sum without values is the
+ * reference's None; the double behind a cleared bit is not read for the decision).
+ *   keep[i] = both valid && level(e^(ln_other[i] - ln_target[i])) < min_level,
+ * level = bio's evidence_kass_raftery of the Bayes factor k: k <= 1 VLR_ODDS_NONE, <= 3 BARELY, <= 20 POSITIVE, <= 150 STRONG,
+ * else VERY_STRONG (a NaN k, e.g. -inf against -inf, fails every comparison: VERY_STRONG).  ln_other == ln_target gives k = 1
+ * exactly: NONE.  The device decides in log space on d = ln_other - ln_target: NONE for d < 2^-53 (exactly the d whose e^d a
+ * correctly rounded exp returns as <= 1), then d <= ln 3, ln 20, ln 150; next to the reference's e^d <= b a decision can differ
+ * only where d is within rounding of ln 3, ln 20 or ln 150.  n = 0 is legal.  Host pointers; uploads, launches on `device`,
+ * copies back. */
+enum { VLR_ODDS_NONE = 0, VLR_ODDS_BARELY = 1, VLR_ODDS_POSITIVE = 2, VLR_ODDS_STRONG = 3, VLR_ODDS_VERY_STRONG = 4 };
+int vlr_posterior_odds_keep(int device, int64_t n, const double* ln_target, const double* ln_other, const uint8_t* valid, int min_level, uint8_t* keep);
+
+/* ------------------------------------------------------------------------------------------------
+ * ln_sum_exp per (range, group) cell: the reduction of `estimate mutational-burden` (estimation/mutational_burden.rs:186-190,
+ * 214-346, where it is a BTreeMap range query, a hash grouping and a ln_sum_exp per minimum VAF).  n entries (vaf, ln_prob,
+ * group in [0, n_groups)); n_ranges half-open ranges [lo[r], hi[r]) (hi = +inf: open).  An entry is in range r when
+ * lo[r] <= vaf && vaf < hi[r] as f64 comparisons with the tabulated bounds — every range is tested on its own bounds (the
+ * reference's ranges are no partition: neighbouring histogram edges are computed separately and may differ by an ulp).
+ *   out[r * n_groups + g] = m + ln1p((c - 1) + S): m = maximum ln_prob of the cell, c = number of entries equal to m,
+ *   S = sum of e^(ln_prob - m) over the entries below m (bio ln_sum_exp); -inf for a cell without
+ *   entries or with only -inf entries.
+ * Summation order of S (fixed: independent of the launch geometry, the scheduling and of how the entries were uploaded): the
+ *   entries in chunks of VLR_LSE_CHUNK consecutive ones; within a chunk a cell's terms are added sequentially in entry order
+ *   starting from 0.0; a cell's chunk sums are added sequentially in chunk order starting from 0.0.  m and c do not depend on
+ *   any order.  No atomics: the same input gives the same bits.
+ * n = 0 is legal (every cell -inf, no device is touched).  A NaN vaf is in no range (dropping it is the caller's business); a
+ *   NaN ln_prob makes its cells NaN.  A group outside [0, n_groups), n_ranges outside [1, VLR_LSE_MAX_RANGES] or n_groups
+ *   outside [1, VLR_LSE_MAX_GROUPS] = VLR_ERR_INVALID_ARGUMENT.  Host pointers; uploads, launches on `device`, copies back. */
+#define VLR_LSE_CHUNK      4096
+#define VLR_LSE_MAX_RANGES 128
+#define VLR_LSE_MAX_GROUPS (14 * VLR_MAX_SAMPLES)
+int vlr_range_group_lse(int device, int64_t n, const double* vaf, const double* ln_prob, const int32_t* group, int n_ranges, const double* lo,
+                        const double* hi, int n_groups, double* out);
+
+/* Diagnostics: device time in milliseconds (a hipEvent pair around the launches, copies excluded) of the kernels of this thread's
+ * last vlr_range_group_lse (also inside vlr_calls_mutational_burden) and last vlr_posterior_odds_keep; either pointer may be NULL. */
+int vlr_callstats_last_kernel_ms(double* range_group_lse_ms, double* posterior_odds_ms);
+
+/* The whole of `varlociraptor filter-calls posterior-odds` (filtration/posterior_odds.rs:19-82): read the calls BCF `in_path`;
+ * the header's PROB_* INFO descriptions must be PHRED scaled (utils::is_phred_scaled, utils/mod.rs:421-446: each ends with
+ * "(PHRED)" or does not end with ")"), otherwise error "Event probabilities are not PHRED scaled" and no output file.  Target
+ * tags: PROB_<UPPER CASE event> (utils::events_to_tags); other tags: the header's PROB_* INFO ids whose suffix equals none of
+ * the event names AS GIVEN (posterior_odds.rs:39-52 — an event given in lower case is therefore summed on both sides, as in the
+ * reference).  Per typed variant both ln-sums are formed here (record typing and tags_prob_sum as vlr_calls_filter_fdr's), the
+ * decisions are made on `device` (vlr_posterior_odds_keep); a record is kept when any of its alleles is kept and is written byte
+ * for byte with the input's header to the BCF `out_path`.  Deviation: the reference trims the removed alleles of a kept record
+ * (Record::remove_alleles); this writes the record untrimmed — the same thing for the single-ALT records `call variants` writes.
+ * min_level: VLR_ODDS_* (the --odds argument).  n_kept / n_total may be NULL. */
+int vlr_calls_filter_odds(const char* in_path, const char* out_path, int n_events, const char* const* events, int min_level, int device, int n_threads,
+                          int64_t* n_kept, int64_t* n_total);
+
+/* The record pass and the reduction of `varlociraptor estimate mutational-burden` (estimation/mutational_burden.rs:93-190): read
+ * the annotated calls BCF `in_path`; per record take FORMAT/AF of each of `samples` (a name the header lacks: error "Sample <name>
+ * not found"); skip records that are not coding (is_valid_variant, :18-43: some ANN entry has |-field 7 == "protein_coding" and a
+ * non-empty field 13; no ANN = not coding) or that lack one of the events' PROB_<UPPER CASE> tags (:141-156); the allele
+ * probability is ln_add_exp over the events of the PHRED value as ln, starting from -inf; the signature is signatures()
+ * (:482-515) with the 14 classes in declaration order DEL METH INS INV DUP BND MNV Complex C>A C>G C>T T>A T>C T>G (an SNV whose
+ * bases are not ACGT is an error that names the record; the reference panics).  One entry per (sample, allele) whose AF is neither
+ * NaN nor missing: (AF widened to f64, probability, group), in record order and within a record by sample name (byte order, as
+ * the reference's BTreeMap of samples iterates), then allele.  group = index of the sample in `samples` * 14 + signature with by_sample != 0 (multibar mode: the key is (vartype, sample)), else the
+ * signature alone (hist, curve and table modes: the reference keys on vartype only).  No entry at all: error "unable to estimate TMB
+ * because no valid records were found in the given BCF/VCF" (errors.rs:32).  out_cells[r * G + g], G = by_sample ? n_samples * 14 : 14: vlr_range_group_lse of the entries over the given
+ * ranges on `device` (the entries are uploaded in pieces, which does not change a bit); *n_entries may be NULL.  The per-megabase
+ * scaling and the output are the caller's (varlociraptor_amd/burden.py). */
+int vlr_calls_mutational_burden(const char* in_path, int n_events, const char* const* events, int n_samples, const char* const* samples, int by_sample,
+                                int n_ranges, const double* lo, const double* hi, int device, int n_threads, double* out_cells, int64_t* n_entries);
 
 /* Diagnostics: the DEVICE build of the platform-independent decision arithmetic (include/vlr_detmath.h; which = 0 det_exp,
  * 1 det_log1p_pos, 2 det_log2_ratio(a, b), 3 det_exp2) and of the kernel's mantissa logarithm (4), element-wise on host

@@ -1,5 +1,6 @@
 """`python -m varlociraptor_amd call variants generic --scenario S.yaml --obs name=path.vcf ... [> calls.vcf]`
-(also `filter-calls control-fdr` and `estimate contamination`, contamination.py)
+(also `filter-calls control-fdr`, `filter-calls posterior-odds` (odds.py), `estimate contamination` (contamination.py) and
+`estimate mutational-burden` (burden.py))
 
 Mirror of the reference's `call variants` surface (src/cli.rs:684-735) for text observation VCFs (format v15):
 `generic` with a scenario YAML (grammar/mod.rs:129-144) and `tumor-normal --tumor --normal --purity`
@@ -757,7 +758,22 @@ def main(argv=None):
     cf.add_argument("--maxlen", type=int)
     cf.add_argument("--device", default="cpu")
     cf.add_argument("--output", "-o", help="BCF file for the kept records (default: a CHROM/POS/ID/REF/ALT table on stdout)")
+    po = fc.add_parser("posterior-odds", help="keep the alleles whose odds against the given events stay below --odds (cli.rs:812-824)")
+    po.add_argument("calls")
+    po.add_argument("--events", nargs="+", required=True)
+    po.add_argument("--odds", choices=["none", "barely", "positive", "strong", "very-strong"], required=True, help="Kass-Raftery evidence at which an allele is removed")
+    po.add_argument("--device", default="0", help="HIP device index, or 'cpu' for the Python restatement")
+    po.add_argument("--output", "-o", help="BCF file for the kept records (default: a CHROM/POS/ID/REF/ALT table on stdout)")
     est = sub.add_parser("estimate").add_subparsers(dest="what", required=True)
+    emb = est.add_parser("mutational-burden", help="expected coding variants per megabase by minimum VAF from annotated calls (cli.rs:493-530)")
+    emb.add_argument("calls")
+    emb.add_argument("--events", nargs="+", required=True)
+    emb.add_argument("--sample", nargs="+", required=True, dest="samples")
+    emb.add_argument("--coding-genome-size", type=float, default=3e7)
+    emb.add_argument("--mode", choices=["hist", "curve", "multibar", "table"], required=True)
+    emb.add_argument("--vaf-cutoff", type=float, default=0.2, help="minimum VAF of the multibar mode")
+    emb.add_argument("--device", default="0", help="HIP device index, or 'cpu' for the Python restatement")
+    emb.add_argument("--output", "-o", help="output file (default stdout)")
     ea = est.add_parser("alignment-properties", help="estimate insert size, CIGAR maxima, gap / homopolymer parameters and the wildtype "
                         "homopolymer error model of a sample (cli.rs:423-448)")
     ea.add_argument("reference", help="FASTA file of the reference genome (indexed with samtools faidx)")
@@ -792,6 +808,15 @@ def main(argv=None):
         if rc:
             sys.exit(rc)
         return
+    if a.cmd == "estimate" and a.what == "mutational-burden":
+        from . import burden
+        out = open(a.output, "w") if a.output else None
+        try:
+            burden.estimate(a.calls, a.events, a.samples, a.coding_genome_size, a.mode, cutoff=a.vaf_cutoff, device=a.device, out=out)
+        finally:
+            if out:
+                out.close()
+        return
     if a.cmd == "estimate":
         # cli.rs:1292-1298: both prior options or neither, and at least one cell
         if (a.prior_estimate is None) != (a.prior_considered_cells is None) or (a.prior_considered_cells is not None and a.prior_considered_cells <= 0):
@@ -800,6 +825,29 @@ def main(argv=None):
         prior = (a.prior_estimate, a.prior_considered_cells) if a.prior_estimate is not None else None
         contamination.estimate_contamination(a.sample, a.contaminant, output=a.output, output_plot=a.output_plot,
                                              output_max_vaf_variants=a.output_max_vaf_variants, prior_estimate=prior, device=a.device)
+        return
+    if a.cmd == "filter-calls" and a.what == "posterior-odds":
+        from . import odds
+        from .bcfio import BcfReader
+        min_level = odds.LEVELS.index(a.odds)
+        if a.output and a.device != "cpu" and os.environ.get("VLR_INGEST", "native") != "python":
+            # the whole command in the engine (vlr_calls_filter_odds): BCF in, kept records out, decisions on the device
+            kept_n, total_n = odds.filter_calls_native(a.calls, a.output, a.events, min_level, device=odds._device_index(a.device))
+            print(f"{kept_n} of {total_n} records kept", file=sys.stderr)
+            return
+        r = BcfReader(a.calls)
+        recs = list(r)
+        kept = odds.filter_by_odds(recs, r.header_lines, a.events, min_level, device=a.device)
+        if a.output:
+            from .bcfio import BcfWriter
+            with BcfWriter(a.output, r.header_text) as w:
+                for rec in kept:
+                    w.write_raw(rec["raw"])
+        else:
+            print("#CHROM\tPOS\tID\tREF\tALT")
+            for rec in kept:
+                print("\t".join(str(rec[k]) for k in ("chrom", "pos", "id", "ref", "alt")))
+        print(f"{len(kept)} of {len(recs)} records kept", file=sys.stderr)
         return
     if a.cmd == "filter-calls":
         from . import fdr
