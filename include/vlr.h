@@ -365,6 +365,11 @@ int  vlr_plan_reserve(vlr_plan* plan, int64_t n_loci, int with_afd);
  * measured with HIP events on the launch stream (synchronises on the stop event).  For bench.py.       */
 int  vlr_plan_last_kernel_ms(vlr_plan* plan, float* ms);
 
+/* Measurement aid: which build of the call kernel the plan's most recent call launch took — *waves: its instance (waves per SIMD:
+ * 2, 3, 4 or 6), *lean: 1 for the lean build (plans that need none of what it leaves out, launched without AFD lists;
+ * VLR_NO_LEAN=1 forces the general build), 0 for the general or the wide build.                        */
+int  vlr_plan_last_instance(const vlr_plan* plan, int* waves, int* lean);
+
 /* Profiling aid: cumulative {pileup-likelihood evaluations, observation terms} executed by the kernels of this
  * plan since creation (or the last reset); synchronises the device.                                     */
 int  vlr_plan_work_counters(vlr_plan* plan, unsigned long long* out2, int reset);

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Register / spill / size notes of the call kernel instances inside a built libvlr (the .hip_fatbin section is unbundled first).
+# Register / spill / size notes of the call kernel instances of every unit (general, lean, deep, wide, widedeep) inside a built libvlr
+# (the .hip_fatbin section is unbundled first).
 #   tools/codeobj_stats.sh [path/to/libvlr.so]
 L=/opt/rocm/lib/llvm/bin
 SO=${1:-$(dirname "$0")/../varlociraptor_amd/libvlr.so}
@@ -34,6 +35,8 @@ for blk in re.split(r'\n\s+- (?=\.a)', t):   # one block per kernel (its keys ar
     g = lambda k: (re.search(r'\.%s:\s+(\d+)' % k, blk) or [0, '?'])[1]
     print(nm.group(1)[:60], 'vgpr', g('vgpr_count'), 'vspill', g('vgpr_spill_count'), 'sgpr', g('sgpr_count'), 'sspill', g('sgpr_spill_count'), 'lds', g('group_segment_fixed_size'), 'scratch', g('private_segment_fixed_size'))
 "
+  # code bytes per call-kernel instance (size of the kernel's function symbol; the namespace tells the unit: vlr, vlr_lean, vlr_deep, vlr_wide, ...)
+  $L/llvm-readelf -sW $f 2>/dev/null | awk '$4 == "FUNC" && $8 ~ /vlr_call_kernel/ {print substr($8, 1, 60), "code", $3}' | sort -u
   ls -l $f | awk "{print \"code object bytes\", \$5}"
 done
 rm -rf $W

@@ -30,12 +30,16 @@ extern "C" int vlr_launch_call_kernel_widedeep(const vlr::DevPlanT<16>* plan_hos
                                                int n_univ, int n_samples, int range_depth, void* stream);
 extern "C" int vlr_launch_afd_kernel_wide(const vlr::DevPlanT<16>* plan_host, const vlr::DevBatch* batch, const vlr::DevResults* out, void* stream);
 extern "C" int vlr_launch_call_kernel_wide(const vlr::DevPlanT<16>* plan_dev, const vlr::DevBatch* batch, const vlr::DevResults* out,
-                                           int n_univ, int n_samples, int max_obs, int range_depth, void* stream);
+                                           int n_univ, int n_samples, int max_obs, int range_depth, void* stream, int* waves_out);
 extern "C" int vlr_launch_call_kernel(const vlr::DevPlanT<8>* plan_dev, const vlr::DevBatch* batch, const vlr::DevResults* out,
-                                      int n_univ, int n_samples, int max_obs, int range_depth, void* stream);
+                                      int n_univ, int n_samples, int max_obs, int range_depth, void* stream, int* waves_out);
 // LDS a workgroup of the plan needs before any coefficient area (call pass, AFD replay, AFD log filter; vlr_kernels.hip)
 extern "C" long long vlr_plan_lds_floor(const vlr::DevPlanT<8>* plan_host, int n_univ, int n_samples, int range_depth);
 extern "C" long long vlr_launch_call_lds_bytes(const vlr::DevPlanT<8>* plan_host, int n_univ, int n_samples, int max_obs, int range_depth);
+// the lean build of the call kernel (vlr_kernels_lean.hip) for plans with plan->lean_ok, launched without AFD lists
+extern "C" int vlr_launch_call_kernel_lean(const vlr::DevPlanT<8>* plan_dev, const vlr::DevBatch* batch, const vlr::DevResults* out,
+                                           int n_univ, int n_samples, int max_obs, int range_depth, void* stream, int* waves_out);
+extern "C" long long vlr_launch_call_lds_bytes_lean(const vlr::DevPlanT<8>* plan_host, int n_univ, int n_samples, int max_obs, int range_depth);
 extern "C" long long vlr_plan_lds_floor_wide(const vlr::DevPlanT<16>* plan_host, int n_univ, int n_samples, int range_depth);
 
 namespace {
@@ -259,6 +263,8 @@ struct vlr_plan {
     int device = 0;
     vlr::DevPlanT<16> host{};  // host copy (device pointers inside): the layout for up to sixteen samples
     long long lds_b0 = -2;     // LDS bytes of a call-kernel workgroup without coefficient area (fit_budget; -2: not asked yet)
+    bool lean_ok = false;      // no path of this plan needs what the lean build of the call kernel leaves out (vlr_plan_create)
+    int last_waves = 0, last_lean = 0;  // instance (waves per SIMD) and unit of the last call launch (vlr_plan_last_instance)
     bool wide = false;         // more than eight samples, four l2fc terms or four nested ranges on a path: the wide build of the kernels
     vlr::DevPlanT<8> host8{};  // the same plan in the layout of the standard and deep builds (plans of at most eight samples)
     vlr::DevPlanT<16>* dev = nullptr;
@@ -817,6 +823,36 @@ int vlr_plan_create(const vlr_scenario_desc* d, int device, vlr_plan** out) {
         }
     }
 
+    // ---- may the plan run the lean build of the call kernel (vlr_kernels_lean.hip)?  Everything that build leaves out must be
+    // unreachable for every locus: no l2fc node, two samples, tables of at most 64 entries, and every root (the probe pass
+    // sees the first 64) one of
+    //   - a flattened all-discrete root (never walked),
+    //   - a compiled chain root — all of them integrating the same sample, so that none is ever handed to the general pass,
+    //   - a proper Range node over one leaf Range node, known to the event loop as not deferrable (kind 2): its walk is one outer
+    //     frame whose rounds run as row-parallel batches.
+    // Single-sample plans would qualify too but keep the general unit: their 6-wave instance measured 3.5-5 % slower in the lean
+    // build (profiles/lean_unit.md).
+    bool lean_ok = !needs_wide && S == 2 && S <= kXcdMapMaxSamples && max_lfc == 0 && P.table_cap <= 64 && froot.size() <= 64;
+    {
+        int chain_inner = -1;
+        for (size_t i = 0; i < froot.size() && lean_ok; ++i) {
+            if (droot[2 * i] >= 0) continue;
+            if (froot[i].kind == 1) {
+                if (chain_inner >= 0 && chain_inner != froot[i].inner) lean_ok = false;
+                chain_inner = froot[i].inner;
+                continue;
+            }
+            const DevNode& r0 = nodes[i == 0 ? P.absent_root : roots[i - 1]];
+            bool ok = froot[i].kind == 2 && r0.kind == VLR_NODE_SAMPLE && r0.vafs.kind == VLR_SPECTRUM_RANGE && r0.vafs.start != r0.vafs.end &&
+                      r0.n_children == 1;
+            if (ok) {
+                const DevNode& ch = nodes[child[r0.child_off]];   // leaf_range_child() of the kernel
+                ok = ch.kind == VLR_NODE_SAMPLE && ch.vafs.kind == VLR_SPECTRUM_RANGE && ch.n_children == 0 && ch.vafs.start != ch.vafs.end;
+            }
+            if (!ok) lean_ok = false;
+        }
+    }
+
     rc = check_device(device);
     if (rc != VLR_OK) return rc;
     HIP_TRY(hipSetDevice(device));
@@ -868,6 +904,12 @@ int vlr_plan_create(const vlr_scenario_desc* d, int device, vlr_plan** out) {
     plan->host = P;
     plan->wide = needs_wide;
     if (S <= 8) plan->host8 = narrow_plan(P);
+    if (lean_ok) {   // ... and only where a workgroup of the lean unit has the LDS footprint of the general one, which fit_budget sizes pileup budgets with
+        const long long bl = vlr_launch_call_lds_bytes_lean(&plan->host8, P.n_univ, S, 0, P.max_range_depth);
+        const long long bg = vlr_launch_call_lds_bytes(&plan->host8, P.n_univ, S, 0, P.max_range_depth);
+        if (bl < 0 || bg < 0) (void)hipGetLastError();
+        plan->lean_ok = bl >= 0 && bl == bg;
+    }
     {   // The tables of the plan (Set candidates, the replay's lists of seen discrete operands: S x max_set doubles each) must leave room
         // for at least a minimal pileup in the 160 KiB of LDS a CU has; otherwise the first batch would fail with a launch error.
         const long long floor_b = !needs_wide ? vlr_plan_lds_floor(&plan->host8, P.n_univ, S, P.max_range_depth) : vlr_plan_lds_floor_wide(&plan->host, P.n_univ, S, P.max_range_depth);
@@ -966,6 +1008,7 @@ static int fit_budget(vlr_plan* plan, const uint32_t* off, int64_t l0, int64_t l
     for (int64_t l = l0; l < l1; ++l) mx = std::max(mx, off[(l + 1) * S] - off[l * S]);
     int best = std::min<int>(cap_budget, (int)mx);
     if (plan->wide || getenv("VLR_NO_FIT_BUDGET")) return best;
+    // (one number serves the general and the lean unit: vlr_plan_create only sets lean_ok where their footprints are equal)
     if (plan->lds_b0 == -2) {
         plan->lds_b0 = vlr_launch_call_lds_bytes(&plan->host8, plan->host.n_univ, S, 0, plan->host.max_range_depth);
         if (plan->lds_b0 < 0) (void)hipGetLastError();
@@ -1122,9 +1165,17 @@ int vlr_batch_run(vlr_plan* plan, const vlr_batch* in, vlr_results* out, void* s
     HIP_TRY(hipEventRecord(plan->ev_start, st));
     // plans beyond the standard build's limits (vlr_plan.h) run the wide build of the kernels (vlr_kernels_wide.hip)
     const bool wide = plan->wide;
+    // ... plans that need nothing of what the lean build leaves out, launched without AFD lists, the lean build (vlr_kernels_lean.hip;
+    // VLR_NO_LEAN=1, read per launch: the general build)
+    const bool lean = plan->lean_ok && !want_afd && !wide && !getenv("VLR_NO_LEAN");
     auto call_launch = [&](const DevBatch* bb, const DevResults* rr, int mo, void* ss) {
-        return wide ? vlr_launch_call_kernel_wide(&plan->host, bb, rr, plan->host.n_univ, plan->host.S, mo, plan->host.max_range_depth, ss)
-                    : vlr_launch_call_kernel(&plan->host8, bb, rr, plan->host.n_univ, plan->host.S, mo, plan->host.max_range_depth, ss);
+        if (lean) {
+            plan->last_lean = 1;
+            return vlr_launch_call_kernel_lean(&plan->host8, bb, rr, plan->host.n_univ, plan->host.S, mo, plan->host.max_range_depth, ss, &plan->last_waves);
+        }
+        plan->last_lean = 0;
+        return wide ? vlr_launch_call_kernel_wide(&plan->host, bb, rr, plan->host.n_univ, plan->host.S, mo, plan->host.max_range_depth, ss, &plan->last_waves)
+                    : vlr_launch_call_kernel(&plan->host8, bb, rr, plan->host.n_univ, plan->host.S, mo, plan->host.max_range_depth, ss, &plan->last_waves);
     };
     auto afd_launch = [&](const DevBatch* bb, const DevResults* rr, void* ss) {
         return wide ? vlr_launch_afd_kernel_wide(&plan->host, bb, rr, ss) : vlr_launch_afd_kernel(&plan->host8, bb, rr, ss);
@@ -1220,6 +1271,14 @@ int vlr_batch_run(vlr_plan* plan, const vlr_batch* in, vlr_results* out, void* s
         HIP_TRY(hipEventRecord(plan->ev_stop, st));
     }
     plan->timed = true;
+    return VLR_OK;
+}
+
+// measurement aid: the call-kernel instance (waves per SIMD) and unit (1: lean build, 0: general or wide build) of the plan's last call launch
+int vlr_plan_last_instance(const vlr_plan* plan, int* waves, int* lean) {
+    if (!plan || !waves || !lean) return fail(VLR_ERR_INVALID_ARGUMENT, "null argument");
+    if (!plan->last_waves) return fail(VLR_ERR_INVALID_ARGUMENT, "no batch has been run on this plan");
+    *waves = plan->last_waves; *lean = plan->last_lean;
     return VLR_OK;
 }
 

@@ -33,6 +33,24 @@
 #else
 #define VLR_DEEP 0
 #endif
+// Lean build (vlr_kernels_lean.hip includes this file with VLR_LEAN_BUILD and the namespace renamed): the same call kernel with
+// everything compiled out that the host has proved unreachable for the plan and the launch (vlr_host.cpp: the lean_ok block of vlr_plan_create, vlr_batch_run) —
+// never anything that depends on the data of a locus.  The traits gate the existing run-time tests in place (`kHasX && test`); what
+// remains computes for a locus exactly what the general build computes for it.
+#ifdef VLR_LEAN_BUILD
+#define VLR_LEAN 1
+#else
+#define VLR_LEAN 0
+#endif
+constexpr bool kHasAfd = !VLR_LEAN;          // AFD log writes, map_disc            (lean: no afd_* result pointers, afd_log == nullptr)
+constexpr bool kHasReplay = !VLR_LEAN;       // AFD replay launch, afd_consider / afd_finish                    (lean: replay == 0)
+constexpr bool kHasLfc = !VLR_LEAN;          // l2fc operands on the path and their checks                 (lean: no l2fc node in the plan)
+// The general walk: Set / Branch frames, Variant / True / False nodes, discrete leaves, the probe pass of walk_root, outer Range
+// frames that take their points one by one and the single-chain runner run_leaf_chain.  Lean: every root of the plan is a flattened
+// all-discrete root, a compiled chain root (all of them integrating the same sample) or a proper Range over one leaf Range with
+// tables of at most 64 entries — walk_root only ever meets the last kind, from its root node, outside the probe pass.
+constexpr bool kHasGeneralWalk = !VLR_LEAN;
+constexpr bool kHasManySamples = !VLR_LEAN;  // plans above kXcdMapMaxSamples samples                                 (lean: S <= 2)
 
 namespace vlr {
 
@@ -1015,6 +1033,8 @@ struct Ctx {
     PROF_DECL
 };
 
+__device__ __forceinline__ int nlfc_of(const Ctx& c) { return kHasLfc ? c.nlfc : 0; }  // l2fc terms on the current path
+
 // Prior::compute via the host-built class table (prior.rs:715-762; see vlr_host.cpp build_prior_table)
 __device__ inline int prior_class(const DevPlan& p, int s, double v) {
     if (p.prior_kind[s] == PK_UNIFORM) {
@@ -1240,7 +1260,7 @@ __device__ inline bool group_contains(Ctx& c, int g, int inner, double x, int ex
     const DevPlan& p = *c.plan;
     WaveSt* w = c.w;
     int r0 = (g == 0) ? 0 : ldc(p.root_off + g - 1), r1 = (g == 0) ? 1 : ldc(p.root_off + g);
-    int full = (1 << c.nlfc) - 1;
+    int full = (1 << nlfc_of(c)) - 1;
     bool result = false;
     for (int ri = r0; ri < r1 && !result; ++ri) {
         int sp = 0;
@@ -1256,9 +1276,9 @@ __device__ inline bool group_contains(Ctx& c, int g, int inner, double x, int ex
                 if (nd.sample == excl) { result = true; continue; }  // vaftree.rs:124-128: excluded sample => true
                 double v = (nd.sample == inner) ? x : w->ops_vaf[nd.sample];
                 contained = spectrum_contains(nd.vafs, p.vafs, v);
-            } else if (nd.kind == VLR_NODE_LFC) {
+            } else if (kHasLfc && nd.kind == VLR_NODE_LFC) {
                 bool found = false;
-                for (int i = 0; i < c.nlfc; ++i)
+                for (int i = 0; i < nlfc_of(c); ++i)
                     if ((mask >> i) & 1)
                         if (w->lfc_a[i] == nd.sample && w->lfc_b[i] == nd.sample_b && w->lfc_cmp[i] == nd.cmp && w->lfc_val[i] == nd.lfc_value) {
                             found = true;
@@ -1318,7 +1338,7 @@ __device__ inline void cross_consider(Ctx& c, int g, double joint, int inner, do
 //   record = header word | S outer operands | nlfc x 2 words (l2fc terms on the path) | payload
 //   header: n (16 bits) | integrated sample + 1 (5) | is_discrete mask (16) | event group (8) | nlfc (4) | kind (2)
 //   kind 1: the visited-point table of a Range chain: n x values, then n joint values;  kind 2: one discrete leaf: its joint
-__device__ __forceinline__ bool log_on(const Ctx& c) { return c.lg != nullptr && c.hyp == 0 && !c.replay && c.lg_pos >= 0; }
+__device__ __forceinline__ bool log_on(const Ctx& c) { return kHasAfd && c.lg != nullptr && c.hyp == 0 && !c.replay && c.lg_pos >= 0; }
 __device__ __forceinline__ long long log_header(int kind, int n, int s_in, int disc, int group, int nlfc) {
     return (long long)n | ((long long)(s_in + 1) << 16) | ((long long)(disc & 0xffff) << 21) | ((long long)(group & 0xff) << 37) |
            ((long long)(nlfc & 0xf) << 45) | ((long long)kind << 49);
@@ -1338,7 +1358,7 @@ __device__ __forceinline__ int log_reserve(Ctx& c, int words) {
 }
 // header + operands + l2fc terms of the CURRENT context (walk state); returns the payload position or -1
 __device__ inline int log_begin(Ctx& c, int kind, int n, int s_in, int disc, int payload_words) {
-    const int S = c.S, nl = c.nlfc;
+    const int S = c.S, nl = nlfc_of(c);
     const int at = log_reserve(c, 1 + S + 2 * nl + payload_words);
     if (at < 0) return -1;
     WaveSt* w = c.w;
@@ -1531,7 +1551,7 @@ __device__ inline double eval_discrete_root(Ctx& c, int l0, int l1) {
 // hash of the ordered list stands for it (0 = no terms).
 __device__ inline long long lfc_ctx_key(const Ctx& c) {
     unsigned long long h = 0;
-    for (int i = 0; i < c.nlfc; ++i) {
+    for (int i = 0; i < nlfc_of(c); ++i) {
         const unsigned long long t = (unsigned long long)(unsigned)c.w->lfc_a[i] | ((unsigned long long)(unsigned)c.w->lfc_b[i] << 8) |
                                      ((unsigned long long)(unsigned)c.w->lfc_cmp[i] << 16) | ((unsigned long long)(i + 1) << 24);
         h = (h ^ t) * 0x9E3779B97F4A7C15ull;
@@ -1539,7 +1559,7 @@ __device__ inline long long lfc_ctx_key(const Ctx& c) {
         h = (h ^ (unsigned long long)__double_as_longlong(c.w->lfc_val[i])) * 0xBF58476D1CE4E5B9ull;
         h ^= h >> 32;
     }
-    return c.nlfc ? (long long)(h | 1ull) : 0ll;
+    return nlfc_of(c) ? (long long)(h | 1ull) : 0ll;
 }
 __device__ inline void afd_consider(Ctx& c, double joint, int inner, double x, int skip_sample = -1) {
     if (c.hyp != 0 || c.afd_mute) return;
@@ -1661,7 +1681,7 @@ __device__ inline void map_all(Ctx& c, double joint, int inner, double x, bool o
 
 // GenericLikelihood::compute step 1 (modes/generic.rs:503-509) for a leaf operand set
 __device__ inline bool lfcs_ok(const Ctx& c, int inner, double x) {
-    for (int i = 0; i < c.nlfc; ++i) {
+    for (int i = 0; i < nlfc_of(c); ++i) {
         int sa = c.w->lfc_a[i], sb = c.w->lfc_b[i];
         double va = (sa == inner) ? x : c.w->ops_vaf[sa];
         double vb = (sb == inner) ? x : c.w->ops_vaf[sb];
@@ -1693,7 +1713,7 @@ __device__ inline double leaf_joint(Ctx& c) {
     TRC(c, 125, joint);
     if (joint != joint) c.status |= VLR_LOCUS_NAN;
     if (log_on(c)) log_leaf(c, joint);
-    if (__builtin_expect(c.replay != 0, 0)) afd_consider(c, joint, -1, 0.0);
+    if (kHasReplay && __builtin_expect(c.replay != 0, 0)) afd_consider(c, joint, -1, 0.0);
     else map_all(c, joint, -1, 0.0, c.contained != 0, c.alive);
     PROF_ADD(c, 22);  // leaf: MAP candidates
     return joint;
@@ -1874,7 +1894,7 @@ __device__ __forceinline__ double run_leaf_chain(Ctx& c, RangeSt& rl, double* tx
             reduce_terms<1, 16>(P1, E1);
             const double lik = fixed + (log(P1[0]) + (double)E1[0] * kLn2) + dep_shift;
             double jv;
-            if (c.nlfc > 0 && !lfcs_ok(c, inner, xr)) jv = VLR_NEG_INF;
+            if (nlfc_of(c) > 0 && !lfcs_ok(c, inner, xr)) jv = VLR_NEG_INF;
             else {
                 int cls = cls_fast ? (xr == 0.0 ? 0 : 1) : prior_class(p, inner, xr);
                 jv = (cls == 0 ? pr0 : cls == 1 ? pr1 : cls == 2 ? pr2 : ptab[pidx + cls * istride]) + lik;
@@ -1895,7 +1915,7 @@ __device__ __forceinline__ double run_leaf_chain(Ctx& c, RangeSt& rl, double* tx
         const alive_t al2 = alive_c ? alive_update(c, alive_c, inner, x) : 0;
         const bool slow = __ballot(owner && (!own_in || al2 != 0)) != 0ull;
         (void)joint;
-        if (c.replay) {
+        if (kHasReplay && c.replay) {
             for (int i = 0; i < np; ++i) {
                 double xi = uni_d(pend[i]);
                 if (!table_has(tx, tn + i, xi, lane)) afd_consider(c, uni_d(vals[i]), inner, xi);
@@ -2344,7 +2364,7 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
             double lm = ln_mantissa(Psel);
             if (__builtin_expect(ones_on, 0)) lm = ln_product_mantissa(Psel);  // (a direct all-ones product may be exactly zero)
             const double lik = q.fixed + (lm + (double)Esel * kLn2);
-            if (__builtin_expect(c.nlfc > 0, 0) && !lfcs_ok(c, q.inner, x)) joint = VLR_NEG_INF;
+            if (__builtin_expect(nlfc_of(c) > 0, 0) && !lfcs_ok(c, q.inner, x)) joint = VLR_NEG_INF;
             else if (__builtin_expect(all_fast, 1)) joint = (x == 0.0 ? q.pr0 : q.pr1) + lik;  // every row inside a uniform-prior universe: class 0 at exactly 0, else 1
             else {
                 const int cls = q.cls_fast ? (x == 0.0 ? 0 : 1) : prior_class(p, q.inner, x);
@@ -2568,9 +2588,9 @@ __device__ __forceinline__ void run_chain_batch(Ctx& c, int rowmask, int inner) 
     TRC(c, 37, regrun ? 1 : 0); TRC(c, 38, D_in); TRC(c, 39, pr0); TRC(c, 40, pr1);
     // keyed passes (see reg_chain_loop): every point of every row has the same finite prior value and a finite fixed part
 #ifdef VLR_DBG_NO_KEYED  // diagnosis builds: every pass takes the logarithm itself
-    const bool keyed = false && c.nlfc == 0 &&
+    const bool keyed = false && nlfc_of(c) == 0 &&
 #else
-    const bool keyed = regrun && c.nlfc == 0 && !(ones_any(c) && ones_risk(c, inner)) &&
+    const bool keyed = regrun && nlfc_of(c) == 0 && !(ones_any(c) && ones_risk(c, inner)) &&
 #endif  // (the exponent of a direct all-ones product is not bounded by the key's 16 bits)
                        __ballot(rowon && !(cls_fast && (pr0 == pr1 || lo != 0.0) && fabs(pr1) < __builtin_huge_val() && fabs(fixed) < __builtin_huge_val())) == 0ull;
     TRC(c, 41, keyed ? 1 : 0); TRC(c, 42, cls_fast ? 1 : 0);
@@ -2689,7 +2709,7 @@ __device__ __forceinline__ void run_chain_batch(Ctx& c, int rowmask, int inner) 
         PROF_ADD(c, 13);  // round: reduction
         const double lik = fixed + (log(Psel) + (double)Esel * kLn2);
         double joint;
-        if (c.nlfc > 0 && !lfcs_ok(c, inner, x)) joint = VLR_NEG_INF;
+        if (nlfc_of(c) > 0 && !lfcs_ok(c, inner, x)) joint = VLR_NEG_INF;
         else {
             int cls = cls_fast ? (x == 0.0 ? 0 : 1) : prior_class(p, inner, x);
             double pv = cls == 0 ? pr0 : cls == 1 ? pr1 : cls == 2 ? pr2 : ptab[pidx + cls * istride];
@@ -2815,7 +2835,7 @@ __device__ __forceinline__ void run_chain_batch(Ctx& c, int rowmask, int inner) 
             }
         }
         // who reads the joint values of this batch's entries (wave-uniform)
-        const bool need_vals = !keyed || log_on(c) || c.replay != 0 || __ballot(rowon && (T.alive != 0 || contained == 0 || anyout)) != 0ull;
+        const bool need_vals = !keyed || log_on(c) || (kHasReplay && c.replay != 0) || __ballot(rowon && (T.alive != 0 || contained == 0 || anyout)) != 0ull;
         if (keyed && need_vals) {
 #pragma unroll
             for (int t = 0; t < 4; ++t)
@@ -3051,7 +3071,7 @@ __device__ inline void scan_chain_candidates(Ctx& c, const double* rx, const dou
 __device__ inline bool ops_lfc_bounds(const Ctx& c, int sample, RangeV& out) {
     bool have = false;
     RangeV acc = range_empty();
-    for (int i = 0; i < c.nlfc; ++i) {
+    for (int i = 0; i < nlfc_of(c); ++i) {
         int sa = c.w->lfc_a[i], sb = c.w->lfc_b[i];
         int cmp = c.w->lfc_cmp[i];
         double val = c.w->lfc_val[i];
@@ -3230,7 +3250,7 @@ __device__ __forceinline__ bool bo_deliver(Ctx& c, const Frame& f, RangeSt& r, d
         VLR_SYNC();
         if (__builtin_expect(dead, 0)) continue;
         const int hb = VLR_RDLANE(hbl, i), n_i = VLR_RDLANE(nl, i);
-        if (__builtin_expect(c.replay != 0, 0)) {
+        if (kHasReplay && __builtin_expect(c.replay != 0, 0)) {
             if (UNI(f.sv_mute) || table_has(txo, tn0 + c0 + i, x, lane)) continue;  // repeated outer VAF: same map keys
             afd_emit_row(c, i, s_in, n_i);
             continue;
@@ -3281,13 +3301,13 @@ __device__ __forceinline__ void flush_deliver(Ctx& c, int rowmask, double* evM, 
         VLR_SYNC();
         if (c.lane < c.S) { w->ops_vaf[c.lane] = c.tvaf[i * c.S + c.lane]; w->curMapVaf[c.lane] = c.mapVaf[u * c.S + c.lane]; }
         VLR_SYNC();
-        c.group = UNI(T.group); c.disc = UNI(T.disc); c.contained = UNI(T.contained); c.alive = UNI_A(T.alive); c.nlfc = 0;
+        c.group = UNI(T.group); c.disc = UNI(T.disc); c.contained = UNI(T.contained); c.alive = UNI_A(T.alive); if (kHasLfc) c.nlfc = 0;
         c.curJ = uni_d(c.mapJ[u]); c.curHyp = UNI(c.mapHyp[u]);
         const double dens = uni_d(T.result);
         TRC(c, 100, dens); TRC(c, 101, u); TRC(c, 102, i);
         if (dens != dens) c.status |= VLR_LOCUS_NAN;
         const int nq = UNI(T.n);
-        if (__builtin_expect(c.replay != 0, 0)) afd_emit_row(c, i, s_in, nq);
+        if (kHasReplay && __builtin_expect(c.replay != 0, 0)) afd_emit_row(c, i, s_in, nq);
         else {
             if (UNI(T.haveBest) & 1) map_consider(c, uni_d(T.bestJ), s_in, uni_d(T.bestX));
             if (__builtin_expect(c.alive != 0 || !c.contained || (UNI(T.haveBest) & 2), 0)) {
@@ -3393,26 +3413,26 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
         sp = UNI(k.sp); node = UNI(k.node); nrange = UNI(k.nrange); skip_record = UNI(k.skip_record) != 0; rv = uni_d(k.rv);
         pc = PC_BO_POST;
     } else {
-        c.present = 0; c.disc = 0; c.nlfc = 0; c.contained = 1; c.afd_mute = 0;
+        c.present = 0; c.disc = 0; if (kHasLfc) c.nlfc = 0; c.contained = 1; c.afd_mute = 0;
         c.alive = ALIVE_FULL(p.n_named + 1) & ~ALIVE_BIT(c.group);  // n_named <= 30 (wide build: 62): no shift reaches the sign bit
     }
     for (;;) {
         if (pc == PC_DESCEND) {
             const DevNode nd = ld_node(p.nodes + node);
-            if (nd.kind == VLR_NODE_LFC) {  // 233-244
-                if (c.nlfc < kMaxLfc) {
+            if (kHasLfc && nd.kind == VLR_NODE_LFC) {  // 233-244
+                if (nlfc_of(c) < kMaxLfc) {
                     VLR_SYNC();
                     if (c.lane == 0) {
-                        w->lfc_a[c.nlfc] = nd.sample; w->lfc_b[c.nlfc] = nd.sample_b;
-                        w->lfc_cmp[c.nlfc] = nd.cmp; w->lfc_val[c.nlfc] = nd.lfc_value;
+                        w->lfc_a[nlfc_of(c)] = nd.sample; w->lfc_b[nlfc_of(c)] = nd.sample_b;
+                        w->lfc_cmp[nlfc_of(c)] = nd.cmp; w->lfc_val[nlfc_of(c)] = nd.lfc_value;
                     }
                     VLR_SYNC();
                     c.nlfc++;
                 }
                 pc = PC_SUB;
-            } else if (nd.kind == VLR_NODE_FALSE) { rv = VLR_NEG_INF; pc = PC_RETURN; }
-            else if (nd.kind == VLR_NODE_TRUE) { rv = 0.0; pc = PC_RETURN; }
-            else if (nd.kind == VLR_NODE_VARIANT) {  // 398-420
+            } else if (kHasGeneralWalk && nd.kind == VLR_NODE_FALSE) { rv = VLR_NEG_INF; pc = PC_RETURN; }
+            else if (kHasGeneralWalk && nd.kind == VLR_NODE_TRUE) { rv = 0.0; pc = PC_RETURN; }
+            else if (kHasGeneralWalk && nd.kind == VLR_NODE_VARIANT) {  // 398-420
                 bool go;
                 if (c.has_snv) {
                     bool contains = iupac_contains(nd.refbase, c.refbase) && iupac_contains(nd.altbase, c.altbase);
@@ -3425,7 +3445,7 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
                 bool have_bounds = ops_lfc_bounds(c, s, bounds);
                 int n_obs = w->nkeep[s];
                 bool clear_ref = n_obs > 10 && w->all_posref[s];  // 270-291
-                bool is_set = nd.vafs.kind == 0;
+                bool is_set = kHasGeneralWalk && nd.vafs.kind == 0;
                 RangeV vr{nd.vafs.start, nd.vafs.end, nd.vafs.lex, nd.vafs.rex};
                 bool dead = have_bounds && range_is_empty(bounds);  // 262-268
                 int ncand = 0;
@@ -3452,7 +3472,7 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
                         if (have_bounds) vr = range_intersect(vr, bounds);
                         if (range_is_empty(vr)) dead = true;
                         else if (clear_ref && vr.start > 0.0) dead = true;
-                        else if (range_is_singleton(vr)) {
+                        else if (kHasGeneralWalk && range_is_singleton(vr)) {
                             VLR_SYNC();
                             if (c.lane == 0) c.setv[s * p.max_set] = vr.start;
                             VLR_SYNC();
@@ -3469,12 +3489,12 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
                     Frame& f = c.frames[sp];
                     if (c.lane == 0) {
                         f.node = node; f.iter = 0; f.accM = VLR_NEG_INF; f.accS = 0.0;
-                        f.sv_present = c.present; f.sv_disc = c.disc; f.sv_nlfc = c.nlfc; f.sv_contained = c.contained;
+                        f.sv_present = c.present; f.sv_disc = c.disc; f.sv_nlfc = nlfc_of(c); f.sv_contained = c.contained;
                         // every operand set below this frame takes sample s from this node: groups whose spectra for s miss the
                         // node's spectrum altogether (static, DevNode::alive_mask) cannot contain any of them
                         f.sv_alive = c.alive & NODE_ALIVE(nd); f.sv_mute = c.afd_mute;
                     }
-                    if (c.defer_ok && (as_set ? (ncand > 1) : (nd.n_children != 0))) {
+                    if (kHasGeneralWalk && c.defer_ok && (as_set ? (ncand > 1) : (nd.n_children != 0))) {
                         c.deferred = 2;  // probe pass: not a single-chain root, evaluate in the second pass
                         return 0.0;
                     }
@@ -3523,7 +3543,7 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
                     }
                 }
             }
-        } else if (pc == PC_SUB) {  // subdensity (199-230)
+        } else if (kHasGeneralWalk && pc == PC_SUB) {  // subdensity (199-230)
             const DevNode nd = ld_node(p.nodes + node);
             if (nd.n_children == 0) { rv = leaf_joint(c); pc = PC_RETURN; }
             else if (nd.n_children == 1) { node = ldc(p.child_index + nd.child_off); pc = PC_DESCEND; }
@@ -3534,7 +3554,7 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
                 Frame& f = c.frames[sp];
                 if (c.lane == 0) {
                     f.kind = FK_BRANCH; f.node = node; f.iter = 0; f.n = nd.n_children; f.accM = VLR_NEG_INF; f.accS = 0.0;
-                    f.sv_present = c.present; f.sv_disc = c.disc; f.sv_nlfc = c.nlfc; f.sv_contained = c.contained;
+                    f.sv_present = c.present; f.sv_disc = c.disc; f.sv_nlfc = nlfc_of(c); f.sv_contained = c.contained;
                     f.sv_alive = c.alive; f.sv_mute = c.afd_mute;
                 }
                 VLR_SYNC();
@@ -3547,19 +3567,21 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
             const int fslot = UNI(f.slot), fnode = UNI(f.node);
             RangeSt& r = c.rs[fslot];
             double* tx = c.tabX + fslot * c.cap;
-            if (UNI(r.tn) + (UNI(r.npend) - UNI(f.iter)) > c.cap) {  // room for the points of this round still to be recorded
+            // (lean build: a frame the host's proof excludes — a leaf Range, or no leaf Range child — ends the locus with a status bit
+            //  instead of taking the batched path it is not made for)
+            if (UNI(r.tn) + (UNI(r.npend) - UNI(f.iter)) > c.cap || (!kHasGeneralWalk && (UNI(r.leaf) || UNI(f.n) < 0))) {  // room for the points of this round still to be recorded
                 c.status |= VLR_LOCUS_TABLE_FULL;
                 rv = __builtin_nan("");
-                c.present = UNI(f.sv_present); c.disc = UNI(f.sv_disc); c.nlfc = UNI(f.sv_nlfc); c.contained = UNI(f.sv_contained); c.alive = UNI_A(f.sv_alive); c.afd_mute = UNI(f.sv_mute);
+                c.present = UNI(f.sv_present); c.disc = UNI(f.sv_disc); if (kHasLfc) c.nlfc = UNI(f.sv_nlfc); c.contained = UNI(f.sv_contained); c.alive = UNI_A(f.sv_alive); c.afd_mute = UNI(f.sv_mute);
                 sp--; nrange--;
                 pc = PC_RETURN;
-            } else if (UNI(r.leaf)) {
+            } else if (kHasGeneralWalk && UNI(r.leaf)) {
                 // innermost chain: evaluate all pending points at once, loop the state machine here
                 c.present = UNI(f.sv_present) | (1 << UNI(r.sample));
-                c.nlfc = UNI(f.sv_nlfc);
+                if (kHasLfc) c.nlfc = UNI(f.sv_nlfc);
                 c.contained = UNI(f.sv_contained);
                 c.alive = UNI_A(f.sv_alive);
-                if (c.defer_ok && (c.cap > 64 || c.nlfc != 0 || (c.ndef > 0 && UNI(w->task[0].inner) != UNI(r.sample)))) {
+                if (c.defer_ok && (c.cap > 64 || nlfc_of(c) != 0 || (c.ndef > 0 && UNI(w->task[0].inner) != UNI(r.sample)))) {
                     c.deferred = 2;
                     return 0.0;
                 }
@@ -3590,14 +3612,14 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
                     return 0.0;
                 }
                 rv = run_leaf_chain(c, r, c.rowX, c.rowV);
-                c.present = UNI(f.sv_present); c.disc = UNI(f.sv_disc); c.nlfc = UNI(f.sv_nlfc); c.contained = UNI(f.sv_contained); c.alive = UNI_A(f.sv_alive); c.afd_mute = UNI(f.sv_mute);
+                c.present = UNI(f.sv_present); c.disc = UNI(f.sv_disc); if (kHasLfc) c.nlfc = UNI(f.sv_nlfc); c.contained = UNI(f.sv_contained); c.alive = UNI_A(f.sv_alive); c.afd_mute = UNI(f.sv_mute);
                 sp--; nrange--;
                 pc = PC_RETURN;
-            } else if (c.cap <= 64 && UNI(f.iter) == 0 && UNI(f.sv_nlfc) == 0 && UNI(f.n) >= 0) {
+            } else if (!kHasGeneralWalk || (c.cap <= 64 && UNI(f.iter) == 0 && (!kHasLfc || UNI(f.sv_nlfc) == 0) && UNI(f.n) >= 0)) {
                 // outer chain over a leaf Range child: all pending points at once, kRows inner chains per pass
                 c.present = UNI(f.sv_present) | (1 << UNI(r.sample));
                 c.disc = UNI(f.sv_disc) & ~(1 << UNI(r.sample));
-                c.nlfc = UNI(f.sv_nlfc);
+                if (kHasLfc) c.nlfc = UNI(f.sv_nlfc);
                 // the frame's constants (inner range, fixed likelihoods, ...) are set up in its first round only; later rounds
                 // just rewind the point counters (no other outer frame can run between the rounds of this one: its children
                 // are leaf chains)
@@ -3615,11 +3637,11 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
                 double x = uni_d(r.pend[it]);
                 c.present = UNI(f.sv_present) | (1 << UNI(r.sample));
                 c.disc = UNI(f.sv_disc) & ~(1 << UNI(r.sample));
-                c.nlfc = UNI(f.sv_nlfc);
+                if (kHasLfc) c.nlfc = UNI(f.sv_nlfc);
                 RangeV orig{r.ostart, r.oend, r.olex, r.orex};
                 c.contained = UNI(f.sv_contained) && range_contains(orig, x);
                 c.alive = alive_update(c, UNI_A(f.sv_alive), UNI(r.sample), x);
-                if (c.replay) c.afd_mute = UNI(f.sv_mute) || table_has(tx, UNI(r.tn), x, c.lane);
+                if (kHasReplay && c.replay) c.afd_mute = UNI(f.sv_mute) || table_has(tx, UNI(r.tn), x, c.lane);
                 VLR_SYNC();
                 if (c.lane == 0) w->ops_vaf[UNI(r.sample)] = x;
                 VLR_SYNC();
@@ -3654,14 +3676,14 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
                 else {
                     rv = range_finish(c, r, tx, tv);
                     PROF_ADD(c, 28);  // outer: range_finish
-                    c.present = UNI(f.sv_present); c.disc = UNI(f.sv_disc); c.nlfc = UNI(f.sv_nlfc); c.contained = UNI(f.sv_contained); c.alive = UNI_A(f.sv_alive); c.afd_mute = UNI(f.sv_mute);
+                    c.present = UNI(f.sv_present); c.disc = UNI(f.sv_disc); if (kHasLfc) c.nlfc = UNI(f.sv_nlfc); c.contained = UNI(f.sv_contained); c.alive = UNI_A(f.sv_alive); c.afd_mute = UNI(f.sv_mute);
                     sp--; nrange--;
                     pc = PC_RETURN;
                 }
             }
         } else {  // PC_RETURN: hand rv to the enclosing frame
             rv = uni_d(rv);
-            if (sp == 0) return rv;
+            if (!kHasGeneralWalk || sp == 0) return rv;
             Frame& f = c.frames[sp - 1];
             if (UNI(f.kind) == FK_RANGE) {
                 const int fslot = UNI(f.slot);
@@ -3681,7 +3703,7 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
                     if (!done) { pc = PC_RANGE_ISSUE; }
                     else {
                         rv = range_finish(c, r, tx, tv);
-                        c.present = UNI(f.sv_present); c.disc = UNI(f.sv_disc); c.nlfc = UNI(f.sv_nlfc); c.contained = UNI(f.sv_contained); c.alive = UNI_A(f.sv_alive); c.afd_mute = UNI(f.sv_mute);
+                        c.present = UNI(f.sv_present); c.disc = UNI(f.sv_disc); if (kHasLfc) c.nlfc = UNI(f.sv_nlfc); c.contained = UNI(f.sv_contained); c.alive = UNI_A(f.sv_alive); c.afd_mute = UNI(f.sv_mute);
                         sp--; nrange--;
                         pc = PC_RETURN;
                     }
@@ -3693,7 +3715,7 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
                 VLR_SYNC();
                 if (c.lane == 0) { f.accM = M; f.accS = S; f.iter = it; }
                 VLR_SYNC();
-                c.present = UNI(f.sv_present); c.disc = UNI(f.sv_disc); c.nlfc = UNI(f.sv_nlfc); c.contained = UNI(f.sv_contained); c.alive = UNI_A(f.sv_alive); c.afd_mute = UNI(f.sv_mute);
+                c.present = UNI(f.sv_present); c.disc = UNI(f.sv_disc); if (kHasLfc) c.nlfc = UNI(f.sv_nlfc); c.contained = UNI(f.sv_contained); c.alive = UNI_A(f.sv_alive); c.afd_mute = UNI(f.sv_mute);
                 if (it < UNI(f.n)) {
                     const int fnode = UNI(f.node);
                     const DevNode nd = ld_node(p.nodes + fnode);
@@ -3733,6 +3755,7 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
 //      record, then its whole table goes to the list of its sample with coalesced stores; the entry at the MAP VAF itself and
 //      the matching entries of the records that differ in exactly one sample take the scalar afd_consider path;
 //   3. discrete leaves: classified one per lane, matches through afd_consider.
+#if !VLR_LEAN   // (the lean unit is only launched without AFD lists: no log filter, no self-test kernels in its code object)
 __global__ void __launch_bounds__(64) vlr_afd_kernel(const DevPlan plan_arg, DevBatch batch, DevResults out) {
     __shared__ WaveSt wst;
     extern __shared__ double sh_seen[];  // [S][seen_cap] (VAF, l2fc key) pairs (dynamic: the plan's largest Set spectrum sets the size)
@@ -3846,7 +3869,7 @@ __global__ void __launch_bounds__(64) vlr_afd_kernel(const DevPlan plan_arg, Dev
         const int at_r = VLR_RDLANE(at, r), n_r = VLR_RDLANE(n, r), sin_r = VLR_RDLANE(s_in, r);
         const int nl_r = VLR_RDLANE(nl, r);
         c.group = VLR_RDLANE(grp, r);
-        c.disc = VLR_RDLANE(disc, r); c.nlfc = nl_r;
+        c.disc = VLR_RDLANE(disc, r); if (kHasLfc) c.nlfc = nl_r;
         const int pay = at_r + 1 + S + 2 * nl_r;
         {
             const int hq = VLR_RDLANE(hitq, r);
@@ -3934,6 +3957,7 @@ __global__ void __launch_bounds__(64) vlr_afd_kernel(const DevPlan plan_arg, Dev
     }
     afd_finish(c);
 }
+#endif  // !VLR_LEAN
 
 // ------------------------------------------------------------------------------------------------
 // Two builds of the same kernel: WPE = 2 waves per SIMD (no spills) for workgroups whose LDS footprint allows only 8 of
@@ -3963,7 +3987,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
 #ifdef VLR_NO_XCD_MAP
     const int64_t locus = blockIdx.x;
 #else
-    const int64_t locus = plan_arg.S <= kXcdMapMaxSamples
+    const int64_t locus = (!kHasManySamples || plan_arg.S <= kXcdMapMaxSamples)
                               ? (int64_t)(blockIdx.x % kXcds) * ((batch.n_loci + kXcds - 1) / kXcds) + (int64_t)(blockIdx.x / kXcds)
                               : (int64_t)blockIdx.x;
 #endif
@@ -3973,7 +3997,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
     // and need the same room again, so together they fit the pool whatever the order of their allocations.
     if (VLR_DEEP && out.replay && !(out.status[locus] & kDeepEvaluated)) return;
     // replay launch next to an AFD log: only the loci whose log region overflowed are re-evaluated
-    if (!VLR_DEEP && out.replay && out.afd_log && __double_as_longlong(out.afd_log[(size_t)locus * (size_t)out.afd_log_stride]) >= 0) return;
+    if (kHasReplay && !VLR_DEEP && out.replay && out.afd_log && __double_as_longlong(out.afd_log[(size_t)locus * (size_t)out.afd_log_stride]) >= 0) return;
     const int S = p.S;
     WaveSt* w = &wst;
 
@@ -4003,7 +4027,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
     c.cacheV = c.cacheB + S * kCacheWays;
     c.afd_seen = c.cacheV + S * kCacheWays;  // [S][seen_cap] x (VAF, l2fc key)
     c.seen_cap = p.max_set > 16 ? p.max_set : 16;
-    const int n_seen = out.replay ? 2 * S * c.seen_cap + 2 * S : 0;  // only the AFD replay pass records discrete VAFs
+    const int n_seen = (kHasReplay && out.replay) ? 2 * S * c.seen_cap + 2 * S : 0;  // only the AFD replay pass records discrete VAFs
     c.mapv = c.afd_seen + 2 * S * c.seen_cap;
     c.afd_nseen = (int*)(c.mapv + S);
     int* mapHyp = (int*)(c.afd_seen + n_seen);  // [n_slots]
@@ -4015,8 +4039,8 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
     c.status = 0;
     if (lane == 0) { w->work[0] = 0; w->work[1] = 0; }
     c.need_batch = 0; c.bt_nt = 0; c.bt_inner = 0;
-    c.replay = out.replay; c.locus = locus; c.outp = &out; c.mapGroup = 0; c.mapDisc = 0; c.marginal = 0.0; c.afd_cnt = nullptr;
-    c.lg = (out.afd_log && !out.replay && !VLR_DEEP) ? out.afd_log + (size_t)locus * (size_t)out.afd_log_stride : nullptr;
+    c.replay = kHasReplay ? out.replay : 0; c.locus = locus; c.outp = &out; c.mapGroup = 0; c.mapDisc = 0; c.marginal = 0.0; c.afd_cnt = nullptr;
+    c.lg = (kHasAfd && out.afd_log && !out.replay && !VLR_DEEP) ? out.afd_log + (size_t)locus * (size_t)out.afd_log_stride : nullptr;
     c.lg_pos = kLogFirst; c.lg_cap = (int)out.afd_log_stride; c.lg_nrec = 0; c.hyp = 0;
 #ifdef VLR_PROFILE
     for (int i = 0; i < 40; ++i) c.prof[i] = 0;
@@ -4295,7 +4319,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
 
     if (too_deep) c.status |= VLR_LOCUS_TOO_DEEP;
     unsigned hyps = too_deep ? 0u : (1u | surviving);
-    if (c.replay) {
+    if (kHasReplay && c.replay) {
         // AFD only exists for a non-artifact MAP (calling.rs:889): MAP operands, best event group and marginal come
         // from the first pass; only the clean events are re-evaluated
         bool have = true;
@@ -4513,7 +4537,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
         if (lane < S) w->cacheN[lane] = 0;
         VLR_SYNC();  // also orders the e coefficients (HBM scratch row, written by other lanes than the ones that read them)
         if (__ballot((c.status & VLR_LOCUS_UNDERFLOW) != 0)) c.status |= VLR_LOCUS_UNDERFLOW;
-        if (p.n_dkey > 0 && !c.replay) {  // pileup likelihoods of the flattened discrete roots under this hypothesis
+        if (p.n_dkey > 0 && !(kHasReplay && c.replay)) {  // pileup likelihoods of the flattened discrete roots under this hypothesis
             for (int k = 0; k < p.n_dkey; ++k) {
                 const double r = sample_lik_point(c, ldc(&p.dkey[k].sample), ldc(&p.dkey[k].a), ldc(&p.dkey[k].b));
                 if (lane == 0) c.dkeyV[k] = r;
@@ -4573,7 +4597,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
                             r1 = (e < 0) ? 1 : ldc(p.root_off + e + 1);
                             // (a FULL set of four cannot be held — two rows and the stash take three —: it runs as a batch of its own here,
                             //  as it would have if a fifth deferrable root had followed)
-                            if (c.ndef > 0 && (c.replay || todo == 0ull || c.ndef == kRows)) {  // nothing left that could give them a ride
+                            if (c.ndef > 0 && ((kHasReplay && c.replay) || todo == 0ull || c.ndef == kRows)) {  // nothing left that could give them a ride
                                 run_kind = 3; run_mask = (1 << c.ndef) - 1; run_inner = UNI(w->task[0].inner); c.ndef = 0;
                             } else if (c.ndef > 0) {
                                 // Held chains: instead of a batch of their own (three of four rows busy in the tumor-normal
@@ -4603,7 +4627,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
                     c.defer_ok = (1 - pass) & (int)((unsigned)(rc_ - 64) >> 31);  // pass == 0 && rc_ < 64, as integer arithmetic (stays a scalar)
                     c.defer_slot = u;
                     const DevFastRoot* fr = p.froot + ((e < 0) ? 0 : 1 + ri);
-                    const bool is_droot = !(c.replay || p.n_dkey == 0) && ldc(p.droot + 2 * ((e < 0) ? 0 : 1 + ri)) >= 0;  // all-discrete roots: below
+                    const bool is_droot = !((kHasReplay && c.replay) || p.n_dkey == 0) && ldc(p.droot + 2 * ((e < 0) ? 0 : 1 + ri)) >= 0;  // all-discrete roots: below
 #ifdef VLR_NO_FAST_CODE
                     const int fkind = 0;
 #else
@@ -4623,7 +4647,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
                     VLR_SYNC();
                     root = (e < 0) ? p.absent_root : ldc(p.roots + ri);
                     const int di = (e < 0) ? 0 : 1 + ri;
-                    const int dl0 = (c.replay || p.n_dkey == 0) ? -1 : ldc(p.droot + 2 * di);
+                    const int dl0 = ((kHasReplay && c.replay) || p.n_dkey == 0) ? -1 : ldc(p.droot + 2 * di);
                     if (dl0 >= 0) {  // all-discrete root: its leaves side by side on the lanes
                         const double dens = eval_discrete_root(c, dl0, ldc(p.droot + 2 * di + 1));
                         PROF_ADD(c, 23);
@@ -4667,7 +4691,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
                 PROF_ADD(c, 22);  // root exit (event accumulators, slot state)
                 if (run_kind) {
                     PROF_ADD(c, 31);  // event loop: between the walk's return and the batch
-                    if (run_kind != 1) c.nlfc = 0;  // deferred chains carry no l2fc terms; a later probe walk may have left some in the context
+                    if (run_kind != 1) if (kHasLfc) c.nlfc = 0;  // deferred chains carry no l2fc terms; a later probe walk may have left some in the context
                     TRC(c, 20, run_mask); TRC(c, 21, run_inner); TRC(c, 22, run_kind); TRC(c, 23, piggy);
                     run_chain_batch(c, run_mask, run_inner);
                     VLR_SYNC();
@@ -4675,7 +4699,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
                         if (piggy) {
                             // the walk is suspended with the MAP candidate of ITS slot and its operands in the context: park them
                             // in the slot arrays, hand the held chains to their events, and take the context back
-                            const int sg = c.group, sd = c.disc, sc = c.contained, sn = c.nlfc;
+                            const int sg = c.group, sd = c.disc, sc = c.contained, sn = nlfc_of(c);
                             const alive_t sa = c.alive;
                             const double so = w->ops_vaf[lane < S ? lane : 0];
                             VLR_SYNC();
@@ -4686,7 +4710,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
                             c.curJ = uni_d(mapJ[u]); c.curHyp = UNI(mapHyp[u]);
                             if (lane < S) { w->curMapVaf[lane] = mapVaf[u * S + lane]; w->ops_vaf[lane] = so; }
                             VLR_SYNC();
-                            c.group = sg; c.disc = sd; c.contained = sc; c.alive = sa; c.nlfc = sn;
+                            c.group = sg; c.disc = sd; c.contained = sc; c.alive = sa; if (kHasLfc) c.nlfc = sn;
                             c.nhold = 0;
                         }
                         resume = 1; st = IT_WALK;
@@ -4701,7 +4725,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
         PROF_ADD(c, 3);
     }
     PROF_ADD(c, 3);  // walk remainder (everything in the event loop not attributed below)
-    if (c.replay) {
+    if (kHasReplay && c.replay) {
         afd_finish(c);
         if (VLR_DEEP && lane == 0) out.status[locus] &= ~(VLR_LOCUS_TOO_DEEP | kDeepEvaluated);  // evaluated by the deep call launch, lists done
         return;
@@ -4797,7 +4821,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
             uint8_t* mb = out.map_bias + locus * VLR_N_BIAS;
             for (int i = 0; i < VLR_N_BIAS; ++i) mb[i] = 0;
             int hh = pick >= 0 ? (mapHyp[pick] & 15) : 0;
-            if (out.map_disc) out.map_disc[locus] = (uint16_t)(pick >= 0 ? (mapHyp[pick] >> 4) : 0);
+            if (kHasAfd && out.map_disc) out.map_disc[locus] = (uint16_t)(pick >= 0 ? (mapHyp[pick] >> 4) : 0);
             switch (hh) {
                 case H_SBF: mb[0] = 1; break;
                 case H_SBR: mb[0] = 2; break;
@@ -4811,7 +4835,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
             }
         }
     }
-    if (c.lg && lane == 0) {  // words used (-1: overflow, the replay launch takes over) and the record count
+    if (kHasAfd && c.lg && lane == 0) {  // words used (-1: overflow, the replay launch takes over) and the record count
         c.lg[0] = __longlong_as_double((long long)c.lg_pos);
         c.lg[1] = __longlong_as_double((long long)c.lg_nrec);
     }
@@ -4833,6 +4857,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
 }  // namespace vlr
 
 // ---- diagnostics: the device build of the decision arithmetic (include/vlr_detmath.h) and of ln_mantissa, element-wise
+#if !VLR_LEAN
 namespace vlr {
 __global__ void vlr_selftest_math_kernel(int which, const double* a, const double* b, double* out, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -4870,13 +4895,20 @@ __global__ void __launch_bounds__(64) vlr_selftest_stream_kernel(const float* in
     }
 }
 }  // namespace vlr
+#endif  // !VLR_LEAN
+// Lean build (vlr_kernels_lean.hip): exports vlr_launch_call_kernel_lean and vlr_launch_call_lds_bytes_lean.
 // Wide build (vlr_kernels_wide.hip: VLR_WIDE_BUILD, VLR_LDS_SAMPLES 16, namespace renamed): the same kernels with per-sample LDS
 // arrays for sixteen samples; exports vlr_launch_call_kernel_wide and vlr_launch_afd_kernel_wide and nothing else.
 #ifdef VLR_WIDE_BUILD
 #define VLR_FN_CALL vlr_launch_call_kernel_wide
 #define VLR_FN_AFD vlr_launch_afd_kernel_wide
 #define VLR_FN_LDS vlr_plan_lds_floor_wide
+#elif VLR_LEAN
+#define VLR_FN_CALL vlr_launch_call_kernel_lean
+#define VLR_FN_LDSB vlr_launch_call_lds_bytes_lean
 #else
+#define VLR_FN_LDSB vlr_launch_call_lds_bytes
+
 #define VLR_FN_CALL vlr_launch_call_kernel
 #define VLR_FN_AFD vlr_launch_afd_kernel
 #define VLR_FN_LDS vlr_plan_lds_floor
@@ -4918,7 +4950,7 @@ extern "C" long long vlr_debug_trace_read(unsigned long long* hdr, double* val, 
 }
 #endif
 #endif
-#if !VLR_DEEP && !defined(VLR_WIDE_BUILD)
+#if !VLR_DEEP && !defined(VLR_WIDE_BUILD) && !VLR_LEAN
 extern "C" int vlr_launch_selftest_stream(const float* in, double* out, long long n, int mode, void* stream) {
     if (n <= 0) return 0;
     const long long per_wg = 64 * 256;
@@ -4960,6 +4992,7 @@ extern "C" int VLR_FN_DEEP(const vlr::DevPlan* plan_host, const vlr::DevBatch* b
     return (int)hipGetLastError();
 }
 #else
+#if !VLR_LEAN
 extern "C" int VLR_FN_AFD(const vlr::DevPlan* plan_host, const vlr::DevBatch* batch, const vlr::DevResults* out, void* stream) {
     if (batch->n_loci <= 0) return 0;
     const size_t seen_bytes = (size_t)2 * plan_host->S * (plan_host->max_set > 16 ? plan_host->max_set : 16) * sizeof(double);
@@ -4970,6 +5003,7 @@ extern "C" int VLR_FN_AFD(const vlr::DevPlan* plan_host, const vlr::DevBatch* ba
     hipLaunchKernelGGL(vlr::vlr_afd_kernel, dim3((unsigned)batch->n_loci), dim3(64), seen_bytes, (hipStream_t)stream, *plan_host, *batch, *out);
     return (int)hipGetLastError();
 }
+#endif  // !VLR_LEAN
 
 // dynamic LDS of one workgroup of the call kernel (the layout at the top of vlr_call_kernel)
 static size_t call_kernel_dyn_lds(const vlr::DevPlan* plan_host, int n_univ, int n_samples, int max_obs, int range_depth, bool replay) {
@@ -4986,26 +5020,28 @@ static size_t call_kernel_dyn_lds(const vlr::DevPlan* plan_host, int n_univ, int
 // Worst-case LDS of a plan's launches without any coefficient area (max_obs = 0): call pass, AFD replay and the AFD log filter.  A plan
 // whose tables alone do not fit the 160 KiB of a CU (Set spectra of hundreds of members in many samples) is refused by vlr_plan_create
 // with this number instead of failing at its first batch with a launch error.
+#if !VLR_LEAN
 extern "C" long long VLR_FN_LDS(const vlr::DevPlan* plan_host, int n_univ, int n_samples, int range_depth) {
     if (range_depth < 1) range_depth = 1;
     const size_t call = call_kernel_dyn_lds(plan_host, n_univ, n_samples, 0, range_depth, true) + 4096;   // + the static part (WaveSt, < 4 KiB in every build)
     const size_t afd = (size_t)2 * plan_host->S * (plan_host->max_set > 16 ? plan_host->max_set : 16) * sizeof(double) + 16384;  // + static part of vlr_afd_kernel
     return (long long)(call > afd ? call : afd);
 }
+#endif  // !VLR_LEAN
 
 // LDS bytes of one workgroup of the call kernel (static + dynamic) at a pileup budget of max_obs: what the launcher's rule below sees
 // (vlr_plan_fit_max_obs in vlr_host.cpp sizes the budget of shallow batches with it)
 #ifndef VLR_WIDE_BUILD
-extern "C" long long vlr_launch_call_lds_bytes(const vlr::DevPlan* plan_host, int n_univ, int n_samples, int max_obs, int range_depth) {
+extern "C" long long VLR_FN_LDSB(const vlr::DevPlan* plan_host, int n_univ, int n_samples, int max_obs, int range_depth) {
     hipFuncAttributes fa{};
     if (hipFuncGetAttributes(&fa, (const void*)vlr::vlr_call_kernel<2>) != hipSuccess) return -1;
     if (range_depth < 1) range_depth = 1;
     return (long long)(fa.sharedSizeBytes + call_kernel_dyn_lds(plan_host, n_univ, n_samples, max_obs, range_depth, false));
 }
 #endif
-// host-callable launcher (used by vlr_host.cpp)
+// host-callable launcher (used by vlr_host.cpp); *waves_out (optional): waves per SIMD of the instance launched (vlr_plan_last_instance)
 extern "C" int VLR_FN_CALL(const vlr::DevPlan* plan_host, const vlr::DevBatch* batch, const vlr::DevResults* out,
-                                      int n_univ, int n_samples, int max_obs, int range_depth, void* stream) {
+                                      int n_univ, int n_samples, int max_obs, int range_depth, void* stream, int* waves_out) {
     using namespace vlr;
     if (batch->n_loci <= 0) return 0;
     if (n_samples > kLdsSamples) return (int)hipErrorInvalidValue;  // (the per-sample LDS arrays of this build; the host picks the wide build)
@@ -5038,6 +5074,7 @@ extern "C" int VLR_FN_CALL(const vlr::DevPlan* plan_host, const vlr::DevBatch* b
     case W: {                                                                                                                \
         hipError_t e = hipFuncSetAttribute((const void*)vlr_call_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); \
         if (e != hipSuccess) return (int)e;                                                                                  \
+        if (waves_out) *waves_out = W;                                                                                       \
         hipLaunchKernelGGL(vlr_call_kernel<W>, grid, block, bytes, (hipStream_t)stream, *plan_host, *batch, *out, max_obs, range_depth); \
         break;                                                                                                               \
     }

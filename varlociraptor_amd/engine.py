@@ -24,7 +24,7 @@ _LIB = None
 EXPORTS = [
     "vlr_abi_version", "vlr_build_id", "vlr_last_error", "vlr_plan_create", "vlr_plan_destroy", "vlr_plan_n_out",
     "vlr_plan_n_samples", "vlr_plan_set_max_depth", "vlr_plan_set_max_obs", "vlr_plan_fit_max_obs", "vlr_plan_reserve", "vlr_batch_run", "vlr_batch_run_host", "vlr_batch_run_device_in",
-    "vlr_plan_last_kernel_ms", "vlr_plan_work_counters", "vlr_host_alloc", "vlr_host_free",
+    "vlr_plan_last_kernel_ms", "vlr_plan_last_instance", "vlr_plan_work_counters", "vlr_host_alloc", "vlr_host_free",
     "vlr_node_create", "vlr_node_destroy", "vlr_node_n_devices", "vlr_node_device", "vlr_node_plan", "vlr_node_set_max_depth", "vlr_node_set_max_obs", "vlr_node_shard_range", "vlr_node_batch_run_host",
     "vlr_realign_batch", "vlr_realign_batch_host", "vlr_realign_fast_batch", "vlr_realign_fast_batch_host", "vlr_realign_homopolymer_batch", "vlr_realign_homopolymer_batch_host", "vlr_edit_distance_batch", "vlr_edit_distance_batch_host", "vlr_fdr_threshold", "vlr_contamination_posterior", "vlr_bamstats_open", "vlr_bamstats_add_bam", "vlr_bamstats_result", "vlr_bamstats_read", "vlr_bamstats_close", "vlr_selftest_math", "vlr_selftest_stream", "vlr_selftest_format_fixed", "vlr_selftest_afd_text",
     "vlr_obs_read", "vlr_obs_table_free", "vlr_obs_table_batch", "vlr_obs_table_sites", "vlr_obs_write", "vlr_calls_write", "vlr_ingest_last_timings", "vlr_ingest_total_timings",
@@ -42,7 +42,7 @@ class EngineError(RuntimeError):
 def build(force: bool = False) -> str:
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
-    srcs = [os.path.join(src_dir, f) for f in ("vlr_kernels.hip", "vlr_kernels_deep.hip", "vlr_kernels_wide.hip", "vlr_kernels_widedeep.hip", "vlr_realign.hip", "vlr_fdr.hip", "vlr_contam.hip", "vlr_callstats.hip", "vlr_bamstats.hip", "vlr_inflate.hip", "vlr_decode.hip", "vlr_host.cpp", "vlr_ingest.cpp", "vlr_plan.h", "vlr_gpuio.h", "vlr_callstats.h")] + [os.path.join(_HERE, "..", "include", "vlr.h")]
+    srcs = [os.path.join(src_dir, f) for f in ("vlr_kernels.hip", "vlr_kernels_lean.hip", "vlr_kernels_deep.hip", "vlr_kernels_wide.hip", "vlr_kernels_widedeep.hip", "vlr_realign.hip", "vlr_fdr.hip", "vlr_contam.hip", "vlr_callstats.hip", "vlr_bamstats.hip", "vlr_inflate.hip", "vlr_decode.hip", "vlr_host.cpp", "vlr_ingest.cpp", "vlr_plan.h", "vlr_gpuio.h", "vlr_callstats.h")] + [os.path.join(_HERE, "..", "include", "vlr.h")]
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", src_dir] + (["-B"] if force else []), stdout=subprocess.DEVNULL)
     return LIB_PATH
@@ -57,7 +57,7 @@ def source_id() -> str:
     """The id a build of the current sources would carry (same recipe as csrc/Makefile)."""
     import hashlib
     h = hashlib.sha1()
-    for f in ("csrc/vlr_kernels.hip", "csrc/vlr_kernels_deep.hip", "csrc/vlr_kernels_wide.hip", "csrc/vlr_kernels_widedeep.hip", "csrc/vlr_realign.hip", "csrc/vlr_fdr.hip", "csrc/vlr_contam.hip", "csrc/vlr_callstats.hip", "csrc/vlr_bamstats.hip", "csrc/vlr_inflate.hip", "csrc/vlr_decode.hip", "csrc/vlr_host.cpp", "csrc/vlr_ingest.cpp", "csrc/vlr_plan.h", "csrc/vlr_gpuio.h", "csrc/vlr_callstats.h", "../include/vlr.h", "../include/vlr_detmath.h"):
+    for f in ("csrc/vlr_kernels.hip", "csrc/vlr_kernels_lean.hip", "csrc/vlr_kernels_deep.hip", "csrc/vlr_kernels_wide.hip", "csrc/vlr_kernels_widedeep.hip", "csrc/vlr_realign.hip", "csrc/vlr_fdr.hip", "csrc/vlr_contam.hip", "csrc/vlr_callstats.hip", "csrc/vlr_bamstats.hip", "csrc/vlr_inflate.hip", "csrc/vlr_decode.hip", "csrc/vlr_host.cpp", "csrc/vlr_ingest.cpp", "csrc/vlr_plan.h", "csrc/vlr_gpuio.h", "csrc/vlr_callstats.h", "../include/vlr.h", "../include/vlr_detmath.h"):
         with open(os.path.join(_HERE, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
@@ -119,6 +119,8 @@ def lib():
         L.vlr_batch_run_host.argtypes = [C.c_void_p, C.POINTER(abi.Batch), C.POINTER(abi.Results)]
         L.vlr_plan_last_kernel_ms.restype = C.c_int
         L.vlr_plan_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.vlr_plan_last_instance.restype = C.c_int
+        L.vlr_plan_last_instance.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.vlr_host_alloc.restype = C.c_void_p
         L.vlr_host_alloc.argtypes = [C.c_size_t]
         L.vlr_host_free.restype = None
@@ -250,6 +252,12 @@ class Plan:
         ms = C.c_float()
         _check(lib().vlr_plan_last_kernel_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+    def last_instance(self):
+        """(waves per SIMD, lean) of the call-kernel build the last call launch of this plan took (vlr_plan_last_instance)."""
+        waves, lean = C.c_int(), C.c_int()
+        _check(lib().vlr_plan_last_instance(self._h, C.byref(waves), C.byref(lean)))
+        return int(waves.value), bool(lean.value)
 
     def work_counters(self, reset: bool = False):
         out = (C.c_ulonglong * 2)()
