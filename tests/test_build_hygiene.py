@@ -109,7 +109,19 @@ def test_asm_statements_of_the_call_kernel_carry_nothing_the_compiler_cannot_che
     and a template of more than one instruction declares every output early-clobber."""
     text = open(os.path.join(ROOT, "varlociraptor_amd", "csrc", "vlr_kernels.hip")).read()
     stmts = _asm_statements(text)
-    assert len(stmts) >= 6
+    # the parser sees every asm statement of the file: as many as an independent count of the keyword outside comments and
+    # string literals, and each of the five there are — the three empty pinning blocks and the two templates of the bitonic step
+    code = re.sub(r'"(?:[^"\\\n]|\\.)*"|//[^\n]*|/\*.*?\*/', lambda m: '""' if m.group(0)[0] == '"' else " ", text, flags=re.S)
+    assert len(stmts) == len(re.findall(r"\basm\b", code))
+    shapes = sorted(([ins.split()[0] for ins in template.replace("\\t", " ").split("\\n") if ins.strip()], outputs) for template, outputs in stmts)
+    select = ["v_cmp_lt_u32_e32", "s_xor_b64", "v_cndmask_b32_e32"]
+    assert shapes == sorted([
+        ([], ["+v"]),                                          # fresh_lane: lane barrier
+        ([], ["+v", "+v"]),                                    # park_sd: pair barrier in VGPRs
+        ([], ["+s", "+s"]),                                    # fresh_sd: pair barrier in SGPRs
+        (select, ["=v"]),                                      # bitonic_pick: compare / select
+        (select + ["v_cndmask_b32_e32"], ["=&v", "=&v"]),      # bitonic_pair: compare / select both ways
+    ])
     for template, outputs in stmts:
         insts = [t.strip() for t in template.replace("\\n", "\n").replace("\\t", " ").split("\n") if t.strip()]
         for ins in insts:

@@ -60,14 +60,7 @@ namespace vlr {
 constexpr unsigned kDeepEvaluated = 1u << 31;
 
 // optional per-phase cycle accounting (build with -DVLR_PROFILE): wall cycles of the wave spent per phase
-#if defined(VLR_PROFILE) && defined(VLR_PROFILE_VALU)
-// Per-region VALU INSTRUCTION counts instead of cycles: tools/valu_profile.sh rewrites the kernel's assembly so that every basic
-// block adds its number of VALU instructions to s100 (a register the compiler leaves alone: it stops at s99); the regions read it
-// where the cycle profile reads the clock.
-#define PROF_DECL unsigned long long prof[40]; unsigned long long prof_t;
-#define PROF_START(c) do { unsigned t_; asm volatile("s_mov_b32 s100, 0\n\ts_mov_b32 %0, 0" : "=s"(t_)); (c).prof_t = t_; } while (0)
-#define PROF_ADD(c, i) do { unsigned t_; asm volatile("s_mov_b32 %0, s100" : "=s"(t_)); (c).prof[i] += (unsigned)(t_ - (unsigned)(c).prof_t); (c).prof_t = t_; } while (0)
-#elif defined(VLR_PROFILE)
+#ifdef VLR_PROFILE
 #define PROF_DECL unsigned long long prof[40]; unsigned long long prof_t;
 #define PROF_START(c) (c).prof_t = __builtin_amdgcn_s_memtime()
 #define PROF_ADD(c, i) do { unsigned long long t_ = __builtin_amdgcn_s_memtime(); (c).prof[i] += t_ - (c).prof_t; (c).prof_t = t_; } while (0)
@@ -75,19 +68,6 @@ constexpr unsigned kDeepEvaluated = 1u << 31;
 #define PROF_DECL
 #define PROF_START(c)
 #define PROF_ADD(c, i)
-#endif
-// Issue priority of a wave (s_setprio): experiment of round 5 — the term products of a pass carry three independent chains per lane and
-// tolerate waiting for an issue slot, the control of the integrator around them is one dependent chain.  -DVLR_PRIO=1: products low, the
-// rest high; 2: the other way round; unset: no priority instructions.
-#if defined(VLR_PRIO) && VLR_PRIO == 1
-#define VLR_PRIO_PRODUCTS() __builtin_amdgcn_s_setprio(0)
-#define VLR_PRIO_CHAIN() __builtin_amdgcn_s_setprio(3)
-#elif defined(VLR_PRIO) && VLR_PRIO == 2
-#define VLR_PRIO_PRODUCTS() __builtin_amdgcn_s_setprio(3)
-#define VLR_PRIO_CHAIN() __builtin_amdgcn_s_setprio(0)
-#else
-#define VLR_PRIO_PRODUCTS()
-#define VLR_PRIO_CHAIN()
 #endif
 
 #define VLR_NEG_INF (-__builtin_huge_val())
@@ -203,100 +183,13 @@ struct WaveSt {
 };
 
 // ------------------------------------------------------------------------------------------------
-// Diagnosis builds of round 6 (VERDICT r05 "next" #1; tools/exec_assert.sh, tools/trace_diff.py).  Neither is part of a shipped library.
-//  -DVLR_DBG_EXEC_ASSERT: every cross-lane operation of the call kernel checks the EXEC mask it runs under against what the site
-//     assumes, and every UNI() / uni_d() / ldc() that its operand really is the same on all active lanes; what is seen goes to
-//     g_xsite[source line] = {site was executed, executions under partial EXEC, executions that break the site's rule, OR of the
-//     disabled lanes}.  Rules: DPP row operations and ds_swizzle inside a row need every 16-lane row all on or all off (a lane
-//     whose source is disabled reads 0 under bound_ctrl); whole-wave shuffles and row-leader reads need full EXEC; a lane read needs
-//     that lane on; a "uniform" value must be uniform.
-//  -DVLR_DBG_TRACE: the wave of ONE locus (vlr_debug_trace_arm) appends (id, source line, EXEC, 64 lane values) records to a device
-//     buffer at the TRC() points below; two builds of the same source are compared record by record on the host.
-#if (defined(VLR_DBG_EXEC_ASSERT) || defined(VLR_DBG_TRACE)) && !VLR_DEEP && !defined(VLR_WIDE_BUILD)
-#define VLR_DBG_OWNER 1   // this translation unit defines the device symbols and the host accessors
-#endif
-#ifdef VLR_DBG_EXEC_ASSERT
-constexpr int kXSites = 8192;
-#ifdef VLR_DBG_OWNER   // (the deep and wide builds are translation units of their own: their checks compile to nothing)
-__device__ unsigned long long g_xsite[kXSites * 4];
-#endif
-enum { XK_ROW = 0, XK_WAVE = 1, XK_ANY = 2 };
-__device__ __forceinline__ bool xrows_partial(unsigned long long e) {
-    bool bad = false;
-    for (int r = 0; r < 4; ++r) { const unsigned b = (unsigned)(e >> (16 * r)) & 0xffffu; bad = bad || (b != 0u && b != 0xffffu); }
-    return bad;
-}
-__device__ __forceinline__ void xnote(int line, unsigned long long e, bool viol) {
-#if VLR_DEEP || defined(VLR_WIDE_BUILD)
-    (void)line; (void)e; (void)viol;
-#else
-    if (__builtin_amdgcn_mbcnt_hi((unsigned)(e >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)e, 0u)) != 0u) return;  // first active lane
-    unsigned long long* g = g_xsite + 4 * (line & (kXSites - 1));
-    g[0] = 1ull;
-    if (e != ~0ull) { atomicAdd(g + 1, 1ull); atomicOr(g + 3, ~e); }
-    if (viol) atomicAdd(g + 2, 1ull);
-#endif
-}
-__device__ __forceinline__ void xchk(int kind, int line) {
-    const unsigned long long e = __builtin_amdgcn_read_exec();
-    xnote(line, e, kind == XK_ROW ? xrows_partial(e) : kind == XK_WAVE ? e != ~0ull : false);
-}
-__device__ __forceinline__ void xchk_lane(int l, int line) {
-    const unsigned long long e = __builtin_amdgcn_read_exec();
-    xnote(line, e, ((e >> (l & 63)) & 1ull) == 0ull);
-}
-__device__ __forceinline__ void xchk_uni(bool differs, int line) {
-    const unsigned long long e = __builtin_amdgcn_read_exec();
-    const bool viol = __builtin_amdgcn_ballot_w64(differs) != 0ull;
-    xnote(line, e, viol);
-}
-#define VLR_XCHK(kind, line) xchk(kind, line)
-#define VLR_XCHK_LANE(l, line) xchk_lane(l, line)
-#define VLR_XCHK_UNI(differs, line) xchk_uni(differs, line)
-#else
-#define VLR_XCHK(kind, line) ((void)0)
-#define VLR_XCHK_LANE(l, line) ((void)0)
-#define VLR_XCHK_UNI(differs, line) ((void)0)
-#endif
-#ifdef VLR_DBG_TRACE
-constexpr int kTraceCap = 1 << 16;
-#ifdef VLR_DBG_OWNER
-__device__ double g_trace_val[(size_t)kTraceCap * 64];
-__device__ unsigned long long g_trace_hdr[(size_t)kTraceCap * 2];  // (id << 32) | source line, EXEC
-__device__ int g_trace_n;
-__device__ long long g_trace_locus = -1;
-#endif
-__device__ __forceinline__ void trc_rec(long long locus, int id, double v, int line) {
-#if !VLR_DEEP && !defined(VLR_WIDE_BUILD)
-    if (locus != __hip_atomic_load(&g_trace_locus, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    const unsigned long long e = __builtin_amdgcn_read_exec();
-    int pos = 0;
-    const bool first = __builtin_amdgcn_mbcnt_hi((unsigned)(e >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)e, 0u)) == 0u;
-    if (first) pos = atomicAdd(&g_trace_n, 1);
-    pos = __builtin_amdgcn_readfirstlane(pos);
-    if (pos >= kTraceCap) return;
-    g_trace_val[(size_t)pos * 64 + (threadIdx.x & 63)] = v;
-    if (first) { g_trace_hdr[2 * (size_t)pos] = ((unsigned long long)(unsigned)id << 32) | (unsigned)line; g_trace_hdr[2 * (size_t)pos + 1] = e; }
-#endif
-}
-#define TRC(c, id, v) trc_rec((c).locus, (id), (double)(v), __LINE__)
-#define TRCB(c, id, v) trc_rec((c).locus, (id), __longlong_as_double((long long)(v)), __LINE__)   // raw 64-bit pattern
-#else
-#define TRC(c, id, v) ((void)0)
-#define TRCB(c, id, v) ((void)0)
-#endif
-#ifdef VLR_DBG_EXEC_ASSERT
-#define VLR_RDLANE(v, l) rdlane_i((v), (l), __LINE__)
-#define VLR_SHFL(v, l) shfl_chk((v), (l), __LINE__)
-#define VLR_SHFL_XOR(v, m) shfl_xor_chk((v), (m), __LINE__)
-__device__ __forceinline__ int rdlane_i(int v, int l, int line) { VLR_XCHK_LANE(l, line); return __builtin_amdgcn_readlane(v, l); }
-template <class T> __device__ __forceinline__ T shfl_chk(T v, int l, int line) { VLR_XCHK(XK_WAVE, line); return __shfl(v, l, 64); }
-template <class T> __device__ __forceinline__ T shfl_xor_chk(T v, int m, int line) { VLR_XCHK(XK_WAVE, line); return __shfl_xor(v, m); }
-#else  // (the plain builtins: the shipped code is the same instruction for instruction with and without these names)
+// Cross-lane operations by name, so that the static EXEC audit (tools/isa_exec_audit.py) and the comments can refer to their sites.
+// What each kind assumes of the EXEC mask it runs under: DPP row operations and ds_swizzle inside a row need every 16-lane row all on
+// or all off (a lane whose source is disabled reads 0 under bound_ctrl); whole-wave shuffles and row-leader reads need full EXEC; a
+// lane read needs that lane on; a "uniform" value (UNI() / uni_d() / ldc()) must be the same on all active lanes.
 #define VLR_RDLANE(v, l) __builtin_amdgcn_readlane((v), (l))
 #define VLR_SHFL(v, l) __shfl((v), (l), 64)
 #define VLR_SHFL_XOR(v, m) __shfl_xor((v), (m))
-#endif
 
 // one observation row (all ten columns) of lane `i`; rows beyond `end` read as an empty observation
 struct ObsRow { uint32_t f; float pm, pa, pr, miss, psa, pdo, phb, hpa, hpv; };
@@ -315,28 +208,11 @@ __device__ __forceinline__ ObsRow load_obs_row(const DevBatch& batch, uint32_t i
 // ------------------------------------------------------------------------------------------------
 // values that are wave-uniform by construction but live in VGPRs/LDS: moving them to SGPRs lets the compiler
 // use scalar branches and scalar (cached) loads of plan data instead of vector loads
-#ifdef VLR_NO_UNI  // diagnosis builds: leave uniformity to the compiler's own analysis
-#define UNI(x) (x)
-__device__ __forceinline__ double uni_d(double v) { return v; }
-#define UNI64(x) (x)
-#else
 #define UNI64(x) __double_as_longlong(uni_d(__longlong_as_double(x)))
-#ifdef VLR_DBG_EXEC_ASSERT
-#define UNI(x) uni_i_chk((x), __LINE__)
-__device__ __forceinline__ int uni_i_chk(int v, int line) {
-    const int r = __builtin_amdgcn_readfirstlane(v);
-    VLR_XCHK_UNI(v != r, line);
-    return r;
-}
-#else
 #define UNI(x) __builtin_amdgcn_readfirstlane(x)
-#endif
-__device__ __forceinline__ double uni_d(double v, int site = __builtin_LINE()) {
-    const double r = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-    VLR_XCHK_UNI(__double_as_longlong(v) != __double_as_longlong(r), site);
-    return r;
+__device__ __forceinline__ double uni_d(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
-#endif
 
 // Ordering of LDS traffic between the lanes of ONE wave (the workgroup is a single wave64): same-wave LDS operations
 // execute in program order, so all that is needed is that the COMPILER keeps the stores of some lanes ahead of the loads
@@ -350,8 +226,6 @@ __device__ __forceinline__ double uni_d(double v, int site = __builtin_LINE()) {
 // compiler-level ordering of VLR_WAVE_FENCE() (a hardware barrier also drains every outstanding load of the wave first)
 #if defined(VLR_WB_SYNC)
 #define VLR_WAVE_FENCE() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); } while (0)
-#elif defined(VLR_WB_PLAIN)
-#define VLR_WAVE_FENCE() __builtin_amdgcn_wave_barrier()
 #else
 #define VLR_WAVE_FENCE() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 #endif
@@ -359,17 +233,7 @@ __device__ __forceinline__ double uni_d(double v, int site = __builtin_LINE()) {
 
 // The lane id as a value the optimiser cannot hoist: without it every lane-derived constant of the chain runners
 // ((double)(lane - 1), row masks, ...) is computed once before the hypothesis loop and then SPILLED across it.
-// (VLR_FRESH_MASK: diagnosis builds keep the opaque id only at the call sites whose bit is set — the sites are numbered in source order)
-#ifndef VLR_FRESH_MASK
-#define VLR_FRESH_MASK 0xffffffffu
-#endif
 __device__ __forceinline__ int fresh_lane(int lane) {
-#ifdef VLR_DBG_NO_FRESH_LANE
-    return lane;
-#endif
-#ifdef VLR_FRESH_BPERMUTE   // the lane's own id through the LDS crossbar: opaque to the optimiser without inline assembly
-    return __builtin_amdgcn_ds_bpermute(lane << 2, lane);
-#endif
     asm volatile("" : "+v"(lane));
     return lane;
 }
@@ -388,9 +252,9 @@ __device__ __forceinline__ int fresh_lane(int lane) {
 //    input: without early-clobber outputs the compiler may give %0 the register of that input — which it did as soon as the parked
 //    pair had been spilled to a VGPR lane and was reloaded into temporaries in front of the statement — and the double came back
 //    as (lo, lo): a reverse rate of exactly 0 for 1 - 0.5.  That was the "max-ILP scheduler with fresh_lane" deviation of round 5.
-// Found with the per-wave trace of tools/exec_trace_run.py (first differing value: coefficient q of a reverse-strand read, in both
-// configurations); tests/test_build_hygiene.py now refuses lane reads and multi-instruction templates without early-clobber
-// outputs in this file's asm statements, and both configurations are back in the build matrix.
+// (First differing value in both configurations: coefficient q of a reverse-strand read; profiles/HISTORY.md tells how it was found.)
+// tests/test_build_hygiene.py now refuses lane reads and multi-instruction templates without early-clobber outputs in this file's
+// asm statements, and both configurations are back in the build matrix.
 struct SgprD { int lo, hi; };
 __device__ __forceinline__ SgprD park_sd(double v) {
     // (the empty statement hides from the optimiser that the halves are wave-uniform: it folds a lane read of a value it knows to be
@@ -424,18 +288,8 @@ __device__ __forceinline__ double div3(double x) {
 // wave-uniform.  (The __shfl_xor butterflies these replace go through ds_bpermute: six lane-address registers that the compiler
 // kept alive — and spilled — across the whole kernel, and six LDS round trips per reduction.)
 template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v, int site = __builtin_LINE()) {
-    VLR_XCHK(XK_ROW, site);
-#ifdef VLR_DBG_DPP_SHFL  // diagnosis builds: the four permutations of the reductions through ds_bpermute instead of DPP moves of the halves
-    const int l_ = (int)__lane_id();
-    const int src_ = CTRL == 0xB1 ? (l_ ^ 1) : CTRL == 0x4E ? (l_ ^ 2) : CTRL == 0x141 ? ((l_ & ~7) | (7 - (l_ & 7))) : CTRL == 0x140 ? ((l_ & ~15) | (15 - (l_ & 15)))
-                   : CTRL == 0x124 ? ((l_ & ~15) | ((l_ + 4) & 15)) : CTRL == 0x128 ? ((l_ & ~15) | ((l_ + 8) & 15)) : l_;
-    if (CTRL == 0xB1 || CTRL == 0x4E || CTRL == 0x141 || CTRL == 0x140 || CTRL == 0x124 || CTRL == 0x128) return __shfl(v, src_, 64);
-#endif
+__device__ __forceinline__ double dpp_f64(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
-#ifdef VLR_DBG_DPP_NOP  // diagnosis builds: wait states between whatever wrote the halves and the DPP reads
-    asm volatile("s_nop 7" : "+v"(lo), "+v"(hi));
-#endif
     // every lane has a valid source under these permutations: bound_ctrl with an undefined `old` lets the compiler write the
     // destination directly instead of copying the source first (three instructions per f64 permute otherwise)
     lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
@@ -443,36 +297,22 @@ __device__ __forceinline__ double dpp_f64(double v, int site = __builtin_LINE())
     return __hiloint2double(hi, lo);
 }
 template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v, int site = __builtin_LINE()) {
-    VLR_XCHK(XK_ROW, site);
-#ifdef VLR_DBG_DPP_NOP
-    asm volatile("s_nop 7" : "+v"(v));
-#endif
+__device__ __forceinline__ int dpp_i32(int v) {
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
 }
-__device__ __forceinline__ double lane_d(double v, int l, int site = __builtin_LINE()) {
-    VLR_XCHK_LANE(l, site);
-#ifdef VLR_DBG_LANE_SHFL
-    return __shfl(v, l, 64);
-#endif
-#ifdef VLR_DBG_DPP_NOP
-    { int lo_ = __double2loint(v), hi_ = __double2hiint(v); asm volatile("s_nop 7" : "+v"(lo_), "+v"(hi_)); v = __hiloint2double(hi_, lo_); }
-#endif
+__device__ __forceinline__ double lane_d(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
-__device__ __forceinline__ double wave_sum(double v, int site = __builtin_LINE()) {
-    VLR_XCHK(XK_WAVE, site);
-    v += dpp_f64<0xB1>(v, site); v += dpp_f64<0x4E>(v, site); v += dpp_f64<0x141>(v, site); v += dpp_f64<0x140>(v, site);
-    return (lane_d(v, 0, site) + lane_d(v, 16, site)) + (lane_d(v, 32, site) + lane_d(v, 48, site));
+__device__ __forceinline__ double wave_sum(double v) {
+    v += dpp_f64<0xB1>(v); v += dpp_f64<0x4E>(v); v += dpp_f64<0x141>(v); v += dpp_f64<0x140>(v);
+    return (lane_d(v, 0) + lane_d(v, 16)) + (lane_d(v, 32) + lane_d(v, 48));
 }
-__device__ __forceinline__ double wave_max(double v, int site = __builtin_LINE()) {
-    VLR_XCHK(XK_WAVE, site);
-    v = fmax(v, dpp_f64<0xB1>(v, site)); v = fmax(v, dpp_f64<0x4E>(v, site)); v = fmax(v, dpp_f64<0x141>(v, site)); v = fmax(v, dpp_f64<0x140>(v, site));
-    return fmax(fmax(lane_d(v, 0, site), lane_d(v, 16, site)), fmax(lane_d(v, 32, site), lane_d(v, 48, site)));
+__device__ __forceinline__ double wave_max(double v) {
+    v = fmax(v, dpp_f64<0xB1>(v)); v = fmax(v, dpp_f64<0x4E>(v)); v = fmax(v, dpp_f64<0x141>(v)); v = fmax(v, dpp_f64<0x140>(v));
+    return fmax(fmax(lane_d(v, 0), lane_d(v, 16)), fmax(lane_d(v, 32), lane_d(v, 48)));
 }
-__device__ __forceinline__ int wave_or(int v, int site = __builtin_LINE()) {
-    VLR_XCHK(XK_WAVE, site);
-    v |= dpp_i32<0xB1>(v, site); v |= dpp_i32<0x4E>(v, site); v |= dpp_i32<0x141>(v, site); v |= dpp_i32<0x140>(v, site);
+__device__ __forceinline__ int wave_or(int v) {
+    v |= dpp_i32<0xB1>(v); v |= dpp_i32<0x4E>(v); v |= dpp_i32<0x141>(v); v |= dpp_i32<0x140>(v);
     return (__builtin_amdgcn_readlane(v, 0) | __builtin_amdgcn_readlane(v, 16)) | (__builtin_amdgcn_readlane(v, 32) | __builtin_amdgcn_readlane(v, 48));
 }
 __device__ inline int popc64(unsigned long long m) { return __popcll(m); }
@@ -517,20 +357,14 @@ __device__ inline double lse_value(double M, double S) {
 // Reading them through the constant address space makes the loads scalar (s_load into SGPRs, scalar data cache)
 // instead of per-lane vector loads that every lane has to wait for.
 #define VLR_K4 __attribute__((address_space(4)))
-#ifdef VLR_NO_K4
 template <class T>
-__device__ __forceinline__ T ldc(const T* ptr, int site = 0) { return *ptr; }
-#else
-template <class T>
-__device__ __forceinline__ T ldc(const T* ptr, int site = __builtin_LINE()) {
+__device__ __forceinline__ T ldc(const T* ptr) {
     // the address is wave-uniform by construction; say so even where the compiler's divergence analysis cannot see it
     const unsigned long long a = (unsigned long long)(uintptr_t)ptr;
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a);
     const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
-    VLR_XCHK_UNI(a != (((unsigned long long)hi << 32) | lo), site);
     return *(const VLR_K4 T*)(uintptr_t)(((unsigned long long)hi << 32) | lo);
 }
-#endif
 __device__ __forceinline__ DevSpectrum ld_spec(const DevSpectrum* g) {
     DevSpectrum s;
     s.kind = ldc(&g->kind); s.set_off = ldc(&g->set_off); s.set_len = ldc(&g->set_len);
@@ -731,12 +565,6 @@ __device__ inline double ddacc_exp(const DdAcc& a, double m) {
 // mantissa/exponent renormalisation of a POSITIVE NORMAL double with integer ops on the high word (the
 // fast path guarantees every partial product stays far above 2^-1022)
 __device__ __forceinline__ void renorm_pos(double& P, int& E) {
-#ifdef VLR_DBG_RENORM_FREXP  // diagnosis builds (tools/o1_variant.sh): the same renormalisation through the frexp instructions
-    int e_;
-    P = __builtin_frexp(P, &e_);
-    E += e_;
-    return;
-#endif
     const int hi = __double2hiint(P);
     E += (int)(((unsigned)hi >> 20) & 0x7ffu) - 1022;
     P = __hiloint2double((hi & 0x800fffff) | 0x3fe00000, __double2loint(P));
@@ -841,9 +669,6 @@ __device__ __forceinline__ void accum_terms_e(const double* __restrict__ coef, c
 template <int NP, int W>
 __device__ __forceinline__ void accum_terms(const double* __restrict__ coef, const double* __restrict__ ecoef, int D, int k, bool fast,
                                             const double* al, const double* be, double* P, int* E) {
-#ifdef VLR_DBG_ROBUST_TERMS  // diagnosis builds: every product through the per-term frexp path
-    fast = false;
-#endif
     bool nz = false;
 #pragma unroll
     for (int j = 0; j < NP; ++j) nz = nz || (be[j] != 0.0);
@@ -1073,9 +898,6 @@ __device__ inline void alpha_beta(const DevPlan& p, int s, double a, double b, d
 __device__ __forceinline__ int* kshift(const Ctx& c) { return (int*)(c.rs + c.nrs); }
 // ln 2 x (exponents taken out of the coefficients of the samples in `mask`): added to every pileup log-likelihood of those samples
 __device__ __forceinline__ double kshift_ln(const Ctx& c, int mask) {
-#ifdef VLR_NO_RESCUE
-    return 0.0;
-#endif
     int k = 0;
     for (int s = 0; s < c.S; ++s)
         if ((mask >> s) & 1) k += kshift(c)[s];
@@ -1121,13 +943,8 @@ __device__ inline double sample_lik_point(Ctx& c, int s, double a, double b) {  
     accum_terms<1, 64>(c.coef + 2 * off, ecoef_of(c, s, off), D, c.lane, (w->fastok >> s) & 1, &al, &be, P1, E1);
     reduce_terms<1, 64>(P1, E1);
     }
-    TRC(c, 120, P1[0]); TRC(c, 121, E1[0]); TRC(c, 122, al); TRC(c, 123, be); TRC(c, 124, s);
     if (c.lane == 0) { w->work[0] += 1; w->work[1] += (unsigned long long)D; }
-#ifdef VLR_NO_RESCUE
-    return uni_d(ln_product_mantissa(P1[0]) + (double)E1[0] * kLn2);
-#else
     return uni_d(ln_product_mantissa(P1[0]) + (double)(E1[0] + kshift(c)[s]) * kLn2);
-#endif
 }
 __device__ inline double sample_lik(Ctx& c, int s, double a, double b) {
     WaveSt* w = c.w;
@@ -1362,7 +1179,7 @@ __device__ inline int log_begin(Ctx& c, int kind, int n, int s_in, int disc, int
     const int at = log_reserve(c, 1 + S + 2 * nl + payload_words);
     if (at < 0) return -1;
     WaveSt* w = c.w;
-    const int lane = (((VLR_FRESH_MASK >> 0) & 1u) ? fresh_lane(c.lane) : (c.lane));  // keeps the lane-derived offsets below out of registers that live across the kernel
+    const int lane = fresh_lane(c.lane);  // keeps the lane-derived offsets below out of registers that live across the kernel
     if (lane == 0) c.lg[at] = __longlong_as_double(log_header(kind, n, s_in, disc, c.group, nl));
     if (lane < S) c.lg[at + 1 + lane] = w->ops_vaf[lane];
     if (lane < nl) {
@@ -1378,7 +1195,7 @@ __device__ inline void log_leaf(Ctx& c, double joint) {
 __device__ inline void log_table(Ctx& c, int s_in, const double* tx, const double* tv, int n) {  // a single chain, all 64 lanes
     const int at = log_begin(c, 1, n, s_in, c.disc & ~(1 << s_in), 2 * n);
     if (at < 0) return;
-    for (int i = (((VLR_FRESH_MASK >> 1) & 1u) ? fresh_lane(c.lane) : (c.lane)); i < n; i += 64) { c.lg[at + i] = tx[i]; c.lg[at + n + i] = tv[i]; }
+    for (int i = fresh_lane(c.lane); i < n; i += 64) { c.lg[at + i] = tx[i]; c.lg[at + n + i] = tv[i]; }
 }
 
 // ---- all-discrete roots (DevDLeaf): every leaf of the root on its own lane --------------------------------------
@@ -1410,7 +1227,7 @@ __device__ inline int dleaf_wave_best(const DevDLeaf* leaves, double bJ, int bL,
 __device__ inline double eval_discrete_root(Ctx& c, int l0, int l1) {
     const DevPlan& p = *c.plan;
     WaveSt* w = c.w;
-    const int lane = (((VLR_FRESH_MASK >> 2) & 1u) ? fresh_lane(c.lane) : (c.lane)), S = c.S;
+    const int lane = fresh_lane(c.lane), S = c.S;
     const DevDLeaf* leaves = p.dleaf;
     unsigned cr = 0;
     for (int s = 0; s < S; ++s)
@@ -1710,7 +1527,6 @@ __device__ inline double leaf_joint(Ctx& c) {
         PROF_ADD(c, 21);  // leaf: prior
     }
     joint = uni_d(joint);
-    TRC(c, 125, joint);
     if (joint != joint) c.status |= VLR_LOCUS_NAN;
     if (log_on(c)) log_leaf(c, joint);
     if (kHasReplay && __builtin_expect(c.replay != 0, 0)) afd_consider(c, joint, -1, 0.0);
@@ -1801,7 +1617,7 @@ __device__ __forceinline__ double run_leaf_chain(Ctx& c, RangeSt& rl, double* tx
 #endif
     const DevPlan& p = *c.plan;
     WaveSt* w = c.w;
-    const int lane = (((VLR_FRESH_MASK >> 3) & 1u) ? fresh_lane(c.lane) : (c.lane));
+    const int lane = fresh_lane(c.lane);
     const int inner = UNI(rl.sample);
     const double lo = uni_d(rl.lo), hi = uni_d(rl.hi), res = uni_d(rl.res);
     const RangeV orig{uni_d(rl.ostart), uni_d(rl.oend), UNI(rl.olex), UNI(rl.orex)};
@@ -2002,23 +1818,23 @@ __device__ __forceinline__ double run_leaf_chain(Ctx& c, RangeSt& rl, double* tx
 // run concurrently, one per 16-lane DPP row.  Every "uniform" control instruction of the adaptive integrator now
 // serves four chains; the row's 16 lanes are split into (point, slice) groups for the pileup products and the
 // partial products are combined with in-row DPP permutes (a 16-lane row is exactly one DPP row).
-__device__ __forceinline__ double row_max(double v, int site = __builtin_LINE()) {
-    v = fmax(v, dpp_f64<0xB1>(v, site)); v = fmax(v, dpp_f64<0x4E>(v, site)); v = fmax(v, dpp_f64<0x141>(v, site)); v = fmax(v, dpp_f64<0x140>(v, site));
+__device__ __forceinline__ double row_max(double v) {
+    v = fmax(v, dpp_f64<0xB1>(v)); v = fmax(v, dpp_f64<0x4E>(v)); v = fmax(v, dpp_f64<0x141>(v)); v = fmax(v, dpp_f64<0x140>(v));
     return v;
 }
-__device__ __forceinline__ double row_sum(double v, int site = __builtin_LINE()) {
-    v += dpp_f64<0xB1>(v, site); v += dpp_f64<0x4E>(v, site); v += dpp_f64<0x141>(v, site); v += dpp_f64<0x140>(v, site);
+__device__ __forceinline__ double row_sum(double v) {
+    v += dpp_f64<0xB1>(v); v += dpp_f64<0x4E>(v); v += dpp_f64<0x141>(v); v += dpp_f64<0x140>(v);
     return v;
 }
 // row maximum of signed 64-bit keys (every lane of the 16-lane row ends with it)
-__device__ __forceinline__ long long row_max_i64(long long k, int site = __builtin_LINE()) {
-#define VLR_STEP_(CTRL) { const long long o_ = (long long)(((unsigned long long)(unsigned)dpp_i32<CTRL>((int)((unsigned long long)k >> 32), site) << 32) | (unsigned)dpp_i32<CTRL>((int)k, site)); k = o_ > k ? o_ : k; }
+__device__ __forceinline__ long long row_max_i64(long long k) {
+#define VLR_STEP_(CTRL) { const long long o_ = (long long)(((unsigned long long)(unsigned)dpp_i32<CTRL>((int)((unsigned long long)k >> 32)) << 32) | (unsigned)dpp_i32<CTRL>((int)k)); k = o_ > k ? o_ : k; }
     VLR_STEP_(0xB1) VLR_STEP_(0x4E) VLR_STEP_(0x141) VLR_STEP_(0x140)
 #undef VLR_STEP_
     return k;
 }
-__device__ __forceinline__ int row_or(int v, int site = __builtin_LINE()) {
-    v |= dpp_i32<0xB1>(v, site); v |= dpp_i32<0x4E>(v, site); v |= dpp_i32<0x141>(v, site); v |= dpp_i32<0x140>(v, site);
+__device__ __forceinline__ int row_or(int v) {
+    v |= dpp_i32<0xB1>(v); v |= dpp_i32<0x4E>(v); v |= dpp_i32<0x141>(v); v |= dpp_i32<0x140>(v);
     return v;
 }
 
@@ -2027,9 +1843,6 @@ __device__ __forceinline__ int row_or(int v, int site = __builtin_LINE()) {
 // fdlibm's e_log.c (< 1 ulp); no special cases (zero, negative, infinite, subnormal arguments cannot occur), about half the
 // instructions of the general log().  Returns ln(m) as hi part; the caller adds E * ln 2.
 __device__ __forceinline__ double ln_mantissa(double m) {
-#ifdef VLR_DBG_LIBM_LOG  // diagnosis builds: the library logarithm
-    return log(m);
-#endif
     const bool small = m < 0.70710678118654752440;
     const double mm = small ? m * 2.0 : m;       // [sqrt(1/2), sqrt(2))
     const double kk = small ? -1.0 : 0.0;
@@ -2051,11 +1864,7 @@ __device__ __forceinline__ double ln_mantissa(double m) {
 
 // value of row lane N on every lane of its 16-lane DPP row (row_newbcast: no LDS round trip)
 template <int N>
-__device__ __forceinline__ double row_bcast(double v, int site = __builtin_LINE()) {
-    VLR_XCHK(XK_ROW, site);
-#ifdef VLR_DBG_BCAST_SHFL
-    return __shfl(v, ((int)__lane_id() & ~15) | N, 64);
-#endif
+__device__ __forceinline__ double row_bcast(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __builtin_amdgcn_update_dpp(0, lo, 0x150 + N, 0xF, 0xF, true);
     hi = __builtin_amdgcn_update_dpp(0, hi, 0x150 + N, 0xF, 0xF, true);
@@ -2067,13 +1876,9 @@ __device__ __forceinline__ double row_bcast(double v, int site = __builtin_LINE(
 // hold {c, q} = {1, 0}, so their term is exactly 1.  Same association as accum_terms_e's two-term groups (mantissas are
 // bit-identical); no renormalisation: every term is in [2^-70, 2] (WaveSt::vfast), 13 of them stay normal.
 constexpr int kRegSlots = 13;  // 16 * 13 = 208 observations of the integrated sample
-#ifdef VLR_DBG_REGHELD  // diagnosis builds: fewer (or no) coefficient pairs held in registers across a batch
-constexpr int kRegHeld = VLR_DBG_REGHELD;
-#else
 constexpr int kRegHeld = 8;    // slots whose coefficient pairs stay in registers for the whole batch; deeper slots of the 13-slot
                                // variant are re-read from LDS every pass (five b128 reads): holding all 13 pushed the
                                // 3-waves-per-SIMD build 20 VGPRs over its budget and the spills around the batch loop went to HBM
-#endif
 template <int NS>
 __device__ __forceinline__ void reg_products(const double* cc, const double* cq, const double* lcoef, int rl, int D, const double* al, double* P) {
     constexpr int NR = NS < kRegHeld ? NS : kRegHeld;
@@ -2212,18 +2017,14 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
     int k = 0, tn = 0;
     bool failed = false, sawnan = false;
     const bool all_fast = __ballot(q.rowon && !q.cls_fast) == 0ull;
-#ifdef VLR_DBG_NO_ONES_PASS
-    const bool ones_on = false;
-#else
     const bool ones_on = ones_any(c) && ones_risk(c, q.inner);
-#endif
     const bool cap_safe = p.table_cap < kTableCapMax;  // the host's bound was not clamped (vlr_host.cpp: table capacity)
     double L = lo, R = hi, vL = VLR_NEG_INF, vR = VLR_NEG_INF, mid = lo;
     long long kL = 0, kR = 0;  // KEYED: the bracket ends' product keys
     PROF_ADD(c, 7);  // batch prologue (task fields, coefficient registers)
     for (;;) {
         PROF_ADD(c, 15);
-        const int rl = (((VLR_FRESH_MASK >> 4) & 1u) ? fresh_lane(rl0) : (rl0));  // lane masks (rl == 1, rl < nn, ...) are recomputed: one compare each instead of two lane reads of a spilled pair
+        const int rl = fresh_lane(rl0);  // lane masks (rl == 1, rl < nn, ...) are recomputed: one compare each instead of two lane reads of a spilled pair
         double px0, px1, px2;
         int nn;
         bool on;
@@ -2264,7 +2065,6 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
             live = live && !over;
             on = on && !over;
         }
-        TRC(c, 50, up); TRC(c, 51, k); TRC(c, 52, px0); TRC(c, 53, px1); TRC(c, 54, px2); TRC(c, 55, nn); TRC(c, 56, on ? 1 : 0); TRC(c, 57, rl); TRC(c, 58, tn);
         double al[3], be[3], P[3];
         int E[3];
         {
@@ -2286,31 +2086,16 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
                 }
             }
         }
-        VLR_PRIO_PRODUCTS();
         if (q.ecoef != nullptr && __ballot(on && (be[0] != 0.0 || be[1] != 0.0 || be[2] != 0.0)) != 0ull)
             lds_products_e(lcoef, q.ecoef, rl, D, al, be, P);
         else
             reg_products<NS>(cc, cq, lcoef, rl, D, al, P);
-        VLR_PRIO_CHAIN();
-        TRC(c, 60, P[0]); TRC(c, 61, P[1]); TRC(c, 62, P[2]); TRC(c, 63, al[0]); TRC(c, 64, al[1]); TRC(c, 65, al[2]);
         PROF_ADD(c, 12);  // pass: term products
         // reduction over the 16 lanes of the row, transposed from the first step on: a lane and its neighbour (xor 1) exchange what the
         // OTHER keeps — the even lane goes on with points 0 and 2, the odd one with point 1 (and a copy of 2) —, then the halves of a
         // quad (xor 2) do the same, lane t of every quad ends with the quad's product of point t, and the four quads are combined for
         // that point alone (rotations by 4 and 8 lanes): lane t of the row ends with point t.  Five multiply / exchange groups instead
         // of eight; the products are the same pairs in the same association as a full butterfly (a b = b a), bit for bit.
-#ifdef VLR_FULL_BUTTERFLY
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            int e;
-            P[t] = __builtin_frexp(P[t], &e); E[t] = e;
-            P[t] *= dpp_f64<0xB1>(P[t]); E[t] += dpp_i32<0xB1>(E[t]);      // quad_perm [1,0,3,2]
-            P[t] *= dpp_f64<0x4E>(P[t]); E[t] += dpp_i32<0x4E>(E[t]);      // quad_perm [2,3,0,1]
-        }
-        const int tq = rl & 3;
-        double Psel = tq == 1 ? P[1] : tq == 2 ? P[2] : P[0];
-        int Esel = tq == 1 ? E[1] : tq == 2 ? E[2] : E[0];
-#else
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             int e;
@@ -2330,7 +2115,6 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
         const int sendBE = tq == 0 ? KBE : KAE, ownBE = tq == 2 ? KBE : KAE;
         double Psel = ownB * dpp_f64<0x4E>(sendB);                         // quad_perm [2,3,0,1]
         int Esel = ownBE + dpp_i32<0x4E>(sendBE);
-#endif
         Psel *= dpp_f64<0x124>(Psel); Esel += dpp_i32<0x124>(Esel);        // row_ror:4
         Psel *= dpp_f64<0x128>(Psel); Esel += dpp_i32<0x128>(Esel);        // row_ror:8
         {
@@ -2338,7 +2122,6 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
             Psel = __builtin_frexp(Psel, &e);  // product of 16 mantissas >= 2^-16: one renormalisation suffices
             Esel += e;
         }
-        TRC(c, 66, Psel); TRC(c, 67, Esel);
         PROF_ADD(c, 13);  // pass: reduction
         const double x = rl == 0 ? px0 : rl == 1 ? px1 : px2;
         const bool owner = on && rl < nn;
@@ -2354,12 +2137,7 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
         long long key = 0;
         if (KEYED) {
             key = product_key(Psel, Esel);
-#ifdef VLR_DBG_UNIFORM_STORES  // diagnosis builds: the table append without a divergent region (lanes that own no point write to a scratch row)
-            { double* dx_ = owner ? q.tx + (tn + rl) : c.w->bpend[0] + (c.lane & 31); double* dv_ = owner ? q.tv + (tn + rl) : c.w->bvals[0] + (c.lane & 31);
-              *dx_ = x; *dv_ = __longlong_as_double(key); }
-#else
             if (owner) { q.tx[tn + rl] = x; q.tv[tn + rl] = __longlong_as_double(key); }
-#endif
         } else {
             double lm = ln_mantissa(Psel);
             if (__builtin_expect(ones_on, 0)) lm = ln_product_mantissa(Psel);  // (a direct all-ones product may be exactly zero)
@@ -2372,14 +2150,8 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
                 joint = pv + lik;
             }
             sawnan = sawnan || (owner && joint != joint);
-#ifdef VLR_DBG_UNIFORM_STORES
-            { double* dx_ = owner ? q.tx + (tn + rl) : c.w->bpend[0] + (c.lane & 31); double* dv_ = owner ? q.tv + (tn + rl) : c.w->bvals[0] + (c.lane & 31);
-              *dx_ = x; *dv_ = joint; }
-#else
             if (owner) { q.tx[tn + rl] = x; q.tv[tn + rl] = joint; }
-#endif
         }
-        TRCB(c, 68, key); TRC(c, 69, joint); TRC(c, 70, owner ? 1 : 0); TRC(c, 71, x);
         tn = on ? tn + nn : tn;
         PROF_ADD(c, 14);  // pass: log + prior + store
         if (__builtin_expect(up == UP_ROUND, 1)) {
@@ -2413,7 +2185,6 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
             const double mX = useM2 ? px2 : px1;
             const bool updL = on && keepR, updR = on && !keepR;
             L = updL ? mX : L; R = updR ? mX : R;
-            TRC(c, 72, L); TRC(c, 73, R); TRCB(c, 74, kL); TRCB(c, 75, kR); TRC(c, 76, vL); TRC(c, 77, vR); TRC(c, 78, keepR ? 1 : 0); TRC(c, 79, useM2 ? 1 : 0);
             act = on && ((R - L) >= res) && L < R;
             if (!__ballot(act)) { up = UP_TAIL; k = 0; }
         } else if (up == UP_TAIL) {
@@ -2435,7 +2206,6 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
         }
     }
     PROF_ADD(c, 15);  // pass: state update (+ loop control)
-    TRC(c, 80, tn);
     q.tn = tn; q.failed = failed; q.sawnan = sawnan;
 }
 
@@ -2446,7 +2216,7 @@ __device__ __forceinline__ void reg_chain_loop(Ctx& c, RegChain& q) {
 // one scalar xor with the stage's lane mask, one select; along a register bit it is one compare and two selects.  146 VALU
 // instructions for 64 keys, where ranking every key against every other one is 2 x 4 x 57.
 template <int XOR>
-__device__ __forceinline__ unsigned swz_xor(unsigned v, int site = __builtin_LINE()) { VLR_XCHK(XK_ROW, site); return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, (XOR << 10) | 0x1f); }
+__device__ __forceinline__ unsigned swz_xor(unsigned v) { return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, (XOR << 10) | 0x1f); }
 // lanes that keep the LARGER key in the cross-lane stage (k, j) / whose register pairs are sorted descending in a register stage of merge k
 template <int NB>
 __device__ constexpr unsigned long long bitonic_keepmax(int k, int j) {
@@ -2534,7 +2304,7 @@ __device__ __forceinline__ void run_chain_batch(Ctx& c, int rowmask, int inner) 
 #endif
     const DevPlan& p = *c.plan;
     WaveSt* w = c.w;
-    const int lane = (((VLR_FRESH_MASK >> 5) & 1u) ? fresh_lane(c.lane) : (c.lane)), row = lane >> 4, rl = lane & 15;
+    const int lane = fresh_lane(c.lane), row = lane >> 4, rl = lane & 15;
     const bool rowon = (rowmask >> row) & 1;
     const int cap = c.cap;
     VLR_WAVE_FENCE();
@@ -2579,21 +2349,10 @@ __device__ __forceinline__ void run_chain_batch(Ctx& c, int rowmask, int inner) 
     const int D_in = UNI(w->nkeep[inner]);
     // register-resident runner: the integrated sample is the only one whose likelihood moves with the chain (no sample is
     // contaminated by it), its pileup fits the register slots and its terms need no renormalisation
-#ifdef VLR_DBG_NO_REGRUN  // diagnosis builds: every batch through the round-1 loop (coefficients from LDS, per-term renormalisation)
-    const bool regrun = false && dep == (1 << inner);
-#else
     const bool regrun = dep == (1 << inner) && D_in <= 16 * kRegSlots && ((UNI(w->vfast) >> inner) & 1);
-#endif
-    TRC(c, 30, lo); TRC(c, 31, hi); TRC(c, 32, res); TRC(c, 33, fixed); TRC(c, 34, simpson_n); TRC(c, 35, pidx); TRC(c, 36, rowon ? 1 : 0);
-    TRC(c, 37, regrun ? 1 : 0); TRC(c, 38, D_in); TRC(c, 39, pr0); TRC(c, 40, pr1);
     // keyed passes (see reg_chain_loop): every point of every row has the same finite prior value and a finite fixed part
-#ifdef VLR_DBG_NO_KEYED  // diagnosis builds: every pass takes the logarithm itself
-    const bool keyed = false && nlfc_of(c) == 0 &&
-#else
-    const bool keyed = regrun && nlfc_of(c) == 0 && !(ones_any(c) && ones_risk(c, inner)) &&
-#endif  // (the exponent of a direct all-ones product is not bounded by the key's 16 bits)
+    const bool keyed = regrun && nlfc_of(c) == 0 && !(ones_any(c) && ones_risk(c, inner)) &&  // (the exponent of a direct all-ones product is not bounded by the key's 16 bits)
                        __ballot(rowon && !(cls_fast && (pr0 == pr1 || lo != 0.0) && fabs(pr1) < __builtin_huge_val() && fabs(fixed) < __builtin_huge_val())) == 0ull;
-    TRC(c, 41, keyed ? 1 : 0); TRC(c, 42, cls_fast ? 1 : 0);
     if (__builtin_expect(regrun, 1)) {
         RegChain rc;
         rc.lo = lo; rc.hi = hi; rc.res = res; rc.fixed = fixed; rc.pr0 = pr0; rc.pr1 = pr1; rc.pr2 = pr2;
@@ -2841,7 +2600,6 @@ __device__ __forceinline__ void run_chain_batch(Ctx& c, int rowmask, int inner) 
             for (int t = 0; t < 4; ++t)
                 if (t < TT) vi[t] = (kk[t] != kKeyNone) ? (xi[t] == 0.0 ? pr0 : pr1) + (fixed + key_ln(kk[t])) : VLR_NEG_INF;
         }
-        TRC(c, 81, n); TRC(c, 82, nmax); TRC(c, 83, xi[0]); TRC(c, 84, vi[0]); TRC(c, 85, xi[1]); TRC(c, 86, vi[1]); TRC(c, 87, bJ); TRC(c, 88, bX);
         // AFD log: the four row tables as they stand (any order), one record per chain (no l2fc terms on batched chains)
         if (log_on(c)) {
             const int hsz = 1 + c.S;
@@ -2872,9 +2630,6 @@ __device__ __forceinline__ void run_chain_batch(Ctx& c, int rowmask, int inner) 
         // the range fail the check and the exact ranking takes over: one 64-bit compare and one add-with-carry per (entry, q) against
         // keys parked in the value table (x and value of every entry are in registers by now).
         if (__ballot(srt && n > 0)) {
-#ifdef VLR_NO_BITONIC
-            bool use32 = false;
-#else
             bool use32 = true;
             {
                 const double span = hi - lo;
@@ -2884,7 +2639,6 @@ __device__ __forceinline__ void run_chain_batch(Ctx& c, int rowmask, int inner) 
                 else if (nmax > 16) bitonic_ranks<1>(xi, n, rl, lo, scale, (unsigned char*)tv, rank);
                 else bitonic_ranks<0>(xi, n, rl, lo, scale, (unsigned char*)tv, rank);
             }
-#endif
             for (;;) {
                 if (__builtin_expect(!use32, 0)) {
                     // sort key: the bit pattern of a non-negative double orders like the number; the low six bits carry the table index.
@@ -3022,7 +2776,6 @@ __device__ __forceinline__ void run_chain_batch(Ctx& c, int rowmask, int inner) 
                 ssum += on ? ev * wgt : 0.0;
             }
         }
-        TRC(c, 89, rank[0]); TRC(c, 90, rank[1]); TRC(c, 91, M); TRC(c, 92, ssum);
         ssum = row_sum(ssum);
         {   // ln of the positive sum: exponent apart, the mantissa through the short logarithm of the passes (ssum == 0: -inf)
             int es;
@@ -3031,7 +2784,6 @@ __device__ __forceinline__ void run_chain_batch(Ctx& c, int rowmask, int inner) 
             rint_ = (M == VLR_NEG_INF) ? VLR_NEG_INF : M + lns;
         }
     }
-    TRC(c, 93, rint_); TRC(c, 94, bJ); TRC(c, 95, bX); TRC(c, 96, bHave);
     int nanrow = row_or(anynan ? 1 : 0);
     const int rowout = row_or(anyout ? 1 : 0);
     double r = rint_;
@@ -3155,7 +2907,7 @@ __device__ __forceinline__ bool bo_setup(Ctx& c, const Frame& f, RangeSt& r) {
     const DevPlan& p = *c.plan;
     WaveSt* w = c.w;
     const BatchOuter& B = w->bo;
-    const int lane = (((VLR_FRESH_MASK >> 6) & 1u) ? fresh_lane(c.lane) : (c.lane)), S = c.S;
+    const int lane = fresh_lane(c.lane), S = c.S;
     const int np = UNI(B.np), c0 = UNI(B.c0), s_in = UNI(B.s_in), s_out = UNI(B.s_out), chn = UNI(B.chn);
     const bool dead = UNI(B.dead) != 0;
     const int free_rows = kRows - c.nhold;  // held event-level chains keep the top rows (they ride along with this batch)
@@ -3211,11 +2963,7 @@ __device__ __forceinline__ bool bo_setup(Ctx& c, const Frame& f, RangeSt& r) {
             }
             VLR_SYNC();
         }
-#ifdef VLR_NO_RESCUE
-        if (lane < nt) w->task[lane].fixed += w->bpend[3][lane];
-#else
         if (lane < nt) w->task[lane].fixed += w->bpend[3][lane] + (double)kshift(c)[s] * kLn2;
-#endif
         if (lane == 0) { w->work[0] += (unsigned long long)nt; w->work[1] += (unsigned long long)nt * (unsigned long long)D; }
         VLR_SYNC();
     }
@@ -3228,7 +2976,7 @@ __device__ __forceinline__ bool bo_setup(Ctx& c, const Frame& f, RangeSt& r) {
 __device__ __forceinline__ bool bo_deliver(Ctx& c, const Frame& f, RangeSt& r, double* txo, double* tvo) {
     WaveSt* w = c.w;
     const BatchOuter& B = w->bo;
-    const int lane = (((VLR_FRESH_MASK >> 7) & 1u) ? fresh_lane(c.lane) : (c.lane));
+    const int lane = fresh_lane(c.lane);
     const int np = UNI(B.np), c0 = UNI(B.c0), nt = UNI(B.nt), s_in = UNI(B.s_in), s_out = UNI(B.s_out);
     const bool dead = UNI(B.dead) != 0;
     PROF_ADD(c, 24);  // walk: resume up to the delivery
@@ -3304,7 +3052,6 @@ __device__ __forceinline__ void flush_deliver(Ctx& c, int rowmask, double* evM, 
         c.group = UNI(T.group); c.disc = UNI(T.disc); c.contained = UNI(T.contained); c.alive = UNI_A(T.alive); if (kHasLfc) c.nlfc = 0;
         c.curJ = uni_d(c.mapJ[u]); c.curHyp = UNI(c.mapHyp[u]);
         const double dens = uni_d(T.result);
-        TRC(c, 100, dens); TRC(c, 101, u); TRC(c, 102, i);
         if (dens != dens) c.status |= VLR_LOCUS_NAN;
         const int nq = UNI(T.n);
         if (kHasReplay && __builtin_expect(c.replay != 0, 0)) afd_emit_row(c, i, s_in, nq);
@@ -3326,7 +3073,7 @@ __device__ __forceinline__ void flush_deliver(Ctx& c, int rowmask, double* evM, 
 // one chain task with its operands from row `from` (or the stash: from < 0) to row `to` (or the stash: to < 0)
 __device__ __forceinline__ void move_task(Ctx& c, int from, int to) {
     WaveSt* w = c.w;
-    const int lane = (((VLR_FRESH_MASK >> 8) & 1u) ? fresh_lane(c.lane) : (c.lane));
+    const int lane = fresh_lane(c.lane);
     constexpr int NW = (int)(sizeof(ChainTask) / 8);
     static_assert(sizeof(ChainTask) % 8 == 0, "ChainTask is copied in 8-byte words");
     const double* src = (const double*)(from < 0 ? &w->stash : &w->task[from]);
@@ -3349,7 +3096,7 @@ __device__ __forceinline__ void move_task(Ctx& c, int from, int to) {
 __device__ __forceinline__ int fast_chain_root(Ctx& c, const DevFastRoot* fr) {
     const DevPlan& p = *c.plan;
     WaveSt* w = c.w;
-    const int lane = (((VLR_FRESH_MASK >> 9) & 1u) ? fresh_lane(c.lane) : (c.lane)), S = c.S;
+    const int lane = fresh_lane(c.lane), S = c.S;
     const int n_fixed = ldc(&fr->n_fixed), inner = ldc(&fr->inner);
     // the fixed values, one per lane (lane k < n_fixed: node k of the path)
     const int kf = lane < n_fixed ? lane : 0;
@@ -3963,14 +3710,9 @@ __global__ void __launch_bounds__(64) vlr_afd_kernel(const DevPlan plan_arg, Dev
 // Two builds of the same kernel: WPE = 2 waves per SIMD (no spills) for workgroups whose LDS footprint allows only 8 of
 // them per CU anyway, WPE = 3 (168 VGPRs, 32 of them spilled) where 9 or more fit (single-sample 30x: 12 workgroups,
 // +33 %).  The launcher picks by LDS bytes.
-#ifdef VLR_DBG_NUM_VGPR  // diagnosis builds: a VGPR cap independent of the launch bounds (run at VLR_WAVES_PER_SIMD=2)
-#define VLR_DBG_VGPR_ATTR __attribute__((amdgpu_num_vgpr(VLR_DBG_NUM_VGPR)))
-#else
-#define VLR_DBG_VGPR_ATTR
-#endif
 constexpr int kGridQuantum = kXcds;   // the launchers round the grid up to a multiple of this (XCD-aware locus mapping below)
 template <int WPE>
-__global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(const DevPlan plan_arg, DevBatch batch, DevResults out,
+__global__ void __launch_bounds__(64, WPE) vlr_call_kernel(const DevPlan plan_arg, DevBatch batch, DevResults out,
                                                            int max_obs, int range_depth) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     __shared__ WaveSt wst;
@@ -3982,15 +3724,11 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
     // shared with the neighbours) meet in the same L2 at about the same time instead of being filled into two L2s.  Measured on
     // config 3 (profiles/r06g.md): L2 fills + write-backs 12.49 -> 10.00 GB per million loci (1.55 -> 1.24 x the algorithmic bytes) for
     // + 0.4 % kernel time; plans with more than two samples lose 1.6 - 2.8 % (configs 4, 5) and keep w -> w.  Tiled variants (8 to
-    // 1024 consecutive loci per XCD in turn) were slower than both.  VLR_NO_XCD_MAP: the A/B build.
+    // 1024 consecutive loci per XCD in turn) were slower than both.
     // (The grid is rounded up to a multiple of eight: kXcds * ceil(n / 8) ids cover 0 .. n - 1 exactly once.)
-#ifdef VLR_NO_XCD_MAP
-    const int64_t locus = blockIdx.x;
-#else
     const int64_t locus = (!kHasManySamples || plan_arg.S <= kXcdMapMaxSamples)
                               ? (int64_t)(blockIdx.x % kXcds) * ((batch.n_loci + kXcds - 1) / kXcds) + (int64_t)(blockIdx.x / kXcds)
                               : (int64_t)blockIdx.x;
-#endif
     if (locus >= batch.n_loci) return;   // (plans above kLdsSamples samples: the host launches the wide build)
     if (VLR_DEEP && !(out.status[locus] & VLR_LOCUS_TOO_DEEP)) return;  // deep launch: only what the LDS-resident kernel could not hold
     // deep replay: only what the deep call launch evaluated (the others keep their flag).  These loci held pool room in the call pass
@@ -4310,7 +4048,6 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
         }
     }
 
-    TRC(c, 1, total_kept); TRC(c, 2, n_alt_like); TRC(c, 3, forward_rate); TRC(c, 4, (int)surviving); TRC(c, 5, (int)enabled); TRC(c, 6, offset_acc);
     PROF_ADD(c, 1);  // gating
     // ============================ phase B: hypotheses x events ============================
     for (int u = lane; u < p.n_univ; u += 64) { evM[u] = VLR_NEG_INF; evS[u] = 0.0; }
@@ -4347,7 +4084,6 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
     for (int h = 0; h < kNHyp; ++h) {
         if (!((hyps >> h) & 1u)) continue;
         c.hyp = h;
-        TRC(c, 10, h);
         // ---- per-observation affine coefficients for this hypothesis -> LDS
         // L_i(alpha, beta) = c_i + q_i*alpha + e_i*beta with
         //   w = e^pm, u = (1-w) * e^(missed + b_any), A = e^(pa + b_alt), R = e^(pr + b_ref), s = e^prob_sample_alt
@@ -4429,8 +4165,6 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
                     double d = A - R;
                     cc_ = wv * R + uu; cq_ = wv * sv * d; ce_ = wv * (1.0 - sv) * d;
                     one_t = wv * A + uu; ref_t = wv * R;  // the term at alpha = beta = 1 formed directly, and what c + q + e cancels
-                    TRC(c, 130, sb_alt); TRC(c, 131, fa); TRC(c, 132, fr); TRC(c, 133, A); TRC(c, 134, R); TRC(c, 135, wv); TRC(c, 136, uu); TRC(c, 137, sv); TRC(c, 138, d); TRC(c, 139, cq_);
-                    TRC(c, 140, exp(pa)); TRC(c, 141, rp_any); TRC(c, 142, he_alt); TRC(c, 143, ro_alt); TRC(c, 144, forward_rate); TRC(c, 145, fresh_sd(reverse_rate)); TRC(c, 146, pa); TRC(c, 147, strand);
                     if (__builtin_expect(scaled != 0, 0)) {
                         // the three log-space addends of the observation's likelihood, their largest as the binary exponent k
                         const double lA = (fa > 0.0 && pa > VLR_NEG_INF) ? pm + pa + log(fa) : VLR_NEG_INF;
@@ -4545,8 +4279,6 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
             VLR_SYNC();
         }
 
-        TRC(c, 11, c.coef[2 * (lane < offset_acc ? lane : 0)]); TRC(c, 12, c.coef[2 * (lane < offset_acc ? lane : 0) + 1]);
-        TRC(c, 13, w->fastok); TRC(c, 14, w->vfast); TRC(c, 15, c.ehas); TRC(c, 16, kshift(c)[lane < S ? lane : 0]);
         PROF_ADD(c, 2);  // coefficient pass
         // ---- events (calling.rs:654-687): absent + clean events under h = none, artifact twins otherwise
         const double bias_prior = (h == 0) ? kLn05 : ln_bias_share;  // modes/generic.rs:437-441
@@ -4628,11 +4360,7 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
                     c.defer_slot = u;
                     const DevFastRoot* fr = p.froot + ((e < 0) ? 0 : 1 + ri);
                     const bool is_droot = !((kHasReplay && c.replay) || p.n_dkey == 0) && ldc(p.droot + 2 * ((e < 0) ? 0 : 1 + ri)) >= 0;  // all-discrete roots: below
-#ifdef VLR_NO_FAST_CODE
-                    const int fkind = 0;
-#else
                     const int fkind = (c.defer_ok && !is_droot) ? ldc(&fr->kind) : 0;
-#endif
                     if (fkind != 0) {  // compiled chain root: the task straight from the plan's record; 2: certainly a root for the general pass
                         const int fk = fkind == 1 ? fast_chain_root(c, fr) : 2;
                         if (fk == 2) todo |= 1ull << rc_;
@@ -4664,7 +4392,6 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
                 }
                 if (st == IT_WALK) {
                     const double dens = uni_d(walk_root(c, root, resume));
-                    TRC(c, 24, dens); TRC(c, 25, u); TRC(c, 26, c.need_batch); TRC(c, 27, c.deferred);
                     PROF_ADD(c, 21);  // walk (descent, frames; the outer-batch steps are counted apart)
                     if (c.need_batch) {
                         c.need_batch = 0; run_kind = 1; run_mask = (1 << c.bt_nt) - 1; run_inner = c.bt_inner;
@@ -4692,7 +4419,6 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
                 if (run_kind) {
                     PROF_ADD(c, 31);  // event loop: between the walk's return and the batch
                     if (run_kind != 1) if (kHasLfc) c.nlfc = 0;  // deferred chains carry no l2fc terms; a later probe walk may have left some in the context
-                    TRC(c, 20, run_mask); TRC(c, 21, run_inner); TRC(c, 22, run_kind); TRC(c, 23, piggy);
                     run_chain_batch(c, run_mask, run_inner);
                     VLR_SYNC();
                     if (run_kind == 1) {
@@ -4746,7 +4472,6 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
     const int u_l = lane < p.n_univ ? lane : 0;
     const double evM_l = evM[u_l];
     const double evV_l = lse_value(evM_l, evS[u_l]);
-    TRC(c, 110, evM_l); TRC(c, 111, evV_l); TRC(c, 112, evS[u_l]);
 #define EV_M(u) lane_d(evM_l, u)
 #define EV_V(u) lane_d(evV_l, u)
 #endif
@@ -4757,7 +4482,6 @@ __global__ void __launch_bounds__(64, WPE) VLR_DBG_VGPR_ATTR vlr_call_kernel(con
         lse_add(mM, mS, v);
     }
     double marginal = (mM != mM) ? mM : lse_value(mM, mS);
-    TRC(c, 113, marginal);
     if (marginal != marginal) c.status |= VLR_LOCUS_NAN;
     // call_record (calling.rs:762-803)
     int best = 0;
@@ -4912,43 +4636,6 @@ __global__ void __launch_bounds__(64) vlr_selftest_stream_kernel(const float* in
 #define VLR_FN_CALL vlr_launch_call_kernel
 #define VLR_FN_AFD vlr_launch_afd_kernel
 #define VLR_FN_LDS vlr_plan_lds_floor
-#endif
-#ifdef VLR_DBG_OWNER  // host side of the diagnosis builds (VLR_DBG_EXEC_ASSERT / VLR_DBG_TRACE above); not in a shipped library
-#ifdef VLR_DBG_EXEC_ASSERT
-// out[4 * line + {0: executed, 1: executions under partial EXEC, 2: executions breaking the site's rule, 3: OR of disabled lanes}]
-extern "C" int vlr_debug_exec_sites(unsigned long long* out, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return 1;
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(vlr::g_xsite), sizeof(unsigned long long) * vlr::kXSites * 4) != hipSuccess) return 2;
-    if (reset) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(vlr::g_xsite)) != hipSuccess) return 3;
-        if (hipMemset(p, 0, sizeof(unsigned long long) * vlr::kXSites * 4) != hipSuccess) return 4;
-    }
-    return 0;
-}
-#endif
-#ifdef VLR_DBG_TRACE
-extern "C" int vlr_debug_trace_arm(long long locus) {   // trace the wave of this locus of the following launches; -1: none
-    if (hipDeviceSynchronize() != hipSuccess) return 1;
-    const int zero = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(vlr::g_trace_n), &zero, sizeof(int)) != hipSuccess) return 2;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(vlr::g_trace_locus), &locus, sizeof(long long)) != hipSuccess) return 3;
-    return 0;
-}
-// records written since vlr_debug_trace_arm (at most cap): hdr[2 r] = (id << 32) | source line, hdr[2 r + 1] = EXEC, val[64 r + lane]
-extern "C" long long vlr_debug_trace_read(unsigned long long* hdr, double* val, long long cap) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    int n = 0;
-    if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(vlr::g_trace_n), sizeof(int)) != hipSuccess) return -2;
-    long long k = n < vlr::kTraceCap ? n : vlr::kTraceCap;
-    if (k > cap) k = cap;
-    if (k > 0) {
-        if (hipMemcpyFromSymbol(hdr, HIP_SYMBOL(vlr::g_trace_hdr), sizeof(unsigned long long) * 2 * (size_t)k) != hipSuccess) return -3;
-        if (hipMemcpyFromSymbol(val, HIP_SYMBOL(vlr::g_trace_val), sizeof(double) * 64 * (size_t)k) != hipSuccess) return -4;
-    }
-    return (long long)n;
-}
-#endif
 #endif
 #if !VLR_DEEP && !defined(VLR_WIDE_BUILD) && !VLR_LEAN
 extern "C" int vlr_launch_selftest_stream(const float* in, double* out, long long n, int mode, void* stream) {

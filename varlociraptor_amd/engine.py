@@ -33,6 +33,13 @@ EXPORTS = [
 ]
 
 
+# What libvlr.so is built from, relative to this package, in the order of csrc/Makefile's SRC and headers (source_id hashes them in it)
+SOURCES = tuple("csrc/" + f for f in (
+    "vlr_kernels.hip", "vlr_kernels_lean.hip", "vlr_kernels_deep.hip", "vlr_kernels_wide.hip", "vlr_kernels_widedeep.hip", "vlr_realign.hip",
+    "vlr_fdr.hip", "vlr_contam.hip", "vlr_callstats.hip", "vlr_bamstats.hip", "vlr_inflate.hip", "vlr_decode.hip", "vlr_host.cpp", "vlr_ingest.cpp",
+    "vlr_plan.h", "vlr_gpuio.h", "vlr_callstats.h")) + ("../include/vlr.h", "../include/vlr_detmath.h")
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("vlr error %d: %s" % (code, msg))
@@ -42,7 +49,7 @@ class EngineError(RuntimeError):
 def build(force: bool = False) -> str:
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
-    srcs = [os.path.join(src_dir, f) for f in ("vlr_kernels.hip", "vlr_kernels_lean.hip", "vlr_kernels_deep.hip", "vlr_kernels_wide.hip", "vlr_kernels_widedeep.hip", "vlr_realign.hip", "vlr_fdr.hip", "vlr_contam.hip", "vlr_callstats.hip", "vlr_bamstats.hip", "vlr_inflate.hip", "vlr_decode.hip", "vlr_host.cpp", "vlr_ingest.cpp", "vlr_plan.h", "vlr_gpuio.h", "vlr_callstats.h")] + [os.path.join(_HERE, "..", "include", "vlr.h")]
+    srcs = [os.path.join(_HERE, f) for f in SOURCES]
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", src_dir] + (["-B"] if force else []), stdout=subprocess.DEVNULL)
     return LIB_PATH
@@ -57,7 +64,7 @@ def source_id() -> str:
     """The id a build of the current sources would carry (same recipe as csrc/Makefile)."""
     import hashlib
     h = hashlib.sha1()
-    for f in ("csrc/vlr_kernels.hip", "csrc/vlr_kernels_lean.hip", "csrc/vlr_kernels_deep.hip", "csrc/vlr_kernels_wide.hip", "csrc/vlr_kernels_widedeep.hip", "csrc/vlr_realign.hip", "csrc/vlr_fdr.hip", "csrc/vlr_contam.hip", "csrc/vlr_callstats.hip", "csrc/vlr_bamstats.hip", "csrc/vlr_inflate.hip", "csrc/vlr_decode.hip", "csrc/vlr_host.cpp", "csrc/vlr_ingest.cpp", "csrc/vlr_plan.h", "csrc/vlr_gpuio.h", "csrc/vlr_callstats.h", "../include/vlr.h", "../include/vlr_detmath.h"):
+    for f in SOURCES:
         with open(os.path.join(_HERE, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
