@@ -34,14 +34,15 @@
 extern "C" {
 #endif
 
-#define VLR_ABI_VERSION 9   /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
+#define VLR_ABI_VERSION 10  /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
                              * 5: sharded device reader, calls-file parts, vlr_ingest_device_trim, CRC32 of BGZF members checked by both readers;
                              * 6: calls emission on the device — vlr_results.afd_text (FORMAT/AFD text), OBS text in the observation summaries,
                              *    vlr_obs_table_summaries;
                              * 7: vlr_contamination_posterior (`estimate contamination`);
                              * 8: vlr_bamstats_* (`estimate alignment-properties`);
                              * 9: vlr_posterior_odds_keep, vlr_range_group_lse, vlr_calls_filter_odds, vlr_calls_mutational_burden
-                             *    (`filter-calls posterior-odds`, `estimate mutational-burden`) */
+                             *    (`filter-calls posterior-odds`, `estimate mutational-burden`);
+                             * 10: vlr_basepileup_* (SNV / MNV allele supports from BAM records) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -513,6 +514,72 @@ int  vlr_bamstats_add_bam(vlr_bamstats* s, const char* bam_path);
 int  vlr_bamstats_result(vlr_bamstats* s, vlr_bamstats_counts* out);
 int  vlr_bamstats_read(vlr_bamstats* s, uint64_t* hop_keys, uint64_t* hop_counts, int64_t n_hop, int64_t* insert_sizes, int64_t n_insert);
 void vlr_bamstats_close(vlr_bamstats* s);
+
+/* ------------------------------------------------------------------------------------------------
+ * SNV / MNV allele supports from BAM records: the no-realignment branch of Snv::allele_support_per_read (variants/types/snv.rs:66-150)
+ * and Mnv::allele_support_per_read (variants/types/mnv.rs:73-205) for every (record, locus) pair of a BAM file, restated in
+ * varlociraptor_amd/basecalls.py.  The file goes through the device reader exactly as for vlr_bamstats_add_bam (BGZF members inflated on
+ * the device, BAM records split there); one thread per record decodes the fixed head, drops unmapped / secondary / duplicate / QC-fail
+ * records (variants/sample.rs:281-286; supplementary ones stay), finds the loci the alignment encloses (SingleLocus::overlap without
+ * clips == Enclosing, variants/types/mod.rs:440-473) and scores each from the read's own bases (variants/evidence/bases.rs).
+ * Loci: n_loci candidates sorted by (ref_id, start) — ref_id = index of the contig in the BAM header —, len = number of bases (1 for
+ *   VLR_BASEPILEUP_SNV, 2 .. VLR_BASEPILEUP_MAX_LEN for VLR_BASEPILEUP_MNV; longer MNVs are refused here and scored by the caller with
+ *   the restatement), ref_bases / alt_bases: the upper-case alleles one behind the other in locus order (sum of len bytes each).
+ * realign_indel_reads != 0: a record with an I or D operation is not scored for the loci it encloses; it comes back as a hit with
+ *   VLR_BASEPILEUP_HIT_NEEDS_REALIGN and no probabilities (realigning against SNV / MNV emission parameters is not part of this path).
+ * hit_capacity: hits the session's device buffer holds.  More hits than that: nothing is written past the buffer, the status word
+ *   carries VLR_BASEPILEUP_OVERFLOW and needed_capacity the exact count — open again with that capacity.
+ * window_bytes: inflated bytes per split (0: 64 MiB; any value >= 1 is legal: a feed holds at least one BGZF member, and a record
+ *   longer than the window grows it).  The hits do not depend on it, bit for bit.
+ * vlr_basepileup_result: the counts, the status word (VLR_BASEPILEUP_BAD_RECORD: a record whose lengths overrun its block_size, whose
+ *   aux fields are malformed, whose CIGAR has an unknown operation or consumes more bases than l_seq, or a file that ends inside a
+ *   record — such a record gives no hits and is never followed; the records in front of it are scored), seconds: [0] file read,
+ *   [1] upload + inflate, [2] record split, [3] count + scan + fill kernels, [4] hits to the host and the locus-major order, [5] total,
+ *   [6] inflate kernels alone.
+ * vlr_basepileup_read copies the n_hits hits (n = n_hits of the result): locus-major, in record order within a locus; `record` counts
+ *   the records of all files given to the session so far, in file order.  Bit-identical from run to run and for every window_bytes.
+ * vlr_basepileup_tables: the tables the kernel scores with — call[q] = ln(1 - 10^(-q/10)) (LogProb::ln_one_minus_exp of the miscall
+ *   probability), miscall[q] = -q ln(10) / 10 — so that a restatement run on them must agree bit for bit. */
+#define VLR_BASEPILEUP_MAX_LEN 32
+enum { VLR_BASEPILEUP_SNV = 0, VLR_BASEPILEUP_MNV = 1 };
+/* status word of a session */
+#define VLR_BASEPILEUP_BAD_RECORD (1u << 0)
+#define VLR_BASEPILEUP_OVERFLOW   (1u << 1)
+#define VLR_BASEPILEUP_GUARD_DAMAGED (1u << 2)  /* the guard words behind the hit buffer changed: a defect of the fill pass, never expected */
+/* status byte of a hit */
+#define VLR_BASEPILEUP_HIT_NEEDS_REALIGN           (1u << 0)
+#define VLR_BASEPILEUP_HIT_READ_POS_OUT_OF_BOUNDS  (1u << 1)  /* SI:Z shorter than the read position (Error::ReadPosOutOfBounds)          */
+#define VLR_BASEPILEUP_HIT_INVALID_STRAND_INFO     (1u << 2)  /* SI:Z character outside "+-*." (Error::InvalidStrandInfo)                */
+#define VLR_BASEPILEUP_HIT_LEADING_REFSKIP         (1u << 3)  /* read_pos fails on a CIGAR that begins with N (rust-htslib)              */
+#define VLR_BASEPILEUP_NO_READ_POSITION 0xffffffffu
+typedef struct {
+    double   prob_ref, prob_alt;   /* ln P(read | ref allele), ln P(read | alt allele)                                                 */
+    uint64_t record;               /* ordinal of the record                                                                            */
+    uint32_t locus;                /* index of the locus in the arrays given at open                                                   */
+    uint32_t read_position;        /* position in the read, leading hard clips included; VLR_BASEPILEUP_NO_READ_POSITION               */
+    uint32_t third_allele;         /* third-allele evidence (edit distance); 0 = none                                                  */
+    uint16_t flag;                 /* the record's FLAG & (0x1 paired | 0x10 reverse | 0x40 first in template)                         */
+    uint8_t  strand;               /* 0 forward, 1 reverse, 2 both, 3 none (the VLR_F_STRAND values)                                   */
+    uint8_t  mapq;
+    uint8_t  status;               /* VLR_BASEPILEUP_HIT_*                                                                             */
+    uint8_t  pad[7];
+} vlr_basepileup_hit;
+typedef struct vlr_basepileup vlr_basepileup;
+typedef struct {
+    int64_t  n_hits, n_records, n_rejected, n_needs_realign;
+    uint64_t status;               /* VLR_BASEPILEUP_BAD_RECORD | VLR_BASEPILEUP_OVERFLOW | VLR_BASEPILEUP_GUARD_DAMAGED               */
+    int64_t  needed_capacity;      /* hits the input produces (== n_hits unless VLR_BASEPILEUP_OVERFLOW)                               */
+    int64_t  first_bad_record;     /* ordinal of the first bad record, -1 = none                                                       */
+    double   seconds[8];
+} vlr_basepileup_counts;
+int  vlr_basepileup_open(int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int32_t* len, const uint8_t* kind,
+                         const uint8_t* ref_bases, const uint8_t* alt_bases, int realign_indel_reads, int64_t hit_capacity, int64_t window_bytes,
+                         vlr_basepileup** out);
+int  vlr_basepileup_add_bam(vlr_basepileup* s, const char* bam_path);
+int  vlr_basepileup_result(vlr_basepileup* s, vlr_basepileup_counts* out);
+int  vlr_basepileup_read(vlr_basepileup* s, vlr_basepileup_hit* hits, int64_t n);
+int  vlr_basepileup_tables(double call[256], double miscall[256]);
+void vlr_basepileup_close(vlr_basepileup* s);
 
 /* The whole of `varlociraptor filter-calls control-fdr` (/root/reference/src/filtration/fdr.rs:36-158, record typing
  * src/utils/collect_variants.rs:44-304, probability sums and the filtering pass src/utils/mod.rs:169-374): read the calls BCF

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_SAMPLES = 16
 N_BIAS = 6
 
@@ -147,3 +147,29 @@ class BamStatsResult(C.Structure):
                 ("max_del", C.c_int64), ("max_ins", C.c_int64), ("max_read_len", C.c_int64), ("max_mapq", C.c_int64),
                 ("frac_max_softclip", C.c_double), ("has_softclip", C.c_int64),
                 ("n_hop_keys", C.c_int64), ("n_insert_sizes", C.c_int64), ("seconds", C.c_double * 10)]
+
+
+# vlr_basepileup_* (SNV / MNV allele supports from BAM records, ABI 10)
+BASEPILEUP_MAX_LEN = 32
+BASEPILEUP_SNV, BASEPILEUP_MNV = 0, 1
+BASEPILEUP_BAD_RECORD, BASEPILEUP_OVERFLOW, BASEPILEUP_GUARD_DAMAGED = 1, 2, 4
+BASEPILEUP_HIT_NEEDS_REALIGN, BASEPILEUP_HIT_READ_POS_OUT_OF_BOUNDS, BASEPILEUP_HIT_INVALID_STRAND_INFO, BASEPILEUP_HIT_LEADING_REFSKIP = 1, 2, 4, 8
+BASEPILEUP_NO_READ_POSITION = 0xFFFFFFFF
+
+
+class BasePileupHit(C.Structure):
+    """vlr_basepileup_hit"""
+    _fields_ = [("prob_ref", C.c_double), ("prob_alt", C.c_double), ("record", C.c_uint64), ("locus", C.c_uint32),
+                ("read_position", C.c_uint32), ("third_allele", C.c_uint32), ("flag", C.c_uint16), ("strand", C.c_uint8),
+                ("mapq", C.c_uint8), ("status", C.c_uint8), ("pad", C.c_uint8 * 7)]
+
+
+BASEPILEUP_HIT_DTYPE = np.dtype([("prob_ref", "<f8"), ("prob_alt", "<f8"), ("record", "<u8"), ("locus", "<u4"), ("read_position", "<u4"),
+                                 ("third_allele", "<u4"), ("flag", "<u2"), ("strand", "u1"), ("mapq", "u1"), ("status", "u1"), ("pad", "u1", (7,))])
+assert C.sizeof(BasePileupHit) == 48 and BASEPILEUP_HIT_DTYPE.itemsize == 48
+
+
+class BasePileupCounts(C.Structure):
+    """vlr_basepileup_counts"""
+    _fields_ = [("n_hits", C.c_int64), ("n_records", C.c_int64), ("n_rejected", C.c_int64), ("n_needs_realign", C.c_int64),
+                ("status", C.c_uint64), ("needed_capacity", C.c_int64), ("first_bad_record", C.c_int64), ("seconds", C.c_double * 8)]

@@ -895,8 +895,8 @@ def aux_field(tag: str, typ: str, value) -> bytes:
 
 
 def encode_record(tid: int, pos: int, mapq: int, flag: int, cigar: Sequence[Tuple[str, int]], seq: str, mtid: int = -1, mpos: int = -1,
-                  tlen: int = 0, aux: bytes = b"", name: str = "r") -> bytes:
-    """One BAM record (block_size included); cigar as (op letter, length)."""
+                  tlen: int = 0, aux: bytes = b"", name: str = "r", qual: Optional[bytes] = None) -> bytes:
+    """One BAM record (block_size included); cigar as (op letter, length); qual: one byte per base (default: 0x1e throughout)."""
     rn = name.encode() + b"\0"
     cig = b"".join(struct.pack("<I", (l << 4) | CIGAR_OPS.index(op)) for op, l in cigar)
     rlen = sum(l for op, l in cigar if op in "MDN=X")
@@ -904,7 +904,8 @@ def encode_record(tid: int, pos: int, mapq: int, flag: int, cigar: Sequence[Tupl
     packed = bytearray((len(codes) + 1) // 2)
     for i, v in enumerate(codes):
         packed[i >> 1] |= v << (4 if (i & 1) == 0 else 0)
-    qual = b"\x1e" * len(seq)
+    qual = b"\x1e" * len(seq) if qual is None else bytes(qual)
+    assert len(qual) == len(seq)
     body = struct.pack("<iiBBHHHiiii", tid, pos, len(rn), mapq, reg2bin(pos, pos + max(rlen, 1)), len(cigar), flag, len(seq),
                        mtid, mpos, tlen) + rn + cig + bytes(packed) + qual + aux
     return struct.pack("<I", len(body)) + body

@@ -37,6 +37,7 @@
 
 #include "../../include/vlr.h"
 #include "vlr_gpuio.h"
+#include "vlr_bamstream.h"
 
 extern "C" void vlr_set_error(const char* msg);  // vlr_host.cpp: the text behind vlr_last_error()
 
@@ -604,13 +605,18 @@ int run_chunk(vlr_bamstats* s, vlr_dev_file* df, int64_t n, uint64_t rec0, const
     return VLR_OK;
 }
 
-int add_bam(vlr_bamstats* s, const char* path) {
+// One BAM file through the device reader: the BGZF member index from the file read in bounded pieces, the feeds up to the window, the
+// header skipped, the record split, and per split the caller's chunk pass (vlr_bamstream.h)
+int stream_bam(const BamStream& b, const char* path) {
     const double t_all = now_s();
+    double sink = 0.0;
+    auto T = [&](double* p) -> double& { return p ? *p : sink; };
+    size_t& window = *b.window;
     FILE* f = fopen(path, "rb");
     if (!f) return bfail(VLR_ERR_INVALID_ARGUMENT, "cannot open %s", path);
     struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
     vlr_dev_file* df = nullptr;
-    int rc = vlr_dev_file_create(s->device, &df);
+    int rc = vlr_dev_file_create(b.device, &df);
     if (rc != VLR_OK) return rc;
     struct Destroyer { vlr_dev_file* d; ~Destroyer() { vlr_dev_file_destroy(d); } } destroyer{df};
     hipStream_t st = (hipStream_t)vlr_dev_file_stream(df);
@@ -632,7 +638,7 @@ int add_bam(vlr_bamstats* s, const char* path) {
         const size_t got = fread(buf.data() + have, 1, kReadPiece, f);
         have += got;
         if (got < kReadPiece) eof = true;
-        s->t[0] += now_s() - t0;
+        T(b.t_read) += now_s() - t0;
         return VLR_OK;
     };
     auto parse_header = [&]() -> int {   // from `head` (host-inflated); sets head_need and names when complete
@@ -660,9 +666,9 @@ int add_bam(vlr_bamstats* s, const char* path) {
     };
     size_t fed_members_bytes = 0;      // compressed bytes consumed from buf by feeds
     while (true) {
-        if (s->n_taken >= (uint64_t)s->cap) break;
+        if (b.done && b.done()) break;
         // feed up to the window
-        while (vlr_dev_file_buffered(df) < s->window + (header_skipped ? 0 : head_need)) {
+        while (vlr_dev_file_buffered(df) < window + (header_skipped ? 0 : head_need)) {
             members.clear();
             size_t used = 0;
             if (!index_members(buf.data() + fed_members_bytes, have - fed_members_bytes, members, &used))
@@ -682,7 +688,7 @@ int add_bam(vlr_bamstats* s, const char* path) {
             ib.clear();
             uint64_t add = 0;
             size_t k = 0;
-            const uint64_t goal = s->window + (header_skipped ? 0 : (head_need ? head_need : s->window));
+            const uint64_t goal = window + (header_skipped ? 0 : (head_need ? head_need : window));
             for (; k < members.size() && (k == 0 || vlr_dev_file_buffered(df) + add < goal) && k < (1u << 16); ++k) {
                 vlr::InflateBlock x;
                 x.src = members[k].off - members[0].off; x.dst = add; x.clen = (uint32_t)members[k].clen; x.isize = members[k].isize; x.crc = members[k].crc; x.pad = 0;
@@ -708,7 +714,7 @@ int add_bam(vlr_bamstats* s, const char* path) {
             t0 = now_s();
             rc = vlr_dev_file_feed(df, mb + members[0].off, comp_bytes, ib.data(), (int)ib.size(), add);
             if (rc == VLR_OK) rc = vlr_dev_file_feed_wait(df);   // (the compressed bytes stay valid until here)
-            s->t[1] += now_s() - t0;
+            T(b.t_feed) += now_s() - t0;
             if (rc != VLR_OK) return rc;
             // everything in front of the end of member k - 1 is consumed (the member headers in between included)
             const size_t consumed_to = fed_members_bytes + (members[k - 1].off + members[k - 1].clen + 8);
@@ -716,14 +722,7 @@ int add_bam(vlr_bamstats* s, const char* path) {
             if (!header_skipped && head_need && vlr_dev_file_buffered(df) >= head_need) {
                 if ((rc = vlr_dev_file_skip(df, head_need)) != VLR_OK) return rc;
                 header_skipped = true;
-                size_t uc = s->used_cap;
-                if ((rc = grow(s->d_used, uc, names.size() + 1)) != VLR_OK) return rc;
-                s->used_cap = uc;
-                if (names.size() + 1 > s->ctg_cap) {
-                    size_t c1 = s->ctg_cap, c2 = s->ctg_cap;
-                    if ((rc = grow(s->d_ctg, c1, names.size() + 1)) || (rc = grow(s->d_ctg_len, c2, names.size() + 1))) return rc;
-                    s->ctg_cap = c1;
-                }
+                if (b.on_header && (rc = b.on_header(names)) != VLR_OK) return rc;
             }
         }
         if (!header_skipped) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: truncated BAM header", path);
@@ -734,22 +733,50 @@ int add_bam(vlr_bamstats* s, const char* path) {
         if (buffered == 0) break;
         // (at most kSplitRecords per split: the reader's record arrays are sized by it)
         rc = vlr_dev_file_split_bam(df, (int64_t)std::min<uint64_t>(buffered / 36 + 1, kSplitRecords), (int)names.size(), &n, &serial);
-        s->t[2] += now_s() - t0;
+        T(b.t_split) += now_s() - t0;
         if (rc != VLR_OK) return rc;
-        s->t[9] += serial;
+        T(b.n_serial) += serial;
         if (n == 0) {
             const bool more = !eof || fed_members_bytes < have;
-            if (!more) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: record %llu: truncated (the file ends inside it)", path, (unsigned long long)rec0);
-            s->window = std::max<size_t>(s->window, (size_t)buffered * 2);   // a record longer than the window: grow it for this record
+            if (!more) {
+                if (b.on_truncated) { rc = b.on_truncated(rec0); break; }
+                return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: record %llu: truncated (the file ends inside it)", path, (unsigned long long)rec0);
+            }
+            window = std::max<size_t>(window, (size_t)buffered * 2);   // a record longer than the window: grow it for this record
             continue;
         }
-        if ((rc = run_chunk(s, df, n, rec0, names, path, st)) != VLR_OK) return rc;
+        if ((rc = b.on_chunk(df, n, rec0, names, path, (void*)st)) != VLR_OK) return rc;
         if ((rc = vlr_dev_file_consume(df, n)) != VLR_OK) return rc;
         rec0 += (uint64_t)n;
     }
-    s->t[8] += vlr_dev_file_inflate_seconds(df, 1);
-    s->t[7] += now_s() - t_all;
-    return VLR_OK;
+    T(b.t_inflate) += vlr_dev_file_inflate_seconds(df, 1);
+    T(b.t_total) += now_s() - t_all;
+    return rc;
+}
+
+// the statistics pass over one BAM file
+int add_bam(vlr_bamstats* s, const char* path) {
+    BamStream b;
+    b.device = s->device;
+    b.window = &s->window;
+    b.t_read = &s->t[0]; b.t_feed = &s->t[1]; b.t_split = &s->t[2]; b.t_inflate = &s->t[8]; b.t_total = &s->t[7]; b.n_serial = &s->t[9];
+    b.done = [s]() { return s->n_taken >= (uint64_t)s->cap; };
+    b.on_header = [s](const std::vector<std::string>& names) -> int {
+        int rc;
+        size_t uc = s->used_cap;
+        if ((rc = grow(s->d_used, uc, names.size() + 1)) != VLR_OK) return rc;
+        s->used_cap = uc;
+        if (names.size() + 1 > s->ctg_cap) {
+            size_t c1 = s->ctg_cap, c2 = s->ctg_cap;
+            if ((rc = grow(s->d_ctg, c1, names.size() + 1)) || (rc = grow(s->d_ctg_len, c2, names.size() + 1))) return rc;
+            s->ctg_cap = c1;
+        }
+        return VLR_OK;
+    };
+    b.on_chunk = [s](vlr_dev_file* df, int64_t n, uint64_t rec0, const std::vector<std::string>& names, const char* path, void* st) {
+        return run_chunk(s, df, n, rec0, names, path, (hipStream_t)st);
+    };
+    return stream_bam(b, path);
 }
 
 }  // namespace vlr_bam

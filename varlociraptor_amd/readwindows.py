@@ -17,9 +17,9 @@ per-read supports that come out of the edit-distance and pair-HMM kernels (`real
   Realigner::allele_support (single locus)    realignment/mod.rs:161-424: edit-distance hit -> banded pair HMM -> normalisation
 
 NOT mirrored (callers must know): fragments — a read pair is two single-end observations here, without the insert-size support of
-deletion.rs:232-258 —, alternative variants at the locus, the read-inferred third allele (mod.rs:311-349), `prob_sample_alt`,
-SNVs / MNVs (scored base by base in the reference, no realignment).  A minimal BAM / FASTA reader is included (BGZF members are gzip
-members): the reference reads through htslib.
+deletion.rs:232-258 —, alternative variants at the locus, the read-inferred third allele (mod.rs:311-349), `prob_sample_alt`.
+SNVs / MNVs are scored base by base in the reference, without realignment: that path is varlociraptor_amd/basecalls.py.  A minimal
+BAM / FASTA reader is included (BGZF members are gzip members): the reference reads through htslib.
 """
 from __future__ import annotations
 
@@ -47,6 +47,7 @@ class BamRecord:
     mate_ref_id: int
     mate_pos: int
     tlen: int
+    aux: bytes = b""  # the raw aux fields behind the qualities
 
     @property
     def reverse(self) -> bool:
@@ -95,7 +96,7 @@ def read_bam(path: str) -> Tuple[List[Tuple[str, int]], List[BamRecord]]:
             seq[i] = ord(SEQ_CODE[(b >> 4) if (i & 1) == 0 else (b & 0xf)])
         p += (l_seq + 1) // 2
         qual = d[p:p + l_seq]
-        recs.append(BamRecord(qname, flag, ref_id, pos, mapq, cigar, bytes(seq), bytes(qual), mate_ref, mate_pos, tlen))
+        recs.append(BamRecord(qname, flag, ref_id, pos, mapq, cigar, bytes(seq), bytes(qual), mate_ref, mate_pos, tlen, bytes(d[p + l_seq:o + 4 + block_size])))
         o += 4 + block_size
     return contigs, recs
 
