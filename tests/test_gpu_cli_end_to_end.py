@@ -184,6 +184,22 @@ def test_cli_breakend_event_that_straddles_reader_chunks(golden_dir, tmp_path, m
             assert np.array_equal(got.map_vaf[l], plain.map_vaf[want], equal_nan=True), l
 
 
+def test_cli_timings_keys_of_the_native_and_the_python_path(golden_dir, tmp_path, monkeypatch):
+    """The `timings` dict is what bench.py reads: each path fills exactly its own set of keys."""
+    d = os.path.join(golden_dir, "flamegraph_profiling")
+    sc = cli.scenario_from_yaml(os.path.join(d, "scenario.yaml"))
+    obs = {"normal": os.path.join(d, "normal.bcf")}
+    monkeypatch.setenv("VLR_CLI_CHUNK", "4")   # 11 records: 4 + 4 + 3
+    native, python = {}, {}
+    cli.call_variants(sc, obs, omit_mask=abi.BIAS_ALL, output=str(tmp_path / "native.bcf"), timings=native)
+    assert set(native) == {"read_s", "call_s", "write_s", "n_loci", "n_obs", "setup_s", "drain_writer_s", "drain_reader_close_s",
+                           "drain_plans_close_s", "wall_s", "chunks", "drain_s"}
+    assert native["chunks"] == 3 and native["n_loci"] == 11
+    cli.call_variants(sc, obs, omit_mask=abi.BIAS_ALL, output=str(tmp_path / "python.bcf"), ingest="python", timings=python)
+    assert set(python) == {"read_s", "call_s", "write_s", "n_loci", "n_obs", "wall_s", "chunks"}
+    assert python["chunks"] == 1 and python["n_loci"] == 11 and python["n_obs"] == native["n_obs"]
+
+
 def test_cli_call_processor_and_candidate_filter_plug_points(tmp_path, monkeypatch):
     """calling.rs:964-1020: the driver's two plug points, as `estimate contamination` uses them (contamination.rs:371-428): a
     candidate filter that keeps SNVs with a clean contaminant pileup and strong alt evidence in the sample, and a processor that

@@ -2,7 +2,7 @@
 
 How much a "sample" is contaminated by a "contaminant", from the allele-frequency distributions (FORMAT/AFD lists) of the
 de-novo SNVs of the sample: `call_variants` runs the command's embedded scenario with the two plug points
-(`cli.ContaminationCandidateFilter`, and `ContaminationEstimator` below as the call processor), the estimator keeps the calls
+(`calldriver.ContaminationCandidateFilter`, and `ContaminationEstimator` below as the call processor), the estimator keeps the calls
 with P(denovo) >= 0.95 and evaluates the posterior of 4 x 101 events (maximum somatic VAF x contamination).  The grid — one
 interpolated density per kept observation and event — runs as HIP (`vlr_contamination_posterior`, csrc/vlr_contam.hip;
 `device=k`); `device="cpu"` is the float64 numpy restatement of contamination.rs:84-224 that the CPU suite uses and the GPU
@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import cli
+from . import calldriver
 
 N_C = 101                              # contaminations: linspace(0.0, 1.0, 101)
 MAX_SOMATIC_VAFS = (0.25, 0.5, 0.75, 1.0)
@@ -268,7 +268,7 @@ def posterior_grid_device(list_offset, list_vaf, list_lnprob, map_vaf, ln_prob_d
 
 
 # ---------------------------------------------------------------------------------------------------- the call processor
-class ContaminationEstimator(cli.CallProcessor):
+class ContaminationEstimator(calldriver.CallProcessor):
     """ContaminationEstimator (contamination.rs:260-399): keeps, per call, the sample's AFD list (sorted by VAF, CSR), its MAP VAF,
     ln P(denovo), chrom and 0-based position when the MAP is not an artifact and P(denovo) >= 0.95; `finalize` evaluates the grid
     and writes the outputs."""
@@ -290,7 +290,7 @@ class ContaminationEstimator(cli.CallProcessor):
         self.k_denovo = list(out_names).index("denovo")
         self.s_sample = list(sample_names).index("sample")
 
-    def process_calls(self, chunk: "cli.CallChunk"):
+    def process_calls(self, chunk: "calldriver.CallChunk"):
         res, s = chunk.results, self.s_sample
         pd = np.asarray(res.ln_posterior[:, self.k_denovo], np.float64)
         mv = np.asarray(res.map_vaf[:, s], np.float64)
@@ -406,6 +406,6 @@ def estimate_contamination(sample: str, contaminant: str, output: Optional[str] 
                            device=0, out=None) -> ContaminationEstimator:
     """estimate_contamination (contamination.rs:430-473): no bias omitted, no full prior, samples ordered by name."""
     est = ContaminationEstimator(output, output_plot, output_max_vaf_variants, prior_estimate, device=device, out=out)
-    cli.call_variants(scenario(), {"sample": sample, "contaminant": contaminant}, afd_capacity=AFD_CAPACITY, device=device if isinstance(device, int) else 0,
-                      processor=est, candidate_filter=cli.ContaminationCandidateFilter())
+    calldriver.call_variants(scenario(), {"sample": sample, "contaminant": contaminant}, afd_capacity=AFD_CAPACITY, device=device if isinstance(device, int) else 0,
+                             processor=est, candidate_filter=calldriver.ContaminationCandidateFilter())
     return est
