@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define VLR_ABI_VERSION 10  /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
+#define VLR_ABI_VERSION 11  /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
                              * 5: sharded device reader, calls-file parts, vlr_ingest_device_trim, CRC32 of BGZF members checked by both readers;
                              * 6: calls emission on the device — vlr_results.afd_text (FORMAT/AFD text), OBS text in the observation summaries,
                              *    vlr_obs_table_summaries;
@@ -42,7 +42,8 @@ extern "C" {
                              * 8: vlr_bamstats_* (`estimate alignment-properties`);
                              * 9: vlr_posterior_odds_keep, vlr_range_group_lse, vlr_calls_filter_odds, vlr_calls_mutational_burden
                              *    (`filter-calls posterior-odds`, `estimate mutational-burden`);
-                             * 10: vlr_basepileup_* (SNV / MNV allele supports from BAM records) */
+                             * 10: vlr_basepileup_* (SNV / MNV allele supports from BAM records);
+                             * 11: vlr_plan_fused_counters (the fused coefficient pass of the lean call kernel) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -374,6 +375,15 @@ int  vlr_plan_last_instance(const vlr_plan* plan, int* waves, int* lean);
 /* Profiling aid: cumulative {pileup-likelihood evaluations, observation terms} executed by the kernels of this
  * plan since creation (or the last reset); synchronises the device.                                     */
 int  vlr_plan_work_counters(vlr_plan* plan, unsigned long long* out2, int reset);
+
+/* Measurement aid for the fused coefficient pass of the lean call kernel (two-sample plans launched without AFD lists): where
+ * artifact hypotheses survive the gates of a locus, the surviving hypotheses are taken in groups of up to three: ONE pass over
+ * the observation rows builds the coefficients of the group's first hypothesis and of the next two, whose sets are parked in
+ * plan-owned device memory and reloaded at their turn (the two sets of a locus are reused by the next group).  out4 = cumulative {fused row passes, sets parked, sets reloaded, hypotheses redone by a row pass of
+ * their own: rescue / all-ones terms, a hypothesis left alone in its group, or no parked set at all} since creation or the last reset (`reset` clears these four alone);
+ * synchronises the device.  VLR_NO_FUSED_COEF=1, read per launch, keeps one row pass per hypothesis (all four stay 0);
+ * VLR_FUSED_SETS=0|1 lowers the parked sets per locus.                                                 */
+int  vlr_plan_fused_counters(vlr_plan* plan, unsigned long long* out4, int reset);
 
 /* ------------------------------------------------------------------------------------------------
  * Read-vs-allele pair HMM: ln P(read window | allele) for a batch of pairs.

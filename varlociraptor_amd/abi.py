@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_SAMPLES = 16
 N_BIAS = 6
 

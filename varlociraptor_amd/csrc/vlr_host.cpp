@@ -288,6 +288,9 @@ struct vlr_plan {
     // kernel scratch, one per slot: the third likelihood coefficient of every kept observation (8 B x max_obs per locus)
     void* escratch[2] = {nullptr, nullptr};
     size_t escratch_bytes[2] = {0, 0};
+    void* parked[2] = {nullptr, nullptr};   // parked coefficient sets of the fused coefficient pass (DevResults::parked), next to escratch
+    size_t parked_bytes[2] = {0, 0};
+    size_t parked_refused[2] = {0, 0};      // smallest size the device had no room for: not asked for again (hipMalloc synchronises)
     // AFD log, one per slot (only when AFD lists are requested): afd_log_words 8-byte words per locus
     void* afd_log[2] = {nullptr, nullptr};
     size_t afd_log_bytes[2] = {0, 0};
@@ -943,6 +946,7 @@ void vlr_plan_destroy(vlr_plan* plan) {
         if (plan->stage[k]) (void)hipFree(plan->stage[k]);
         if (plan->afd_scratch[k]) (void)hipFree(plan->afd_scratch[k]);
         if (plan->escratch[k]) (void)hipFree(plan->escratch[k]);
+        if (plan->parked[k]) (void)hipFree(plan->parked[k]);
         if (plan->afd_log[k]) (void)hipFree(plan->afd_log[k]);
         if (plan->afd_keys[k]) (void)hipFree(plan->afd_keys[k]);
         if (plan->deep_pool[k]) (void)hipFree(plan->deep_pool[k]);
@@ -1046,6 +1050,21 @@ int vlr_plan_fit_max_obs(vlr_plan* plan, const uint32_t* obs_offset_host, int64_
     return rc != VLR_OK ? rc : std::max(1, b);
 }
 
+// Parked sets per locus of a launch that takes the fused coefficient pass (DevResults::parked_sets), -1 for every other launch: the
+// lean unit has the pass (kHasFusedCoef in vlr_kernels.hip).  Read per launch like VLR_NO_LEAN: VLR_NO_FUSED_COEF=1 keeps one row
+// pass per hypothesis, VLR_FUSED_SETS=n lowers the sets per locus (0: every artifact hypothesis keeps its own pass, and is counted).
+static int fused_sets(const vlr_plan* plan, bool want_afd) {
+    if (!plan->lean_ok || want_afd || plan->wide || getenv("VLR_NO_LEAN") || getenv("VLR_NO_FUSED_COEF")) return -1;
+    int n = vlr::kFusedSets;
+    if (const char* ev = getenv("VLR_FUSED_SETS")) n = std::min(std::max(atoi(ev), 0), vlr::kFusedSets);
+    return n;
+}
+
+// (the kernel strides the area by the launch's own number of sets: VLR_FUSED_SETS lowers the footprint with the use)
+static size_t parked_bytes_for(size_t n_loci, int sets, int max_obs) {
+    return std::max<size_t>(n_loci * (size_t)sets * vlr::parked_set_words(max_obs) * sizeof(double), 256);
+}
+
 // Device buffers a batch of n_loci needs besides the caller's: kernel scratch (third coefficients), and with AFD the replay
 // scratch and the AFD log.  Grown here (hipMalloc/hipFree synchronise the device); vlr_batch_run calls this itself, callers that
 // need a strictly asynchronous vlr_batch_run size the plan once with vlr_plan_reserve.
@@ -1091,6 +1110,16 @@ static int ensure_buffers(vlr_plan* plan, int64_t n_loci, int max_obs, bool want
         // one 8-byte key per AFD entry of the batch (as large as the caller's own afd_vaf): the l2fc part of the reference's map key
         rc = grow(&plan->afd_keys[k], &plan->afd_keys_bytes[k], L * (size_t)plan->host.S * (size_t)std::max(afd_capacity, 1) * sizeof(long long), false);
         if (rc != VLR_OK) return rc;
+    }
+    // Parked coefficient sets, only for launches that take the fused pass, and after everything a launch cannot do without.  Optional:
+    // without room for them the launch keeps one row pass per hypothesis (vlr_plan_fused_counters shows it), and a size the device
+    // refused once is not asked for again, so that vlr_batch_run stays asynchronous after vlr_plan_reserve either way.
+    if (const int fs = fused_sets(plan, want_afd); fs >= 0) {
+        const size_t need = parked_bytes_for(L, fs, max_obs);
+        if (need > plan->parked_bytes[k] && (plan->parked_refused[k] == 0 || need < plan->parked_refused[k])) {
+            (void)grow(&plan->parked[k], &plan->parked_bytes[k], need, true);
+            if (!plan->parked[k]) plan->parked_refused[k] = need;
+        }
     }
     return VLR_OK;
 }
@@ -1157,6 +1186,10 @@ int vlr_batch_run(vlr_plan* plan, const vlr_batch* in, vlr_results* out, void* s
         r.afd_key = (long long*)plan->afd_keys[k];
     }
     r.escratch = (double*)plan->escratch[plan->slot & 1];
+    if (const int fs = fused_sets(plan, want_afd); fs >= 0 && plan->parked[plan->slot & 1] && plan->parked_bytes[plan->slot & 1] >= parked_bytes_for((size_t)in->n_loci, fs, max_obs)) {
+        r.parked = (double*)plan->parked[plan->slot & 1];
+        r.parked_sets = fs;
+    }
     if (want_afd && !getenv("VLR_AFD_REPLAY") && plan->afd_log[plan->slot & 1]) {
         r.afd_log = (double*)plan->afd_log[plan->slot & 1];
         r.afd_log_stride = (long long)plan->afd_log_words;
@@ -1297,6 +1330,17 @@ int vlr_plan_work_counters(vlr_plan* plan, unsigned long long* out2, int reset) 
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out2, plan->work_dev, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (reset) HIP_TRY(hipMemset(plan->work_dev, 0, 64 * sizeof(unsigned long long)));
+    return VLR_OK;
+}
+
+// measurement aid: cumulative {fused row passes, sets parked, sets reloaded, hypotheses redone by a row pass of their own} of the
+// fused coefficient pass since plan creation or the last reset (synchronises; `reset` clears these four counts alone)
+int vlr_plan_fused_counters(vlr_plan* plan, unsigned long long* out4, int reset) {
+    if (!plan || !out4) return fail(VLR_ERR_INVALID_ARGUMENT, "null argument");
+    HIP_TRY(hipSetDevice(plan->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out4, plan->work_dev + vlr::kFusedCounter0, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(plan->work_dev + vlr::kFusedCounter0, 0, 4 * sizeof(unsigned long long)));
     return VLR_OK;
 }
 

@@ -51,6 +51,11 @@ constexpr bool kHasLfc = !VLR_LEAN;          // l2fc operands on the path and th
 // tables of at most 64 entries — walk_root only ever meets the last kind, from its root node, outside the probe pass.
 constexpr bool kHasGeneralWalk = !VLR_LEAN;
 constexpr bool kHasManySamples = !VLR_LEAN;  // plans above kXcdMapMaxSamples samples                                 (lean: S <= 2)
+// The fused coefficient pass (phase B): one pass over the rows builds the coefficients of the first kFusedSets surviving artifact
+// hypotheses next to those of h = none and parks them in DevResults::parked.  The only trait that compiles something IN: the lean
+// unit alone has it (the other units keep one row pass per hypothesis); the host enables it per launch by passing `parked`.
+#define VLR_FUSED_COEF (VLR_LEAN && !VLR_DEEP)
+constexpr bool kHasFusedCoef = VLR_FUSED_COEF;
 
 namespace vlr {
 
@@ -915,6 +920,8 @@ __device__ __forceinline__ bool ones_any(const Ctx& c) { return ((unsigned)c.eha
 __device__ __forceinline__ bool ones_risk(const Ctx& c, int s) { return (((unsigned)c.ehas >> (16 + s)) & 1u) != 0u; }
 __device__ __forceinline__ bool is_all_ones(const DevPlan& p, int s, double a, double b) { return a == 1.0 && (p.by[s] < 0 || b == 1.0); }
 // (the 2 S words in front of the locus' scratch row: no pointer of their own in the context)
+// (valid only while c.ecoef is the locus' own scratch row: a hypothesis reloaded from a parked set has c.ecoef inside that set and
+//  onesmask == 0, so ones_any(c) is false and nothing comes here)
 __device__ __forceinline__ double* ones_ptr(const Ctx& c) { return const_cast<double*>(c.ecoef) - 2 * c.S; }
 __device__ __forceinline__ void ones_load(const Ctx& c, int s, double& Pm, int& E) {
     const double* o = ones_ptr(c);
@@ -4081,6 +4088,124 @@ __global__ void __launch_bounds__(64, WPE) vlr_call_kernel(const DevPlan plan_ar
     // into VGPRs and spilled to scratch across the loop)
     const double ln_bias_share = uni_d(kLn05 + log(1.0 / (double)n_biases));
     const SgprD reverse_rate = park_sd(1.0 - forward_rate);
+#if VLR_FUSED_COEF
+    // The terms of one kept observation, in two parts.  obs_shared: everything that does not depend on the hypothesis — every
+    // transcendental of the row; `want_sb` / `want_hev` / `want_hea` say which of the strand factor and the two homopolymer factors some
+    // hypothesis of the pass reads (wave-uniform: the others cost nothing).  obs_hyp: the selects and products of hypothesis hh — the
+    // affine coefficients, the term at alpha = beta = 1 formed directly (one_t) and what c + q + e cancels there (ref_t); `scaled`:
+    // relative to the observation's own power of two 2^ki.  One row pass per hypothesis calls both per hypothesis; the fused pass
+    // calls obs_shared once per row and obs_hyp per hypothesis, which gives the same bits.
+    struct ObsShared { double wv, mis, ea, er, em, sv, rp_any, sb, he_v, he_a; };
+    auto obs_shared = [&](const ObsRow& cur, bool ehas_s, bool want_sb, bool want_hev, bool want_hea) {
+        ObsShared t;
+        double pm = cur.pm, pa = cur.pa, pr = cur.pr, miss = cur.miss;
+        double psa = cur.psa, pdo = cur.pdo, phb = cur.phb;
+        if (singleton && pa > pr) { pa = kLn05; pr = kLn05; }  // prob_alt_adj / prob_ref_adj
+        const int strand = f_strand(cur.f);
+        const bool major = (cur.f & VLR_F_READPOS_MAJOR) != 0;
+        // read position: prob_any (read_position_bias.rs:27-37,51-62)
+        double one_minus_hit = (phb != 0.0) ? -expm1(phb) : 1.0;
+        t.rp_any = major ? exp(phb) : one_minus_hit;
+        // strand (strand_bias.rs:30-58), every hypothesis but the two strand artifacts
+        t.sb = 1.0;
+        if (want_sb) {
+            if (strand == VLR_STRAND_BOTH) t.sb = exp(pdo);
+            else if (strand == VLR_STRAND_NONE) t.sb = 1.0;
+            else {
+                double rate = (strand == VLR_STRAND_FORWARD) ? forward_rate : fresh_sd(reverse_rate);
+                t.sb = rate * (-expm1(pdo));  // ln(rate) + prob_single_overlap
+            }
+        }
+        // homopolymer (homopolymer_error.rs:23-44): prob_ref = prob_alt, prob_any = 1
+        t.he_v = 1.0; t.he_a = 1.0;
+        if (want_hev) {
+            const double he_lp = cur.hpv;
+            if (__ballot(he_lp == he_lp)) t.he_v = (he_lp == he_lp) ? exp(he_lp) : 1.0;  // (no homopolymer evidence in the whole row: no exponential)
+        }
+        if (want_hea) {
+            const double he_lp = cur.hpa;
+            if (__ballot(he_lp == he_lp)) t.he_a = (he_lp == he_lp) ? exp(he_lp) : 1.0;
+        }
+        t.wv = exp(pm);
+        t.mis = -expm1(pm);  // prob_mismapping = ln_one_minus_exp(pm) (read_observation.rs:283-286)
+        t.ea = exp(pa); t.er = exp(pr); t.em = exp(miss);
+        t.sv = ehas_s ? exp(psa) : 1.0;  // (!ehas: prob_sample_alt == 0 on every kept observation of the sample, e^0 = 1)
+        return t;
+    };
+    auto obs_hyp = [&](const ObsRow& cur, const ObsShared& t, int hh, int scaled, double& cc_, double& cq_, double& ce_, double& one_t, double& ref_t, bool& uflow, int& ki) {
+        const uint32_t f = cur.f;
+        ki = 0;
+        double pa = cur.pa, pr = cur.pr;
+        if (singleton && pa > pr) { pa = kLn05; pr = kLn05; }
+        int strand = f_strand(f), orient = f_orient(f);
+        bool major = (f & VLR_F_READPOS_MAJOR) != 0;
+        // linear-space bias factors for alt / ref / any
+        double fa, fr, fany;
+        // strand (strand_bias.rs:30-58)
+        double sb_alt;
+        if (hh == H_SBF) sb_alt = (strand == VLR_STRAND_FORWARD || strand == VLR_STRAND_NONE) ? 1.0 : 0.0;
+        else if (hh == H_SBR) sb_alt = (strand == VLR_STRAND_REVERSE || strand == VLR_STRAND_NONE) ? 1.0 : 0.0;
+        else sb_alt = t.sb;
+        // orientation (read_orientation_bias.rs:18-36)
+        double ro_alt = 0.5;
+        if (hh == H_F1R2) ro_alt = (orient == VLR_ORIENT_F1R2) ? 1.0 : (orient == VLR_ORIENT_F2R1) ? 0.0 : 0.5;
+        else if (hh == H_F2R1) ro_alt = (orient == VLR_ORIENT_F2R1) ? 1.0 : (orient == VLR_ORIENT_F1R2) ? 0.0 : 0.5;
+        // position (read_position_bias.rs:18-25)
+        double rp_alt = (hh == H_RPB) ? (major ? 1.0 : 0.0) : t.rp_any;
+        // softclip (softclip_bias.rs:15-29)
+        double sc_alt = (hh == H_SCB) ? ((f & VLR_F_SOFTCLIPPED) ? 1.0 : 0.0) : 1.0;
+        double he_alt = (hh == H_HE) ? t.he_a : t.he_v;
+        // alt locus (alt_locus_bias.rs:63-113)
+        double al_alt = 0.5, al_ref = 0.5;
+        if (hh == H_ALB) {
+            if (has_alt_loci) {
+                bool mj = f_altlocus(f) == VLR_ALTLOCUS_MAJOR;
+                al_alt = mj ? 1.0 : 0.0;
+                al_ref = mj ? 0.0 : 1.0;
+            } else {
+                al_alt = (f & VLR_F_MAX_MAPQ) ? 0.0 : 1.0;
+                al_ref = 0.5;
+            }
+        }
+        fa = sb_alt * ro_alt * rp_alt * sc_alt * he_alt * al_alt;
+        fr = 0.5 * 0.5 * t.rp_any * 1.0 * he_alt * al_ref;
+        fany = 0.5 * 0.5 * t.rp_any * 0.5;
+        const double wv = t.wv, mis = t.mis, sv = t.sv;
+        double A = t.ea * fa, R = t.er * fr;
+        double uu = mis * t.em * fany;
+        uflow = (A == 0.0 && fa != 0.0 && pa > VLR_NEG_INF) || (R == 0.0 && fr != 0.0 && pr > VLR_NEG_INF);
+        double d = A - R;
+        cc_ = wv * R + uu; cq_ = wv * sv * d; ce_ = wv * (1.0 - sv) * d;
+        one_t = wv * A + uu; ref_t = wv * R;  // the term at alpha = beta = 1 formed directly, and what c + q + e cancels
+        if (__builtin_expect(scaled != 0, 0)) {
+            // the three log-space addends of the observation's likelihood, their largest as the binary exponent k
+            const double pm = cur.pm, miss = cur.miss;
+            const double lA = (fa > 0.0 && pa > VLR_NEG_INF) ? pm + pa + log(fa) : VLR_NEG_INF;
+            const double lR = (fr > 0.0 && pr > VLR_NEG_INF) ? pm + pr + log(fr) : VLR_NEG_INF;
+            const double lU = (mis > 0.0 && fany > 0.0 && miss > VLR_NEG_INF) ? log(mis) + miss + log(fany) : VLR_NEG_INF;
+            const double mx = fmax(lA, fmax(lR, lU));
+            ki = (mx > VLR_NEG_INF) ? (int)floor(mx / kLn2) : 0;
+            const double sh = (double)ki * kLn2;
+            const double WA = (lA > VLR_NEG_INF) ? exp(lA - sh) : 0.0, WR = (lR > VLR_NEG_INF) ? exp(lR - sh) : 0.0;
+            const double UU = (lU > VLR_NEG_INF) ? exp(lU - sh) : 0.0;
+            d = WA - WR;
+            cc_ = WR + UU; cq_ = sv * d; ce_ = (1.0 - sv) * d;
+            one_t = WA + UU; ref_t = WR;
+            uflow = false;
+        }
+    };
+    // Fused coefficient pass (kHasFusedCoef, DevResults::parked): a hypothesis that finds other surviving hypotheses behind it leads a
+    // group — its row pass also builds the coefficients of the next parked_sets of them and parks those in the locus' parked sets;
+    // a parked hypothesis starts by copying its set into the coefficient area (which frees the set for the next group), so
+    // 1 + parked_sets hypotheses share one pass over the rows.  A hypothesis whose terms need the underflow rescue or the all-ones
+    // pass takes the row pass of its own at its turn ("redone"), as every artifact hypothesis does with parked_sets == 0.
+    double* const park0 = out.parked ? out.parked + (size_t)locus * (size_t)out.parked_sets * parked_set_words(max_obs) : nullptr;
+    const double* const ecoef0 = c.ecoef;
+    unsigned parked_ok = 0;   // bit h: the coefficients of hypothesis h are parked, in set (setof >> 2 h) & 3
+    unsigned setof = 0;
+    unsigned rare = 0;        // bit h: a fused pass found h in need of the rescue or the all-ones pass
+    unsigned fusedcnt = 0;    // bytes: fused row passes, sets parked, sets reloaded, hypotheses redone
+#endif
     for (int h = 0; h < kNHyp; ++h) {
         if (!((hyps >> h) & 1u)) continue;
         c.hyp = h;
@@ -4090,7 +4215,122 @@ __global__ void __launch_bounds__(64, WPE) vlr_call_kernel(const DevPlan plan_ar
         //   c = w*R + u, q = w*s*(A-R), e = w*(1-s)*(A-R)
         // (likelihood.rs:43-53,86-115,171-220; bias factors bias/mod.rs:259-284)
         int fastmask = 0, vfastmask = 0, onesmask = 0;
-        for (int s = 0; s < S; ++s) {
+        bool have = false;   // the coefficients of h are in place already (fused pass or reload): no row pass of its own
+#if VLR_FUSED_COEF
+        if (park0) {
+            c.ecoef = ecoef0;
+            bool led = false;
+            if (!(((parked_ok | rare) >> h) & 1u)) {
+                // the group: h and the next parked_sets surviving hypotheses; member g (4 bits of `grp`) is parked in set g - 1
+                unsigned grp = (unsigned)h, ng = 1;
+                unsigned rest = hyps & ~rare & ~((2u << h) - 1u);
+                bool want_sb = h != H_SBF && h != H_SBR, want_hev = h != H_HE, want_hea = h == H_HE;
+                for (int g = 1; g <= kFusedSets && g <= out.parked_sets && rest; ++g) {
+                    const int hg = __ffs(rest) - 1;
+                    rest &= rest - 1u;
+                    grp |= (unsigned)hg << (4 * g); ng = g + 1;
+                    want_sb = want_sb || (hg != H_SBF && hg != H_SBR);
+                    want_hev = want_hev || hg != H_HE;
+                    want_hea = want_hea || hg == H_HE;
+                }
+                if (ng > 1) {
+                    // per member g, 8 bits each (lean: two samples): bit s of byte g = fast / very fast sample mask; redo: bit g
+                    unsigned fm = 0, vm = 0, redo = 0;
+                    for (int s = 0; s < S; ++s) {
+                        const int64_t pidx = locus * S + s;
+                        const uint32_t o0 = batch.obs_offset[pidx], o1 = batch.obs_offset[pidx + 1];
+                        int wr = w->soff[s];
+                        const bool ehas_s = (ehas_mask >> s) & 1;
+                        unsigned slow = 0, vslow = 0;   // bit g: some term of member g is tiny / small
+                        ObsRow nxt = load_obs_row(batch, o0 + lane, o1);
+                        for (uint32_t base = o0; base < o1; base += 64) {
+                            uint32_t i = base + lane;
+                            bool valid = i < o1;
+                            const ObsRow cur = nxt;
+                            if (base + 64 < o1) nxt = load_obs_row(batch, i + 64, o1);
+                            bool keep = valid && !(remove_nonstd && f_orient(cur.f) == VLR_ORIENT_OTHER);
+                            unsigned long long km = __ballot(keep);
+                            int pos = wr + popc64(km & ((1ull << lane) - 1ull));
+                            ObsShared sh{};
+                            if (keep) sh = obs_shared(cur, ehas_s, want_sb, want_hev, want_hea);
+#pragma nounroll
+                            for (unsigned g = 0; g < ng; ++g) {
+                                bool tiny = false, small = false, bad = false;
+                                if (keep) {
+                                    double cc_, cq_, ce_, one_t, ref_t;
+                                    bool uflow;
+                                    int ki;
+                                    obs_hyp(cur, sh, (int)((grp >> (4 * g)) & 15u), 0, cc_, cq_, ce_, one_t, ref_t, uflow, ki);
+                                    if (pos < max_obs) {
+                                        if (g == 0) {
+                                            c.coef[2 * pos + 0] = cc_;
+                                            c.coef[2 * pos + 1] = cq_;
+                                            if (ehas_s) __hip_atomic_store(const_cast<double*>(ecoef0) + pos, ce_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                        } else {
+                                            double* ps = park0 + (size_t)(g - 1) * parked_set_words(max_obs) + 2;
+                                            *reinterpret_cast<double2*>(ps + 2 * pos) = make_double2(cc_, cq_);   // 16 B per lane, consecutive kept lanes adjacent
+                                            if (ehas_s) __hip_atomic_store(ps + 2 * max_obs + pos, ce_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                        }
+                                    }
+                                    // (the corner tests of the row pass below)
+                                    double mn = fmin(fmin(cc_, cc_ + cq_), fmin(cc_ + ce_, cc_ + cq_ + ce_));
+                                    tiny = !(mn >= 0x1p-200);
+                                    small = !(mn >= 0x1p-70 && fmax(fmax(cc_, cc_ + cq_), fmax(cc_ + ce_, cc_ + cq_ + ce_)) <= 2.0);
+                                    bad = (uflow && !(mn >= 0x1p-1022)) || (ref_t > 0x1p24 * one_t);
+                                }
+                                if (__ballot(tiny)) slow |= 1u << g;
+                                if (__ballot(small)) vslow |= 1u << g;
+                                if (__ballot(bad)) redo |= 1u << g;
+                            }
+                            wr += popc64(km);
+                        }
+                        for (unsigned g = 0; g < ng; ++g) {
+                            if (!((slow >> g) & 1u)) fm |= 1u << (8 * g + s);
+                            if (!((vslow >> g) & 1u)) vm |= 1u << (8 * g + s);
+                        }
+                    }
+                    fusedcnt += 1u;
+                    led = true;
+                    for (unsigned g = 1; g < ng; ++g) {
+                        const unsigned hg = (grp >> (4 * g)) & 15u;
+                        if ((redo >> g) & 1u) { rare |= 1u << hg; continue; }
+                        if (lane == 0) {
+                            long long* hd = reinterpret_cast<long long*>(park0 + (size_t)(g - 1) * parked_set_words(max_obs));
+                            __hip_atomic_store(hd, (long long)((fm >> (8 * g)) & 0xffu) | ((long long)((vm >> (8 * g)) & 0xffu) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                        parked_ok |= 1u << hg;
+                        setof = (setof & ~(3u << (2 * hg))) | ((g - 1) << (2 * hg));
+                        fusedcnt += 1u << 8;
+                    }
+                    if (!(redo & 1u)) {
+                        have = true;
+                        fastmask = (int)(fm & 0xffu); vfastmask = (int)(vm & 0xffu);
+                        if (lane < S) kshift(c)[lane] = 0;
+                    }
+                }
+            } else if ((parked_ok >> h) & 1u) {
+                // reload: the parked set of h into the coefficient area; its e row is read where it lies.  The pairs were stored by other
+                // lanes of this wave with plain stores and are read back with plain loads: same-wave vector memory operations execute in
+                // order through the CU's L1, and the VLR_SYNC() at the end of every coefficient pass (the fused one included) keeps the
+                // compiler from moving these loads above those stores — the arrangement the e row has always relied on.
+                // ones_ptr(c) = c.ecoef - 2 S points INTO the pair row while c.ecoef is repointed: nothing may read it, and nothing does,
+                // because a parked hypothesis has no all-ones products (onesmask == 0: a risky term sends it to the row pass of its own).
+                const int g = (int)((setof >> (2 * h)) & 3u);
+                const double* ps = park0 + (size_t)g * parked_set_words(max_obs);
+                const long long hd = UNI64(__hip_atomic_load(reinterpret_cast<const long long*>(ps), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                fastmask = (int)(hd & 0xffffffffll); vfastmask = (int)(hd >> 32);
+                const double2* src = reinterpret_cast<const double2*>(ps + 2);
+                double2* dst = reinterpret_cast<double2*>(c.coef);
+                for (int i = lane; i < offset_acc; i += 64) dst[i] = src[i];
+                c.ecoef = ps + 2 + 2 * max_obs;
+                if (lane < S) kshift(c)[lane] = 0;
+                have = true;
+                fusedcnt += 1u << 16;
+            }
+            if (!have && (h != 0 || led)) fusedcnt += 1u << 24;   // a row pass of its own below (h = none: only behind a fused pass that met rare terms)
+        }
+#endif
+        for (int s = have ? S : 0; s < S; ++s) {
             const int64_t pidx = locus * S + s;
             const uint32_t o0 = batch.obs_offset[pidx], o1 = batch.obs_offset[pidx + 1];
             int wr = w->soff[s];
@@ -4102,6 +4342,13 @@ __global__ void __launch_bounds__(64, WPE) vlr_call_kernel(const DevPlan plan_ar
             // sample gets back (kshift_ln).  Never taken on pair-HMM output (supports are normalised, realignment/mod.rs:359-374).
             bool need_rescue = false;
             int kacc = 0;
+#if VLR_FUSED_COEF
+            // (obs_shared + obs_hyp above: the same expressions as below, split where the hypothesis comes in)
+            auto obs_terms = [&](const ObsRow& cur, int scaled, double& cc_, double& cq_, double& ce_, double& one_t, double& ref_t, bool& uflow, int& ki) {
+                const ObsShared sh = obs_shared(cur, ehas_s, h != H_SBF && h != H_SBR, h != H_HE, h == H_HE);
+                obs_hyp(cur, sh, h, scaled, cc_, cq_, ce_, one_t, ref_t, uflow, ki);
+            };
+#else
             // the terms of one kept observation under hypothesis h: the affine coefficients, the term at alpha = beta = 1 formed directly
             // (one_t) and what c + q + e cancels there (ref_t); `scaled`: relative to the observation's own power of two 2^ki
             auto obs_terms = [&](const ObsRow& cur, int scaled, double& cc_, double& cq_, double& ce_, double& one_t, double& ref_t, bool& uflow, int& ki) {
@@ -4181,6 +4428,7 @@ __global__ void __launch_bounds__(64, WPE) vlr_call_kernel(const DevPlan plan_ar
                         uflow = false;
                     }
             };
+#endif
           for (int scaled = 0; scaled < 2; ++scaled) {
             if (scaled && !need_rescue) break;
             wr = w->soff[s]; fast_s = 1; vfast_s = 1;
@@ -4450,6 +4698,9 @@ __global__ void __launch_bounds__(64, WPE) vlr_call_kernel(const DevPlan plan_ar
         }
         PROF_ADD(c, 3);
     }
+#if VLR_FUSED_COEF
+    c.ecoef = ecoef0;   // (a last hypothesis that was reloaded leaves it inside its parked set)
+#endif
     PROF_ADD(c, 3);  // walk remainder (everything in the event loop not attributed below)
     if (kHasReplay && c.replay) {
         afd_finish(c);
@@ -4570,6 +4821,11 @@ __global__ void __launch_bounds__(64, WPE) vlr_call_kernel(const DevPlan plan_ar
         if (out.work) {
             atomicAdd(&out.work[0], w->work[0]);
             atomicAdd(&out.work[1], w->work[1]);
+#if VLR_FUSED_COEF
+            if (fusedcnt)
+                for (int i = 0; i < 4; ++i)
+                    if ((fusedcnt >> (8 * i)) & 0xffu) atomicAdd(&out.work[kFusedCounter0 + i], (unsigned long long)((fusedcnt >> (8 * i)) & 0xffu));
+#endif
 #ifdef VLR_PROFILE
             PROF_ADD(c, 9);  // phase C
             for (int i = 0; i < 40; ++i) atomicAdd(&out.work[2 + i], c.prof[i]);

@@ -209,6 +209,18 @@ struct DevResults {
     double* deep_pool;
     unsigned long long* deep_used;
     long long deep_capacity;
+    // fused coefficient pass (lean unit; nullptr: one row pass per hypothesis): per locus parked_sets sets of parked_set_words(max_obs)
+    // doubles, one per hypothesis whose coefficients the row pass of its group's first hypothesis built along — 2 header words (fast /
+    // very-fast sample masks), the {c, q} pairs of every kept observation, then their third coefficients e; a set is free again once
+    // its hypothesis has copied it into the coefficient area, so the next group of the locus reuses it
+    double* parked;
+    int32_t parked_sets;    // 0 .. kFusedSets; surviving hypotheses beyond it keep their own row pass
 };
+
+constexpr int kFusedSets = 2;
+// (max_obs is a multiple of four: every set, its pair row and its e row start 16 B aligned)
+constexpr size_t parked_set_words(int max_obs) { return 2 + 3 * (size_t)max_obs; }
+// slots of DevResults::work behind the work and profile counters: fused row passes, sets parked, sets reloaded, hypotheses redone
+constexpr int kFusedCounter0 = 48;
 
 }  // namespace vlr

@@ -24,7 +24,7 @@ _LIB = None
 EXPORTS = [
     "vlr_abi_version", "vlr_build_id", "vlr_last_error", "vlr_plan_create", "vlr_plan_destroy", "vlr_plan_n_out",
     "vlr_plan_n_samples", "vlr_plan_set_max_depth", "vlr_plan_set_max_obs", "vlr_plan_fit_max_obs", "vlr_plan_reserve", "vlr_batch_run", "vlr_batch_run_host", "vlr_batch_run_device_in",
-    "vlr_plan_last_kernel_ms", "vlr_plan_last_instance", "vlr_plan_work_counters", "vlr_host_alloc", "vlr_host_free",
+    "vlr_plan_last_kernel_ms", "vlr_plan_last_instance", "vlr_plan_work_counters", "vlr_plan_fused_counters", "vlr_host_alloc", "vlr_host_free",
     "vlr_node_create", "vlr_node_destroy", "vlr_node_n_devices", "vlr_node_device", "vlr_node_plan", "vlr_node_set_max_depth", "vlr_node_set_max_obs", "vlr_node_shard_range", "vlr_node_batch_run_host",
     "vlr_realign_batch", "vlr_realign_batch_host", "vlr_realign_fast_batch", "vlr_realign_fast_batch_host", "vlr_realign_homopolymer_batch", "vlr_realign_homopolymer_batch_host", "vlr_edit_distance_batch", "vlr_edit_distance_batch_host", "vlr_fdr_threshold", "vlr_contamination_posterior", "vlr_bamstats_open", "vlr_bamstats_add_bam", "vlr_bamstats_result", "vlr_bamstats_read", "vlr_bamstats_close", "vlr_basepileup_open", "vlr_basepileup_add_bam", "vlr_basepileup_result", "vlr_basepileup_read", "vlr_basepileup_tables", "vlr_basepileup_close", "vlr_selftest_math", "vlr_selftest_stream", "vlr_selftest_format_fixed", "vlr_selftest_afd_text",
     "vlr_obs_read", "vlr_obs_table_free", "vlr_obs_table_batch", "vlr_obs_table_sites", "vlr_obs_write", "vlr_calls_write", "vlr_ingest_last_timings", "vlr_ingest_total_timings",
@@ -134,6 +134,8 @@ def lib():
         L.vlr_host_free.argtypes = [C.c_void_p]
         L.vlr_plan_work_counters.restype = C.c_int
         L.vlr_plan_work_counters.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
+        L.vlr_plan_fused_counters.restype = C.c_int
+        L.vlr_plan_fused_counters.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
         if L.vlr_abi_version() != abi.ABI_VERSION:
             raise EngineError(abi.ERR_INVALID_ARGUMENT, "ABI version mismatch")
         _LIB = L
@@ -270,6 +272,13 @@ class Plan:
         out = (C.c_ulonglong * 2)()
         _check(lib().vlr_plan_work_counters(self._h, out, int(reset)))
         return int(out[0]), int(out[1])
+
+    def fused_counters(self, reset: bool = False):
+        """(fused row passes, sets parked, sets reloaded, hypotheses redone) of the lean unit's fused coefficient pass since the
+        last reset (vlr_plan_fused_counters); all zero under VLR_NO_FUSED_COEF=1 and for launches of the other units."""
+        out = (C.c_ulonglong * 4)()
+        _check(lib().vlr_plan_fused_counters(self._h, out, int(reset)))
+        return tuple(int(v) for v in out)
 
 
 def shard_range(n_loci: int, n_shards: int, shard: int):
