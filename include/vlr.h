@@ -396,10 +396,13 @@ int  vlr_plan_fused_counters(vlr_plan* plan, unsigned long long* out4, int reset
  *
  * Pair p: allele bases x_bases[x_offset[p] .. x_offset[p+1]) (ASCII, case-insensitive), read window
  * y_bases / y_quals [y_offset[p] .. y_offset[p+1]) (ASCII bases, PHRED qualities without offset), at most 128 read bases
- * (EditDistanceCalculation::max_pattern_len, edit_distance.rs:145-147).  max_edit_dist[p] >= 0 restricts the matrix
+ * (EditDistanceCalculation::max_pattern_len, edit_distance.rs:145-147).  Qualities above 93 — the largest PHRED value a
+ * SAM / FASTQ record can hold — are out of range: the scaling of the summing kernels is dimensioned for error
+ * probabilities down to 10^-9.3.  max_edit_dist[p] >= 0 restricts the matrix
  * to cells reachable with at most that many edits (band = hit distance + 4, pairhmm.rs:20); < 0 or a NULL array:
  * full matrix.  gap[] = ln { P(gap in x) = prob_insertion_artifact, P(gap in y) = prob_deletion_artifact,
- * P(extend gap in x), P(extend gap in y) } (pairhmm.rs:119-180; -inf = no extension, the default).
+ * P(extend gap in x), P(extend gap in y) } (pairhmm.rs:119-180; -inf = no extension, the default); P(gap in x) +
+ * P(gap in y) above one (beyond rounding) leaves no probability for a match and is VLR_ERR_INVALID_ARGUMENT.
  * ln_prob[p] <- result, -inf for an empty sequence, NaN for a read window above 128 bases.            */
 typedef struct vlr_realign_batch_desc {
     int64_t n_pairs;

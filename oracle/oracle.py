@@ -155,10 +155,16 @@ def homopoly_prob_related(allele: bytes, read: bytes, qual, gap, hop, max_edit_d
     return float(L.vlro_homopoly_prob_related(x.ctypes.data, len(allele), y.ctypes.data, q.ctypes.data, len(read), g, h, int(max_edit_dist)))
 
 
-def homopoly_batch(batch, gap, hop):
+def homopoly_batch(batch, gap, hop, threads=1):
     g = [gap.prob_insertion_artifact, gap.prob_deletion_artifact, gap.prob_insertion_extend_artifact, gap.prob_deletion_extend_artifact]
     h = hop.as_list()
-    return np.array([homopoly_prob_related(batch.x[k], batch.y[k], batch.q[k], g, h, batch.band[k]) for k in range(len(batch))])
+    f = lambda k: homopoly_prob_related(batch.x[k], batch.y[k], batch.q[k], g, h, batch.band[k])
+    if threads > 1:
+        lib()  # bind once, before the workers
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=threads) as ex:
+            return np.array(list(ex.map(f, range(len(batch)))))
+    return np.array([f(k) for k in range(len(batch))])
 
 
 def edit_distance(allele: bytes, read: bytes):

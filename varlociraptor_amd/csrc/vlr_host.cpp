@@ -1793,6 +1793,8 @@ static int check_realign(const vlr_realign_batch_desc* b, const double* ln_prob)
     if (b->n_pairs < 0) return fail(VLR_ERR_INVALID_ARGUMENT, "negative pair count");
     for (int k = 0; k < 4; ++k)
         if (b->gap[k] != b->gap[k] || b->gap[k] > 0.0) return fail(VLR_ERR_INVALID_ARGUMENT, "gap[%d] is not a log probability", k);
+    // P(no gap) = 1 - (P(gap x) + P(gap y)) must not be negative (a sum of one is legal; 1e-12 covers the rounding of exp)
+    if (std::exp(b->gap[0]) + std::exp(b->gap[1]) > 1.0 + 1e-12) return fail(VLR_ERR_INVALID_ARGUMENT, "P(gap in x) + P(gap in y) exceeds one");
     return VLR_OK;
 }
 

@@ -52,6 +52,30 @@ __device__ __forceinline__ unsigned shr1(unsigned v, unsigned edge) {
 
 constexpr unsigned kBig = 0x3fffffffu;  // "unreachable" edit distance (adding one cannot wrap)
 
+// Scaling of the three summing kernels.  Every lane stores its states and its total with a factor 2^scale of its own.
+//   * own states only shrink from step to step (every factor of the recurrence is at most one), by at most 2^-50 per step for
+//     qualities up to 93 (a gap open times the insertion emission; a Q93 mismatch is 2^-35): the check every 8 steps, which brings
+//     a lane whose largest state left 2^+-200 back to ~1, keeps them above 2^-600;
+//   * what can GROW is what the lane above hands down: deep rows of a read swing by hundreds of binary orders between adjacent
+//     columns, and a lane that has just brought tiny lead-in cells up to ~1 may be handed the bulk, 2^1000 and more above them,
+//     at the next step.  So the exchange looks at what arrives BEFORE it is multiplied: if it would land above 2^200 in this
+//     lane's units the lane lowers its own scale first so that it lands at ~1 (its own states, then more than 200 binary
+//     orders below, keep their exact values or, beyond the range of f64, are flushed to zero).
+// With that no state exceeds ~2^203 and nothing that carries weight falls below 2^-600: no overflow, no NaN, for read windows
+// of up to 128 bases and qualities up to 93 (include/vlr.h).  All factors are powers of two, so scaling never rounds.
+constexpr int kScaleHi = 200;
+// exponent by which a lane lowers its scale before it takes `mi` (largest incoming state, in the units of the lane above) times 2^dsc
+__device__ __forceinline__ int incoming_excess(double mi, int dsc) {
+    int ei = 0;
+    (void)__builtin_frexp(mi, &ei);
+    const int ein = ei + dsc;
+    return (mi > 0.0 && dsc != 0 && ein > kScaleHi) ? ein : 0;
+}
+// 2^-e for the lane's own states: exactly zero once they would leave the range of f64
+__device__ __forceinline__ double down_factor(int e) { return __builtin_ldexp(1.0, e > 1100 ? -1100 : -e); }
+// factor for incoming states: finite for empty input of any scale difference, zero for what lies 2^1100 below this lane
+__device__ __forceinline__ double align_factor(int dsc) { return __builtin_ldexp(1.0, dsc > 1000 ? 1000 : dsc < -1100 ? -1100 : dsc); }
+
 __device__ __forceinline__ void realign_one(const RealignArgs& a, const int64_t pair, const int lane) {
     const uint32_t x0 = a.x_offset[pair], y0 = a.y_offset[pair];
     const int len_x = (int)(a.x_offset[pair + 1] - x0), len_y = (int)(a.y_offset[pair + 1] - y0);
@@ -115,8 +139,15 @@ __device__ __forceinline__ void realign_one(const RealignArgs& a, const int64_t 
                 const double mass = ((M1[0] + M1[1]) + (X1[0] + X1[1])) + ((Y1[0] + Y1[1]) + (Mt[0] + Mt[1])) + ((Xt[0] + Xt[1]) + (Yt[0] + Yt[1])) + total;
                 if (mass == 0.0) scale = nb;
                 int dsc = scale - nb;
-                dsc = dsc > 1000 ? 1000 : dsc < -1000 ? -1000 : dsc;
-                const double f = __builtin_ldexp(1.0, dsc);
+                const int over = incoming_excess(fmax(fmax(Mu[0], Xu[0]), Yu[0]), dsc);
+                if (over) {  // (per lane) make room for what arrives
+                    const double g = down_factor(over);
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) { M1[r] *= g; X1[r] *= g; Y1[r] *= g; Mt[r] *= g; Xt[r] *= g; Yt[r] *= g; }
+                    total *= g;
+                    scale -= over; dsc -= over;
+                }
+                const double f = align_factor(dsc);
                 Mu[0] *= f; Xu[0] *= f; Yu[0] *= f;
             }
         }
@@ -156,10 +187,11 @@ __device__ __forceinline__ void realign_one(const RealignArgs& a, const int64_t 
         // this step's "top" of a row is its "top-left" at the next step
 #pragma unroll
         for (int r = 0; r < 2; ++r) { Mt[r] = Mu[r]; Xt[r] = Xu[r]; Yt[r] = Yu[r]; Et[r] = Eu[r]; M1[r] = Mn[r]; X1[r] = Xn[r]; Y1[r] = Yn[r]; E1[r] = En[r]; }
-        // underflow guard, every 8 steps (a Q93 mismatch shrinks a state by 1e-10: 1e-80 between two checks).  Rows deep in
-        // the read carry far smaller numbers than the first rows, so every LANE keeps its own power-of-two scale: when its
-        // largest state has dropped below 2^-200 it is brought back to ~1 (exact), unless what the lane has collected for
-        // the result already outweighs anything its states can still add.
+        // underflow guard, every 8 steps: a lane's own states shrink by at most 2^-50 per step (see kScaleHi above), 2^-400
+        // between two checks.  Rows deep in the read carry far smaller numbers than the first rows, so every LANE keeps its
+        // own power-of-two scale: when its largest state has left 2^+-200 it is brought back to ~1 (exact), unless what the
+        // lane has collected for the result already outweighs anything its states can still add.  Growth between two checks
+        // comes only from the lane above and is handled where it arrives (the exchange above), not here.
         if ((d & 7) == 7) {
             double mx = fmax(fmax(fmax(M1[0], X1[0]), fmax(Y1[0], M1[1])), fmax(X1[1], Y1[1]));
             mx = fmax(mx, fmax(fmax(Mt[0], Xt[0]), fmax(fmax(Yt[0], Mt[1]), fmax(Xt[1], Yt[1]))));
@@ -199,7 +231,9 @@ __global__ void __launch_bounds__(64) vlr_realign_kernel(RealignArgs a) {
 // reference and the alt allele of one read are adjacent in a batch and share the read window — and, when both windows are
 // short, runs them side by side: lanes 0-31 pair 2w, lanes 32-63 pair 2w + 1.  Everything that was wave-uniform per pair
 // (lengths, band, owner lane, step count) is per half; the wave_shr:1 shifts cross the half boundary, so lane 32 takes the edge
-// value instead of lane 31's.  Same arithmetic per cell in the same order: results are bit-identical to the one-pair kernel.
+// value instead of lane 31's.  Same arithmetic per cell in the same order, and every per-lane decision of the scaling depends on
+// the lane's own values alone (never on what the other half made the wave-wide ballots say): results are bit-identical to the
+// one-pair kernel, which VLR_REALIGN_SINGLE selects (compared in tests/test_gpu_realign_guard.py).
 __global__ void __launch_bounds__(64) vlr_realign_kernel2(RealignArgs a) {
     const int64_t pair0 = 2 * (int64_t)blockIdx.x;
     if (pair0 >= a.n_pairs) return;
@@ -274,8 +308,15 @@ __global__ void __launch_bounds__(64) vlr_realign_kernel2(RealignArgs a) {
                 const double mass = ((M1[0] + M1[1]) + (X1[0] + X1[1])) + ((Y1[0] + Y1[1]) + (Mt[0] + Mt[1])) + ((Xt[0] + Xt[1]) + (Yt[0] + Yt[1])) + total;
                 if (mass == 0.0) scale = nb;
                 int dsc = scale - nb;
-                dsc = dsc > 1000 ? 1000 : dsc < -1000 ? -1000 : dsc;
-                const double f = __builtin_ldexp(1.0, dsc);
+                const int over = incoming_excess(fmax(fmax(Mu[0], Xu[0]), Yu[0]), dsc);
+                if (over) {  // (per lane) make room for what arrives
+                    const double g = down_factor(over);
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) { M1[r] *= g; X1[r] *= g; Y1[r] *= g; Mt[r] *= g; Xt[r] *= g; Yt[r] *= g; }
+                    total *= g;
+                    scale -= over; dsc -= over;
+                }
+                const double f = align_factor(dsc);
                 Mu[0] *= f; Xu[0] *= f; Yu[0] *= f;
             }
         }
@@ -438,8 +479,15 @@ __global__ void __launch_bounds__(64) vlr_homopoly_kernel(HomopolyArgs h) {
                                     ((P1[0] + P1[1]) + (Q1[0] + Q1[1])) + ((Pt[0] + Pt[1]) + (Qt[0] + Qt[1])) + total;
                 if (mass == 0.0) scale = nb;
                 int dsc = scale - nb;
-                dsc = dsc > 1000 ? 1000 : dsc < -1000 ? -1000 : dsc;
-                const double f = __builtin_ldexp(1.0, dsc);
+                const int over = incoming_excess(fmax(fmax(fmax(Mu[0], Xu[0]), Yu[0]), fmax(Pu0, Qu[0])), dsc);
+                if (over) {
+                    const double g = down_factor(over);
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) { M1[r] *= g; X1[r] *= g; Y1[r] *= g; P1[r] *= g; Q1[r] *= g; Mt[r] *= g; Xt[r] *= g; Yt[r] *= g; Pt[r] *= g; Qt[r] *= g; }
+                    total *= g;
+                    scale -= over; dsc -= over;
+                }
+                const double f = align_factor(dsc);
                 Mu[0] *= f; Xu[0] *= f; Yu[0] *= f; Pu0 *= f; Qu[0] *= f;
             }
         }
@@ -746,7 +794,7 @@ extern "C" int vlr_launch_pathhmm_kernel(const vlr_realign_batch_desc* b, double
     // PathHMMRealigner::new (realignment/mod.rs:560-584)
     const double gx = exp(b->gap[0]), gy = exp(b->gap[1]), gxe = exp(b->gap[2]), gye = exp(b->gap[3]);
     a.gap_x = b->gap[0]; a.gap_y = b->gap[1];
-    a.no_gap = log(1.0 - (gx + gy));
+    a.no_gap = log(fmax(0.0, 1.0 - (gx + gy)));
     a.close_x = log(1.0 - gxe); a.close_y = log(1.0 - gye);
     a.reopen_x = log(gxe + (1.0 - gxe) * gx); a.reopen_y = log(gye + (1.0 - gye) * gy);
     hipLaunchKernelGGL(vlr_pathhmm_kernel, dim3((unsigned)b->n_pairs), dim3(64), 0, (hipStream_t)stream, a);
@@ -763,11 +811,16 @@ extern "C" int vlr_launch_homopoly_kernel(const vlr_realign_batch_desc* b, const
     a.y_quals = b->y_quals; a.max_edit_dist = b->max_edit_dist; a.ln_prob = ln_prob;
     const double gx = exp(b->gap[0]), gy = exp(b->gap[1]), gxe = exp(b->gap[2]), gye = exp(b->gap[3]);
     a.pgx = gx; a.pgy = gy; a.pgxe = gxe; a.pgye = gye;
-    a.pn = 1.0 - (gx + gy); a.pnx = 1.0 - gxe; a.pny = 1.0 - gye;
+    a.pn = fmax(0.0, 1.0 - (gx + gy)); a.pnx = 1.0 - gxe; a.pny = 1.0 - gye;  // (fmax: a legal sum of one may round to just above it)
     for (int k = 0; k < 4; ++k) { h.hx[k] = exp(hop[k]); h.hy[k] = exp(hop[4 + k]); h.hxe[k] = exp(hop[8 + k]); h.hye[k] = exp(hop[12 + k]); }
     hipLaunchKernelGGL(vlr_homopoly_kernel, dim3((unsigned)b->n_pairs), dim3(64), 0, (hipStream_t)stream, h);
     return (int)hipGetLastError();
 }
+
+// which pair-HMM kernel the last vlr_launch_realign_kernel of this process launched: 1 = vlr_realign_kernel, 2 = vlr_realign_kernel2,
+// 0 = none yet (for the test that compares the two)
+static int realign_pairs_per_wave = 0;
+extern "C" int vlr_launch_realign_pairs_per_wave(void) { return realign_pairs_per_wave; }
 
 extern "C" int vlr_launch_realign_kernel(const vlr_realign_batch_desc* b, double* ln_prob, void* stream) {
     using namespace vlr;
@@ -778,8 +831,9 @@ extern "C" int vlr_launch_realign_kernel(const vlr_realign_batch_desc* b, double
     // GapParamCache of the pair HMM: P(no gap) = 1 - (P(gap x) + P(gap y)); leaving a gap state: 1 - P(extend)
     const double gx = exp(b->gap[0]), gy = exp(b->gap[1]), gxe = exp(b->gap[2]), gye = exp(b->gap[3]);
     a.pgx = gx; a.pgy = gy; a.pgxe = gxe; a.pgye = gye;
-    a.pn = 1.0 - (gx + gy); a.pnx = 1.0 - gxe; a.pny = 1.0 - gye;
+    a.pn = fmax(0.0, 1.0 - (gx + gy)); a.pnx = 1.0 - gxe; a.pny = 1.0 - gye;  // (fmax: a legal sum of one may round to just above it)
     static const bool single = getenv("VLR_REALIGN_SINGLE") != nullptr;  // tuning / comparison knob
+    realign_pairs_per_wave = single ? 1 : 2;
     if (single) hipLaunchKernelGGL(vlr_realign_kernel, dim3((unsigned)b->n_pairs), dim3(64), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(vlr_realign_kernel2, dim3((unsigned)((b->n_pairs + 1) / 2)), dim3(64), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();

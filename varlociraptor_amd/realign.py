@@ -115,6 +115,13 @@ def prob_related(batch: PairBatch, gap: Optional[GapParams] = None, device: int 
     return out
 
 
+def last_pairs_per_wave() -> int:
+    """Which kernel the last prob_related / DevicePairs.run of this process launched: 1 = one pair per wave (VLR_REALIGN_SINGLE), 2 = two, 0 = none yet."""
+    f = engine.lib().vlr_launch_realign_pairs_per_wave
+    f.restype = C.c_int
+    return int(f())
+
+
 def prob_best_path(batch: PairBatch, gap: Optional[GapParams] = None, device: int = 0) -> np.ndarray:
     """`fast` mode (PathHMMRealigner, realignment/mod.rs:547-678): ln of the best path probability over the minimal-edit-distance
     alignments of every pair (vlr_realign_fast_batch_host)."""
@@ -178,6 +185,19 @@ class DevicePairs:
         p = [t.data_ptr() for t in self.t]
         d = RealignDesc(self.n, p[0], p[1], p[2], p[3], p[4], p[5], gap.as_array())
         rc = L.vlr_realign_homopolymer_batch(device, C.byref(d), hop.as_array(), self.out.data_ptr(), stream)
+        if rc != 0:
+            raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+        return self.out
+
+    def run_fast(self, gap: Optional[GapParams] = None, device: int = 0, stream: int = 0):
+        """`fast` mode on the resident pairs (vlr_realign_fast_batch; the band is not read)."""
+        L = _bind()
+        L.vlr_realign_fast_batch.restype = C.c_int
+        L.vlr_realign_fast_batch.argtypes = [C.c_int, C.POINTER(RealignDesc), C.c_void_p, C.c_void_p]
+        gap = gap or GapParams()
+        p = [t.data_ptr() for t in self.t]
+        d = RealignDesc(self.n, p[0], p[1], p[2], p[3], p[4], None, gap.as_array())
+        rc = L.vlr_realign_fast_batch(device, C.byref(d), self.out.data_ptr(), stream)
         if rc != 0:
             raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
         return self.out
