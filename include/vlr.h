@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define VLR_ABI_VERSION 11  /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
+#define VLR_ABI_VERSION 12  /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
                              * 5: sharded device reader, calls-file parts, vlr_ingest_device_trim, CRC32 of BGZF members checked by both readers;
                              * 6: calls emission on the device — vlr_results.afd_text (FORMAT/AFD text), OBS text in the observation summaries,
                              *    vlr_obs_table_summaries;
@@ -43,7 +43,8 @@ extern "C" {
                              * 9: vlr_posterior_odds_keep, vlr_range_group_lse, vlr_calls_filter_odds, vlr_calls_mutational_burden
                              *    (`filter-calls posterior-odds`, `estimate mutational-burden`);
                              * 10: vlr_basepileup_* (SNV / MNV allele supports from BAM records);
-                             * 11: vlr_plan_fused_counters (the fused coefficient pass of the lean call kernel) */
+                             * 11: vlr_plan_fused_counters (the fused coefficient pass of the lean call kernel);
+                             * 12: vlr_indelpileup_* (indel allele supports from BAM records) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -593,6 +594,90 @@ int  vlr_basepileup_result(vlr_basepileup* s, vlr_basepileup_counts* out);
 int  vlr_basepileup_read(vlr_basepileup* s, vlr_basepileup_hit* hits, int64_t n);
 int  vlr_basepileup_tables(double call[256], double miscall[256]);
 void vlr_basepileup_close(vlr_basepileup* s);
+
+/* ------------------------------------------------------------------------------------------------
+ * Indel allele supports from BAM records: the single-locus part of Realigner::allele_support (variants/evidence/realignment/mod.rs:
+ * 161-424) for every (record, locus) pair of a BAM file, restated in varlociraptor_amd/readwindows.py (`evidence`).  The file goes
+ * through the device reader exactly as for vlr_basepileup_add_bam.  One thread per record decodes and validates the record (the decode
+ * and the flag rule of vlr_basepileup_*: unmapped / secondary / duplicate / QC-fail records dropped, supplementary ones kept), finds
+ * the loci its alignment with its soft clips overlaps, and computes the candidate region of each (Realigner::candidate_region,
+ * mod.rs:58-153, on rust-htslib's read_pos(pos, include_softclips = true, include_dels = true)); one wave per evidence then copies the
+ * read window (bases unpacked from the 4-bit SEQ, qualities), the ref allele window from the contig and the locus's alt allele window
+ * into the pair arrays of vlr_realign_batch_desc — pair 2e = (ref allele, read), pair 2e + 1 = (alt allele, read) —, and the engine's
+ * own kernels score them: the edit-distance kernel, band = distance + 4 (-1 where there is no hit), then the pair HMM of `mode`.
+ * Loci: n_loci candidates sorted by (ref_id, start) — ref_id = index of the contig in the BAM header —, [start, end) the locus
+ *   (the anchor base of a deletion / insertion, the REF allele's interval of a replacement), kind VLR_INDELPILEUP_DELETION / _INSERTION /
+ *   _REPLACEMENT (informational), and the alt allele window of locus k at alt_bases[alt_offset[k] .. alt_offset[k + 1]): it does
+ *   not depend on the read and is computed by the caller (varlociraptor_amd/readwindows.py: indel_locus).
+ * fasta_path: the reference (its .fai is required).  The contigs the loci lie on are read when a BAM file names them, upper-cased and
+ *   uploaded; a locus on a contig the FASTA lacks, or with a ref_id the BAM header does not have, is VLR_ERR_INVALID_ARGUMENT from
+ *   vlr_indelpileup_add_bam.  A record on a contig without loci, or with a reference id out of range, gives no hits.
+ * window: --realignment-window, 1 .. VLR_INDELPILEUP_MAX_WINDOW (a read window must fit the 128 bases of the kernels); the ref window
+ *   is window * 3 / 2 on either side of the breakpoint, clamped to the contig.
+ * mode: VLR_INDELPILEUP_EXACT (vlr_realign_batch's kernel), _FAST (vlr_realign_fast_batch's; the band is not computed and stays -1)
+ *   or _HOMOPOLYMER (vlr_realign_homopolymer_batch's; hop[16] as there, NULL otherwise).  gap[4] as in vlr_realign_batch_desc.
+ * hit_capacity, window_bytes: as for vlr_basepileup_open; nothing is written past the hit buffer, VLR_INDELPILEUP_OVERFLOW comes with
+ *   the exact needed_capacity, and the hits do not depend on window_bytes, bit for bit: a hit's place is a function of the record
+ *   order alone.
+ * keep_pairs != 0: the pair arrays are copied to the host as they are scored (for tests, and for callers that score them again in
+ *   another mode); vlr_indelpileup_read_pairs hands them out in hit order.
+ * A hit: ln_ref / ln_alt are the raw outputs of the pair-HMM kernel for the two pairs (the normalisation of mod.rs:359-385 is the
+ *   caller's: varlociraptor_amd/realign.py normalize_support), dist_ref / dist_alt the edit distances (-1: no hit), [ref_begin,
+ *   ref_begin + ref_len) the ref allele window on the contig, [read_begin, read_begin + read_len) the read window.  status
+ *   VLR_INDELPILEUP_HIT_NO_OVERLAP: the candidate region does not overlap the read (mod.rs:186-199: supports ln 0.5 / ln 0.5);
+ *   VLR_INDELPILEUP_HIT_LEADING_REFSKIP: read_pos fails on a CIGAR that begins with N.  Both come with empty windows, two empty pairs,
+ *   ln -inf and distance -1.  An evidence whose read window is empty is not reported.
+ * vlr_indelpileup_result: the counts, the status word (VLR_INDELPILEUP_BAD_RECORD as VLR_BASEPILEUP_BAD_RECORD: the record gives no hits
+ *   and is never followed, the records in front of it are scored), x_bytes / y_bytes: the bytes of the pair arrays, seconds: [0] file
+ *   read, [1] upload + inflate, [2] record split, [3] count + scan kernels, [4] fill + gather kernels, [5] edit-distance + band kernels,
+ *   [6] the pair-HMM kernels alone, [7] collect kernel and the copy of kept pairs, [8] hits to the host and the locus-major order,
+ *   [9] total of vlr_indelpileup_add_bam, [10] inflate kernels alone.
+ * vlr_indelpileup_read copies the n_hits hits: locus-major, in record order within a locus; `record` counts the records of all files
+ *   given to the session so far.  vlr_indelpileup_read_pairs (keep_pairs sessions): x_offset / y_offset [n_pairs + 1], x_bases
+ *   [x_bytes], y_bases / y_quals [y_bytes], band [n_pairs], n_pairs = 2 * n_hits, in hit order.
+ * NOT part of this path (Realigner::allele_support has them): the read-inferred third allele, alt_variants, merged multi-locus
+ *   regions, homopolymer_indel_len, SI:Z strand information over an interval, mate merging with the insert-size term. */
+#define VLR_INDELPILEUP_MAX_WINDOW 64
+enum { VLR_INDELPILEUP_DELETION = 0, VLR_INDELPILEUP_INSERTION = 1, VLR_INDELPILEUP_REPLACEMENT = 2 };
+enum { VLR_INDELPILEUP_EXACT = 0, VLR_INDELPILEUP_FAST = 1, VLR_INDELPILEUP_HOMOPOLYMER = 2 };
+/* status word of a session */
+#define VLR_INDELPILEUP_BAD_RECORD (1u << 0)
+#define VLR_INDELPILEUP_OVERFLOW   (1u << 1)
+#define VLR_INDELPILEUP_GUARD_DAMAGED (1u << 2)  /* the guard words behind the hit buffer changed: a defect, never expected */
+/* status byte of a hit */
+#define VLR_INDELPILEUP_HIT_NO_OVERLAP      (1u << 0)
+#define VLR_INDELPILEUP_HIT_LEADING_REFSKIP (1u << 1)
+typedef struct {
+    double   ln_ref, ln_alt;       /* ln P(read window | ref allele), ln P(read window | alt allele): raw kernel outputs               */
+    uint64_t record;               /* ordinal of the record                                                                            */
+    int64_t  ref_begin;            /* start of the ref allele window on the contig                                                     */
+    uint32_t locus;                /* index of the locus in the arrays given at open                                                   */
+    uint32_t ref_len;              /* bases of the ref allele window                                                                   */
+    uint32_t read_begin, read_len; /* the read window                                                                                  */
+    int32_t  dist_ref, dist_alt;   /* edit distance of the read window against the ref / alt allele window; -1 = no hit                */
+    uint16_t flag;                 /* the record's FLAG & (0x1 paired | 0x10 reverse | 0x40 first in template)                         */
+    uint8_t  mapq;
+    uint8_t  status;               /* VLR_INDELPILEUP_HIT_*                                                                            */
+    uint8_t  pad[4];
+} vlr_indelpileup_hit;
+typedef struct vlr_indelpileup vlr_indelpileup;
+typedef struct {
+    int64_t  n_hits, n_records, n_rejected, n_pairs;
+    int64_t  x_bytes, y_bytes;     /* bytes of the pair arrays (allele windows; read windows)                                          */
+    uint64_t status;               /* VLR_INDELPILEUP_BAD_RECORD | VLR_INDELPILEUP_OVERFLOW | VLR_INDELPILEUP_GUARD_DAMAGED            */
+    int64_t  needed_capacity;      /* hits the input produces (== n_hits unless VLR_INDELPILEUP_OVERFLOW)                              */
+    int64_t  first_bad_record;     /* ordinal of the first bad record, -1 = none                                                       */
+    double   seconds[12];
+} vlr_indelpileup_counts;
+int  vlr_indelpileup_open(int device, const char* fasta_path, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int64_t* end,
+                          const uint8_t* kind, const uint64_t* alt_offset, const uint8_t* alt_bases, int window, int mode, const double gap[4],
+                          const double* hop, int keep_pairs, int64_t hit_capacity, int64_t window_bytes, vlr_indelpileup** out);
+int  vlr_indelpileup_add_bam(vlr_indelpileup* s, const char* bam_path);
+int  vlr_indelpileup_result(vlr_indelpileup* s, vlr_indelpileup_counts* out);
+int  vlr_indelpileup_read(vlr_indelpileup* s, vlr_indelpileup_hit* hits, int64_t n);
+int  vlr_indelpileup_read_pairs(vlr_indelpileup* s, uint32_t* x_offset, uint8_t* x_bases, int64_t x_bytes, uint32_t* y_offset, uint8_t* y_bases,
+                                uint8_t* y_quals, int64_t y_bytes, int32_t* band, int64_t n_pairs);
+void vlr_indelpileup_close(vlr_indelpileup* s);
 
 /* The whole of `varlociraptor filter-calls control-fdr` (/root/reference/src/filtration/fdr.rs:36-158, record typing
  * src/utils/collect_variants.rs:44-304, probability sums and the filtering pass src/utils/mod.rs:169-374): read the calls BCF

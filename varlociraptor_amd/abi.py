@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_SAMPLES = 16
 N_BIAS = 6
 
@@ -173,3 +173,30 @@ class BasePileupCounts(C.Structure):
     """vlr_basepileup_counts"""
     _fields_ = [("n_hits", C.c_int64), ("n_records", C.c_int64), ("n_rejected", C.c_int64), ("n_needs_realign", C.c_int64),
                 ("status", C.c_uint64), ("needed_capacity", C.c_int64), ("first_bad_record", C.c_int64), ("seconds", C.c_double * 8)]
+
+
+# vlr_indelpileup_* (indel allele supports from BAM records, ABI 12)
+INDELPILEUP_MAX_WINDOW = 64
+INDELPILEUP_DELETION, INDELPILEUP_INSERTION, INDELPILEUP_REPLACEMENT = 0, 1, 2
+INDELPILEUP_EXACT, INDELPILEUP_FAST, INDELPILEUP_HOMOPOLYMER = 0, 1, 2
+INDELPILEUP_BAD_RECORD, INDELPILEUP_OVERFLOW, INDELPILEUP_GUARD_DAMAGED = 1, 2, 4
+INDELPILEUP_HIT_NO_OVERLAP, INDELPILEUP_HIT_LEADING_REFSKIP = 1, 2
+
+
+class IndelPileupHit(C.Structure):
+    """vlr_indelpileup_hit"""
+    _fields_ = [("ln_ref", C.c_double), ("ln_alt", C.c_double), ("record", C.c_uint64), ("ref_begin", C.c_int64), ("locus", C.c_uint32),
+                ("ref_len", C.c_uint32), ("read_begin", C.c_uint32), ("read_len", C.c_uint32), ("dist_ref", C.c_int32), ("dist_alt", C.c_int32),
+                ("flag", C.c_uint16), ("mapq", C.c_uint8), ("status", C.c_uint8), ("pad", C.c_uint8 * 4)]
+
+
+INDELPILEUP_HIT_DTYPE = np.dtype([("ln_ref", "<f8"), ("ln_alt", "<f8"), ("record", "<u8"), ("ref_begin", "<i8"), ("locus", "<u4"), ("ref_len", "<u4"),
+                                  ("read_begin", "<u4"), ("read_len", "<u4"), ("dist_ref", "<i4"), ("dist_alt", "<i4"), ("flag", "<u2"), ("mapq", "u1"),
+                                  ("status", "u1"), ("pad", "u1", (4,))])
+assert C.sizeof(IndelPileupHit) == 64 and INDELPILEUP_HIT_DTYPE.itemsize == 64
+
+
+class IndelPileupCounts(C.Structure):
+    """vlr_indelpileup_counts"""
+    _fields_ = [("n_hits", C.c_int64), ("n_records", C.c_int64), ("n_rejected", C.c_int64), ("n_pairs", C.c_int64), ("x_bytes", C.c_int64),
+                ("y_bytes", C.c_int64), ("status", C.c_uint64), ("needed_capacity", C.c_int64), ("first_bad_record", C.c_int64), ("seconds", C.c_double * 12)]

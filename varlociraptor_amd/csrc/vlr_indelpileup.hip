@@ -1,0 +1,629 @@
+// vlr_indelpileup.hip — indel allele supports from BAM records for gfx950 (vlr_indelpileup_*, include/vlr.h): the evidence text of
+// vlr_indelpileup.h over every record of a BAM file streamed through the device reader (vlr_bamstream.h), the window gather, the
+// engine's own edit-distance and pair-HMM kernels (vlr_realign.hip, through their vlr_launch_* entry points) on the gathered pairs, and
+// the host driver of the session.
+//
+// Per chunk of split records:
+//   indelpileup_count_kernel    one record per thread: decode and validate (vlr_bp::decode), find the loci the alignment with its clips
+//                               overlaps, candidate region of each -> evidences and x / y bytes of the record (nothing else is written);
+//                               rejected and bad records go to integer counters (sums and a minimum: order-independent)
+//   indelpileup_scan_kernel     one workgroup per count array: exclusive prefix sums -> offsets, the chunk's totals
+//   indelpileup_fill_kernel     one record per thread: the same text again writes the evidence descriptors (the hits, scores unset) at
+//                               hits[hit0 + ev_off[i] ...) and the x_offset / y_offset entries of pairs 2e (ref allele, read) and 2e + 1
+//                               (alt allele, read) from the scanned byte offsets
+//   indelpileup_gather_kernel   one wave per evidence: its lanes copy the read window (bases unpacked from the 4-bit SEQ, qualities; once
+//                               per pair), the ref allele window from the contig and the locus's alt window, lane-contiguous — the only
+//                               pass that moves more than a few bytes per item
+//   vlr_launch_edit_kernel, indelpileup_band_kernel (band = dist + 4, -1 without a hit; not in fast mode), then the pair HMM of the mode
+//   indelpileup_collect_kernel  one evidence per thread: ln_ref / ln_alt / dist_ref / dist_alt into the hits
+// A hit's place and a pair's bytes are functions of the record order alone: no atomics decide a position, and how the file was cut
+// into feeds and chunks (window_bytes) cannot change the output.  The pair offsets are uint32: a chunk whose x or y bytes pass
+// kPairByteLimit is processed in record sub-ranges cut at the scanned offsets.  The hits leave the device record-major;
+// vlr_indelpileup_result puts them locus-major with a stable counting sort on the host.
+//
+// Bounds: see vlr_indelpileup.h.  The fill pass runs only when all evidences of the chunk fit the hit buffer and writes hits[k] only for
+// k < capacity; guard words behind the buffer are checked at the end.  The pair buffers are sized from the scanned totals before the
+// fill pass, and the gather pass writes window k of a pair only below the pair's own length.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/vlr.h"
+#include "vlr_gpuio.h"
+#include "vlr_bamstream.h"
+#include "vlr_indelpileup.h"
+
+static_assert(sizeof(vlr_indelpileup_hit) == 64, "hit layout");
+
+extern "C" int vlr_launch_edit_kernel(const vlr_realign_batch_desc* b, int32_t* dist, int32_t* end, int32_t* n_hits, void* stream);
+extern "C" int vlr_launch_realign_kernel(const vlr_realign_batch_desc* b, double* ln_prob, void* stream);
+extern "C" int vlr_launch_pathhmm_kernel(const vlr_realign_batch_desc* b, double* ln_prob, void* stream);
+extern "C" int vlr_launch_homopoly_kernel(const vlr_realign_batch_desc* b, const double* hop, double* ln_prob, void* stream);
+
+namespace vlr_ip {
+
+enum Counter { C_REJECTED, C_BAD, C_FIRST_BAD, C_N };
+enum { K_EV = 0, K_X = 1, K_Y = 2, K_N = 3 };   // the three counts of a record
+constexpr int kThreads = 256;
+constexpr int kScanThreads = 1024;
+constexpr int kEditBand = 4;                 // pairhmm.rs:20
+constexpr size_t kGuardHits = 4;             // guard words behind the hit buffer: kGuardHits * sizeof(hit) bytes of kGuardByte
+constexpr int kGuardByte = 0xA5;
+constexpr uint64_t kPairByteLimit = 1ull << 31;
+
+// where the windows of an evidence come from (chunk-local, one per evidence of the sub-range)
+struct Src {
+    uint64_t seq, qual;   // offsets of the record's packed SEQ and its QUAL from the chunk's base
+    uint32_t l_seq, pad;
+};
+
+__global__ __launch_bounds__(kThreads) void indelpileup_count_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0, Loci L,
+                                                                     int window, uint64_t* __restrict__ cnt, int64_t stride, unsigned long long* __restrict__ counters) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t o = starts[i], end = starts[i + 1];
+    const RecEvidence r = record_evidence(L, base + o, end - o, rec0 + (uint64_t)i, window, nullptr, 0);
+    cnt[K_EV * stride + i] = r.n_ev;
+    cnt[K_X * stride + i] = r.x_bytes;
+    cnt[K_Y * stride + i] = r.y_bytes;
+    if (r.cls == REC_REJECTED) atomicAdd(&counters[C_REJECTED], 1ull);
+    if (r.cls == REC_BAD) { atomicAdd(&counters[C_BAD], 1ull); atomicMin(&counters[C_FIRST_BAD], (unsigned long long)(rec0 + (uint64_t)i)); }
+}
+
+// workgroup b scans count array b: thread t sums the slice [t * per, (t + 1) * per), the sums are scanned in LDS, then the slice's offsets written
+__global__ __launch_bounds__(kScanThreads) void indelpileup_scan_kernel(const uint64_t* __restrict__ cnt_all, int64_t n, int64_t stride, uint64_t* __restrict__ off_all,
+                                                                        uint64_t* __restrict__ total) {
+    __shared__ uint64_t s[2][kScanThreads];
+    const uint64_t* cnt = cnt_all + (int64_t)blockIdx.x * stride;
+    uint64_t* off = off_all + (int64_t)blockIdx.x * stride;
+    const int t = (int)threadIdx.x;
+    const int64_t per = (n + kScanThreads - 1) / kScanThreads;
+    const int64_t lo = std::min<int64_t>((int64_t)t * per, n), hi = std::min<int64_t>(lo + per, n);
+    uint64_t sum = 0;
+    for (int64_t i = lo; i < hi; ++i) sum += cnt[i];
+    s[0][t] = sum;
+    __syncthreads();
+    int cur = 0;
+    for (int d = 1; d < kScanThreads; d <<= 1) {
+        s[cur ^ 1][t] = s[cur][t] + (t >= d ? s[cur][t - d] : 0ull);
+        cur ^= 1;
+        __syncthreads();
+    }
+    uint64_t run = s[cur][t] - sum;   // exclusive
+    for (int64_t i = lo; i < hi; ++i) { off[i] = run; run += cnt[i]; }
+    if (t == kScanThreads - 1) total[blockIdx.x] = s[cur][t];
+}
+
+// records [i0, i1) of the chunk: their evidences are [e0, e0 + n_ev) of the chunk and go to hits[hit0 + (e - e0)], their pair bytes
+// start at x0 / y0 of the chunk's scanned offsets
+struct Range {
+    int64_t i0, i1;
+    uint64_t e0, x0, y0, n_ev, x_bytes, y_bytes;
+};
+
+__global__ __launch_bounds__(kThreads) void indelpileup_fill_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, uint64_t rec0, Loci L, int window,
+                                                                    const uint64_t* __restrict__ cnt, const uint64_t* __restrict__ off, int64_t stride, Range g,
+                                                                    uint64_t hit0, uint64_t capacity, vlr_indelpileup_hit* __restrict__ hits, Src* __restrict__ src,
+                                                                    uint32_t* __restrict__ x_offset, uint32_t* __restrict__ y_offset, int32_t* __restrict__ band) {
+    const int64_t i = g.i0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == g.i0) { x_offset[2 * g.n_ev] = (uint32_t)g.x_bytes; y_offset[2 * g.n_ev] = (uint32_t)g.y_bytes; }
+    if (i >= g.i1 || cnt[K_EV * stride + i] == 0) return;
+    const uint64_t e = off[K_EV * stride + i] - g.e0;   // first evidence of the record within the range
+    const uint64_t first = hit0 + e;
+    if (first >= capacity) return;
+    const uint64_t o = starts[i], end = starts[i + 1];
+    const RecEvidence r = record_evidence(L, base + o, end - o, rec0 + (uint64_t)i, window, hits + first, capacity - first);
+    uint64_t x = off[K_X * stride + i] - g.x0, y = off[K_Y * stride + i] - g.y0;
+    for (uint32_t k = 0; k < r.n_ev && e + k < g.n_ev && first + k < capacity; ++k) {
+        const vlr_indelpileup_hit h = hits[first + k];
+        const uint64_t alt = h.status ? 0ull : L.alt_off[h.locus + 1] - L.alt_off[h.locus];
+        const uint64_t p = 2 * (e + k);
+        x_offset[p] = (uint32_t)x; x += h.ref_len;
+        x_offset[p + 1] = (uint32_t)x; x += alt;
+        y_offset[p] = (uint32_t)y; y += h.read_len;
+        y_offset[p + 1] = (uint32_t)y; y += h.read_len;
+        band[p] = -1; band[p + 1] = -1;
+        src[e + k] = Src{o + r.seq_off, o + r.qual_off, r.l_seq, 0u};
+    }
+}
+
+// One wave per evidence: lane-contiguous copies of its four windows
+__global__ __launch_bounds__(kThreads) void indelpileup_gather_kernel(const uint8_t* __restrict__ base, uint64_t n_ev, const vlr_indelpileup_hit* __restrict__ hits, Loci L,
+                                                                      const uint8_t* const* __restrict__ ctg, const uint8_t* __restrict__ alt_bases,
+                                                                      const Src* __restrict__ src, const uint32_t* __restrict__ x_offset, const uint32_t* __restrict__ y_offset,
+                                                                      uint8_t* __restrict__ x_bases, uint8_t* __restrict__ y_bases, uint8_t* __restrict__ y_quals) {
+    const uint64_t e = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (e >= n_ev) return;
+    const vlr_indelpileup_hit h = hits[e];
+    if (h.status || (int64_t)h.locus >= L.n) return;
+    const int32_t ref_id = L.ref_id[h.locus];
+    const uint8_t* contig = ctg[ref_id];
+    const int64_t contig_len = L.ctg_len[ref_id];
+    const Src s = src[e];
+    const uint32_t x_ref = x_offset[2 * e], x_alt = x_offset[2 * e + 1], x_end = x_offset[2 * e + 2];
+    const uint32_t y_ref = y_offset[2 * e], y_alt = y_offset[2 * e + 1], y_end = y_offset[2 * e + 2];
+    for (uint32_t k = lane; k < h.ref_len && x_ref + k < x_alt; k += 64) x_bases[x_ref + k] = window_byte(WB_REF_BASE, contig, contig_len, h.ref_begin, k);
+    const uint8_t* alt = alt_bases + L.alt_off[h.locus];
+    const uint32_t alt_len = (uint32_t)(L.alt_off[h.locus + 1] - L.alt_off[h.locus]);
+    for (uint32_t k = lane; k < alt_len && x_alt + k < x_end; k += 64) x_bases[x_alt + k] = alt[k];
+    for (uint32_t k = lane; k < h.read_len && y_ref + k < y_alt && y_alt + k < y_end; k += 64) {
+        const uint8_t b = window_byte(WB_READ_BASE, base + s.seq, s.l_seq, h.read_begin, k);
+        const uint8_t q = window_byte(WB_READ_QUAL, base + s.qual, s.l_seq, h.read_begin, k);
+        y_bases[y_ref + k] = b; y_quals[y_ref + k] = q;
+        y_bases[y_alt + k] = b; y_quals[y_alt + k] = q;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void indelpileup_band_kernel(const int32_t* __restrict__ dist, int64_t n_pairs, int32_t* __restrict__ band) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n_pairs) band[p] = dist[p] >= 0 ? dist[p] + kEditBand : -1;
+}
+
+__global__ __launch_bounds__(kThreads) void indelpileup_collect_kernel(const double* __restrict__ lnp, const int32_t* __restrict__ dist, uint64_t n_ev, uint64_t hit0,
+                                                                       uint64_t capacity, vlr_indelpileup_hit* __restrict__ hits) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_ev || hit0 + e >= capacity) return;
+    vlr_indelpileup_hit* h = hits + hit0 + e;
+    h->ln_ref = lnp[2 * e]; h->ln_alt = lnp[2 * e + 1];
+    h->dist_ref = dist[2 * e]; h->dist_alt = dist[2 * e + 1];
+}
+
+struct FaiEntry { uint64_t len, off, lb, lw; };
+
+}  // namespace vlr_ip
+
+struct vlr_indelpileup {
+    int device = 0;
+    int window = 64, mode = VLR_INDELPILEUP_EXACT;
+    bool keep_pairs = false;
+    double gap[4] = {0, 0, 0, 0};
+    double hop[16];
+    int64_t n_loci = 0;
+    uint64_t capacity = 0;
+    size_t window_bytes = (size_t)64 << 20;
+    uint64_t pair_byte_limit = vlr_ip::kPairByteLimit;
+    std::string fasta;
+    std::map<std::string, vlr_ip::FaiEntry> fai;
+    std::vector<int32_t> h_ref_id;                                          // of the loci
+    std::map<std::string, std::pair<uint8_t*, int64_t>> contigs;            // uploaded contigs by name
+    // device state
+    int32_t* d_ref_id = nullptr; int64_t *d_start = nullptr, *d_end = nullptr; uint64_t* d_alt_off = nullptr; uint8_t* d_altb = nullptr;
+    const uint8_t** d_ctg = nullptr; int64_t* d_ctg_len = nullptr; size_t ctg_cap = 0;
+    vlr_indelpileup_hit* d_hits = nullptr;
+    uint64_t *d_cnt = nullptr, *d_off = nullptr; size_t rec_cap = 0;        // [K_N][rec_cap]
+    unsigned long long* d_counters = nullptr; uint64_t* d_total = nullptr;
+    vlr_ip::Src* d_src = nullptr; uint32_t *d_xoff = nullptr, *d_yoff = nullptr; int32_t *d_band = nullptr, *d_dist = nullptr; double* d_lnp = nullptr; size_t ev_cap = 0;
+    uint8_t *d_xb = nullptr, *d_yb = nullptr, *d_yq = nullptr; size_t x_cap = 0, y_cap = 0;
+    vlr_ip::Loci loci{};
+    // host state
+    uint64_t n_total = 0;        // evidences the input produced so far
+    uint64_t n_records = 0;      // records of the files given so far
+    uint64_t x_total = 0, y_total = 0;
+    uint64_t status = 0;
+    bool overflow = false;
+    int64_t trunc_record = -1;   // a file ended inside this record
+    std::vector<vlr_indelpileup_hit> hits;
+    std::vector<uint64_t> perm;  // hits[k] is evidence perm[k] of the record-major order
+    // kept pairs, record-major: per pair its lengths, the bytes one behind the other
+    std::vector<uint32_t> p_xlen, p_ylen; std::vector<int32_t> p_band; std::vector<uint8_t> p_xb, p_yb, p_yq;
+    bool collected = false;
+    uint64_t counters[vlr_ip::C_N] = {0, 0, ~0ull};
+    double t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+namespace vlr_ip {
+using vlr_bam::bfail;
+using vlr_bam::now_s;
+
+#define IP_HIP_OK(call)                                                                          \
+    do {                                                                                          \
+        hipError_t e_ = (call);                                                                   \
+        if (e_ != hipSuccess) return bfail(e_ == hipErrorOutOfMemory ? VLR_ERR_OUT_OF_MEMORY : VLR_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+template <class T> int upload(T*& d, const T* h, size_t n) {
+    IP_HIP_OK(hipMalloc((void**)&d, std::max<size_t>(n, 1) * sizeof(T)));
+    if (n) IP_HIP_OK(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return VLR_OK;
+}
+
+// device buffers only grow (the stream is idle when this runs: every stage below ends with a synchronisation)
+template <class T> int grow(T*& p, size_t& cap, size_t need) {
+    if (need <= cap) return VLR_OK;
+    if (p) (void)hipFree((void*)p);
+    p = nullptr; cap = 0;
+    const size_t ncap = need + need / 4 + 1024;
+    IP_HIP_OK(hipMalloc((void**)&p, ncap * sizeof(T)));
+    cap = ncap;
+    return VLR_OK;
+}
+
+int read_fai(vlr_indelpileup* s) {
+    const std::string path = s->fasta + ".fai";
+    FILE* f = fopen(path.c_str(), "r");
+    if (!f) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: no .fai index (index the reference with samtools faidx)", s->fasta.c_str());
+    char line[4096];
+    while (fgets(line, sizeof line, f)) {
+        char name[2048];
+        unsigned long long a, b, c, d;
+        if (sscanf(line, "%2047[^\t]\t%llu\t%llu\t%llu\t%llu", name, &a, &b, &c, &d) == 5 && c > 0 && d >= c) s->fai[name] = {a, b, c, d};
+    }
+    fclose(f);
+    return VLR_OK;
+}
+
+// the bases of one contig through the .fai, upper-cased (the reference's buffer hands out upper case), on the device
+int load_contig(vlr_indelpileup* s, const std::string& name, const char* bam, std::pair<uint8_t*, int64_t>& out) {
+    auto it = s->contigs.find(name);
+    if (it != s->contigs.end()) { out = it->second; return VLR_OK; }
+    auto e = s->fai.find(name);
+    if (e == s->fai.end()) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: contig %s (of %s) is missing from the reference", s->fasta.c_str(), name.c_str(), bam);
+    const FaiEntry& x = e->second;
+    std::vector<uint8_t> seq(x.len);
+    if (x.len) {
+        const uint64_t nlines = (x.len - 1) / x.lb + 1;
+        const uint64_t raw_n = (nlines - 1) * x.lw + (x.len - (nlines - 1) * x.lb);
+        std::vector<uint8_t> raw(raw_n);
+        FILE* f = fopen(s->fasta.c_str(), "rb");
+        if (!f) return bfail(VLR_ERR_INVALID_ARGUMENT, "cannot open %s", s->fasta.c_str());
+        const bool ok = fseeko(f, (off_t)x.off, SEEK_SET) == 0 && fread(raw.data(), 1, raw_n, f) == raw_n;
+        fclose(f);
+        if (!ok) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: contig %s shorter than its .fai entry", s->fasta.c_str(), name.c_str());
+        for (uint64_t l = 0, k = 0; l < nlines; ++l) {
+            const uint64_t m = std::min<uint64_t>(x.lb, x.len - k);
+            memcpy(seq.data() + k, raw.data() + l * x.lw, m);
+            k += m;
+        }
+        for (auto& c : seq) if (c >= 'a' && c <= 'z') c = (uint8_t)(c - 32);
+    }
+    uint8_t* d = nullptr;
+    IP_HIP_OK(hipMalloc((void**)&d, x.len + 1));
+    if (x.len) IP_HIP_OK(hipMemcpy(d, seq.data(), x.len, hipMemcpyHostToDevice));
+    out = s->contigs[name] = {d, (int64_t)x.len};
+    return VLR_OK;
+}
+
+// the contig table of a file: entry k = contig k of its header when a locus lies on it
+int on_header(vlr_indelpileup* s, const std::vector<std::string>& names, const char* path) {
+    const size_t n = names.size();
+    std::vector<const uint8_t*> ctg(n + 1, nullptr);
+    std::vector<int64_t> len(n + 1, -1);
+    for (int32_t id : s->h_ref_id) {
+        if ((size_t)id >= n) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: a locus lies on reference id %d, the header has %zu contigs", path, (int)id, n);
+        if (len[(size_t)id] >= 0) continue;
+        std::pair<uint8_t*, int64_t> c;
+        const int rc = load_contig(s, names[(size_t)id], path, c);
+        if (rc != VLR_OK) return rc;
+        ctg[(size_t)id] = c.first; len[(size_t)id] = c.second;
+    }
+    if (n + 1 > s->ctg_cap) {
+        size_t c1 = s->ctg_cap, c2 = s->ctg_cap;
+        int rc;
+        if ((rc = grow(s->d_ctg, c1, n + 1)) != VLR_OK || (rc = grow(s->d_ctg_len, c2, n + 1)) != VLR_OK) return rc;
+        s->ctg_cap = std::min(c1, c2);
+    }
+    IP_HIP_OK(hipMemcpy((void*)s->d_ctg, ctg.data(), (n + 1) * sizeof(uint8_t*), hipMemcpyHostToDevice));
+    IP_HIP_OK(hipMemcpy(s->d_ctg_len, len.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    s->loci.n_refs = (int64_t)n;
+    s->loci.ctg_len = s->d_ctg_len;
+    return VLR_OK;
+}
+
+int sync_stage(hipStream_t st, double& t, double& t0) {
+    IP_HIP_OK(hipStreamSynchronize(st));
+    IP_HIP_OK(hipGetLastError());
+    const double now = now_s();
+    t += now - t0;
+    t0 = now;
+    return VLR_OK;
+}
+
+// fill, gather, score and collect the evidences of one record sub-range
+int run_range(vlr_indelpileup* s, const uint8_t* d_base, const uint64_t* d_starts, uint64_t rec0, const Range& g, hipStream_t st) {
+    int rc;
+    const size_t ne = (size_t)g.n_ev, np = 2 * ne;
+    if (ne > s->ev_cap) {
+        size_t c = s->ev_cap, p[5] = {0, 0, 0, 0, 0};   // (0: the arrays below are all allocated anew)
+        if ((rc = grow(s->d_src, c, ne)) != VLR_OK) return rc;
+        s->ev_cap = 0;
+        const size_t pairs = 2 * c + 1;   // two pairs per evidence, one more offset
+        if ((rc = grow(s->d_xoff, p[0], pairs)) != VLR_OK || (rc = grow(s->d_yoff, p[1], pairs)) != VLR_OK || (rc = grow(s->d_band, p[2], pairs)) != VLR_OK ||
+            (rc = grow(s->d_dist, p[3], pairs)) != VLR_OK || (rc = grow(s->d_lnp, p[4], pairs)) != VLR_OK)
+            return rc;
+        s->ev_cap = c;
+    }
+    if ((rc = grow(s->d_xb, s->x_cap, (size_t)g.x_bytes + 8)) != VLR_OK) return rc;
+    if ((size_t)g.y_bytes + 8 > s->y_cap) {
+        size_t c1 = s->y_cap, c2 = s->y_cap;
+        if ((rc = grow(s->d_yb, c1, (size_t)g.y_bytes + 8)) != VLR_OK || (rc = grow(s->d_yq, c2, (size_t)g.y_bytes + 8)) != VLR_OK) return rc;
+        s->y_cap = std::min(c1, c2);
+    }
+    double t0 = now_s();
+    const int64_t stride = (int64_t)s->rec_cap;
+    const unsigned rec_blocks = (unsigned)((g.i1 - g.i0 + kThreads - 1) / kThreads);
+    const uint64_t hit0 = s->n_total;
+    hipLaunchKernelGGL(indelpileup_fill_kernel, dim3(rec_blocks), dim3(kThreads), 0, st, d_base, d_starts, rec0, s->loci, s->window, s->d_cnt, s->d_off, stride, g, hit0,
+                       s->capacity, s->d_hits, s->d_src, s->d_xoff, s->d_yoff, s->d_band);
+    const unsigned waves_per_block = kThreads / 64;
+    hipLaunchKernelGGL(indelpileup_gather_kernel, dim3((unsigned)((ne + waves_per_block - 1) / waves_per_block)), dim3(kThreads), 0, st, d_base, (uint64_t)ne,
+                       s->d_hits + hit0, s->loci, s->d_ctg, s->d_altb, s->d_src, s->d_xoff, s->d_yoff, s->d_xb, s->d_yb, s->d_yq);
+    if ((rc = sync_stage(st, s->t[4], t0)) != VLR_OK) return rc;
+    vlr_realign_batch_desc b;
+    b.n_pairs = (int64_t)np;
+    b.x_offset = s->d_xoff; b.x_bases = s->d_xb; b.y_offset = s->d_yoff; b.y_bases = s->d_yb; b.y_quals = s->d_yq;
+    b.max_edit_dist = s->d_band;
+    for (int k = 0; k < 4; ++k) b.gap[k] = s->gap[k];
+    const unsigned pair_blocks = (unsigned)((np + kThreads - 1) / kThreads);
+    hipError_t e = (hipError_t)vlr_launch_edit_kernel(&b, s->d_dist, nullptr, nullptr, (void*)st);
+    if (e != hipSuccess) return bfail(VLR_ERR_HIP, "edit-distance kernel launch: %s", hipGetErrorString(e));
+    if (s->mode != VLR_INDELPILEUP_FAST) hipLaunchKernelGGL(indelpileup_band_kernel, dim3(pair_blocks), dim3(kThreads), 0, st, s->d_dist, (int64_t)np, s->d_band);
+    if ((rc = sync_stage(st, s->t[5], t0)) != VLR_OK) return rc;
+    if (s->mode == VLR_INDELPILEUP_FAST) e = (hipError_t)vlr_launch_pathhmm_kernel(&b, s->d_lnp, (void*)st);
+    else if (s->mode == VLR_INDELPILEUP_HOMOPOLYMER) e = (hipError_t)vlr_launch_homopoly_kernel(&b, s->hop, s->d_lnp, (void*)st);
+    else e = (hipError_t)vlr_launch_realign_kernel(&b, s->d_lnp, (void*)st);
+    if (e != hipSuccess) return bfail(VLR_ERR_HIP, "realign kernel launch: %s", hipGetErrorString(e));
+    if ((rc = sync_stage(st, s->t[6], t0)) != VLR_OK) return rc;
+    hipLaunchKernelGGL(indelpileup_collect_kernel, dim3((unsigned)((ne + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, s->d_lnp, s->d_dist, (uint64_t)ne, hit0, s->capacity,
+                       s->d_hits);
+    if (s->keep_pairs) {
+        std::vector<uint32_t> xo(np + 1), yo(np + 1);
+        const size_t at = s->p_xlen.size(), ax = s->p_xb.size(), ay = s->p_yb.size();
+        s->p_xlen.resize(at + np); s->p_ylen.resize(at + np); s->p_band.resize(at + np);
+        s->p_xb.resize(ax + (size_t)g.x_bytes); s->p_yb.resize(ay + (size_t)g.y_bytes); s->p_yq.resize(ay + (size_t)g.y_bytes);
+        IP_HIP_OK(hipMemcpyAsync(xo.data(), s->d_xoff, (np + 1) * 4, hipMemcpyDeviceToHost, st));
+        IP_HIP_OK(hipMemcpyAsync(yo.data(), s->d_yoff, (np + 1) * 4, hipMemcpyDeviceToHost, st));
+        IP_HIP_OK(hipMemcpyAsync(s->p_band.data() + at, s->d_band, np * 4, hipMemcpyDeviceToHost, st));
+        if (g.x_bytes) IP_HIP_OK(hipMemcpyAsync(s->p_xb.data() + ax, s->d_xb, (size_t)g.x_bytes, hipMemcpyDeviceToHost, st));
+        if (g.y_bytes) IP_HIP_OK(hipMemcpyAsync(s->p_yb.data() + ay, s->d_yb, (size_t)g.y_bytes, hipMemcpyDeviceToHost, st));
+        if (g.y_bytes) IP_HIP_OK(hipMemcpyAsync(s->p_yq.data() + ay, s->d_yq, (size_t)g.y_bytes, hipMemcpyDeviceToHost, st));
+        IP_HIP_OK(hipStreamSynchronize(st));
+        for (size_t p = 0; p < np; ++p) { s->p_xlen[at + p] = xo[p + 1] - xo[p]; s->p_ylen[at + p] = yo[p + 1] - yo[p]; }
+    }
+    if ((rc = sync_stage(st, s->t[7], t0)) != VLR_OK) return rc;
+    s->n_total += g.n_ev;
+    s->x_total += g.x_bytes;
+    s->y_total += g.y_bytes;
+    return VLR_OK;
+}
+
+int run_chunk(vlr_indelpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
+    const uint8_t* d_base; const uint64_t* d_starts;
+    int rc = vlr_dev_file_split_view(df, &d_base, &d_starts);
+    if (rc != VLR_OK) return rc;
+    if ((size_t)n > s->rec_cap) {
+        IP_HIP_OK(hipStreamSynchronize(st));
+        if (s->d_cnt) (void)hipFree(s->d_cnt);
+        if (s->d_off) (void)hipFree(s->d_off);
+        s->d_cnt = nullptr; s->d_off = nullptr; s->rec_cap = 0;
+        const size_t cap = (size_t)n + (size_t)n / 4 + 1024;
+        IP_HIP_OK(hipMalloc((void**)&s->d_cnt, K_N * cap * 8));
+        IP_HIP_OK(hipMalloc((void**)&s->d_off, K_N * cap * 8));
+        s->rec_cap = cap;
+    }
+    double t0 = now_s();
+    const int64_t stride = (int64_t)s->rec_cap;
+    const unsigned blocks = (unsigned)((n + kThreads - 1) / kThreads);
+    const uint64_t rec0 = s->n_records;
+    hipLaunchKernelGGL(indelpileup_count_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->loci, s->window, s->d_cnt, stride, s->d_counters);
+    hipLaunchKernelGGL(indelpileup_scan_kernel, dim3(K_N), dim3(kScanThreads), 0, st, s->d_cnt, n, stride, s->d_off, s->d_total);
+    uint64_t total[K_N] = {0, 0, 0};
+    IP_HIP_OK(hipMemcpyAsync(total, s->d_total, sizeof total, hipMemcpyDeviceToHost, st));
+    if ((rc = sync_stage(st, s->t[3], t0)) != VLR_OK) return rc;
+    s->n_records += (uint64_t)n;
+    if (total[K_EV] == 0) return VLR_OK;
+    if (s->overflow || s->n_total + total[K_EV] > s->capacity) {   // counted, not written: the caller opens again with needed_capacity
+        s->overflow = true;
+        s->n_total += total[K_EV];
+        return VLR_OK;
+    }
+    if (total[K_X] <= s->pair_byte_limit && total[K_Y] <= s->pair_byte_limit)
+        return run_range(s, d_base, d_starts, rec0, Range{0, n, 0, 0, 0, total[K_EV], total[K_X], total[K_Y]}, st);
+    // sub-ranges of records whose pair bytes fit the uint32 offsets, cut at the scanned offsets
+    std::vector<uint64_t> off((size_t)K_N * (size_t)n);
+    for (int k = 0; k < K_N; ++k) IP_HIP_OK(hipMemcpy(off.data() + (size_t)k * (size_t)n, s->d_off + (size_t)k * s->rec_cap, (size_t)n * 8, hipMemcpyDeviceToHost));
+    auto at = [&](int k, int64_t i) { return i < n ? off[(size_t)k * (size_t)n + (size_t)i] : total[k]; };
+    for (int64_t i0 = 0; i0 < n;) {
+        int64_t i1 = i0 + 1;
+        while (i1 < n && at(K_X, i1 + 1) - at(K_X, i0) <= s->pair_byte_limit && at(K_Y, i1 + 1) - at(K_Y, i0) <= s->pair_byte_limit) ++i1;
+        const Range g{i0, i1, at(K_EV, i0), at(K_X, i0), at(K_Y, i0), at(K_EV, i1) - at(K_EV, i0), at(K_X, i1) - at(K_X, i0), at(K_Y, i1) - at(K_Y, i0)};
+        if (g.x_bytes >= (1ull << 32) || g.y_bytes >= (1ull << 32))
+            return bfail(VLR_ERR_UNSUPPORTED, "record %llu: the windows of its evidences take 4 GiB or more", (unsigned long long)(rec0 + (uint64_t)i0));
+        if (g.n_ev && (rc = run_range(s, d_base, d_starts, rec0, g, st)) != VLR_OK) return rc;
+        i0 = i1;
+    }
+    return VLR_OK;
+}
+
+}  // namespace vlr_ip
+
+extern "C" {
+
+int vlr_indelpileup_open(int device, const char* fasta_path, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int64_t* end, const uint8_t* kind,
+                         const uint64_t* alt_offset, const uint8_t* alt_bases, int window, int mode, const double gap[4], const double* hop, int keep_pairs,
+                         int64_t hit_capacity, int64_t window_bytes, vlr_indelpileup** out) {
+    using namespace vlr_ip;
+    if (!out || !fasta_path || !gap || n_loci < 0 || n_loci > 0x7fffffff || hit_capacity < 0 || window_bytes < 0 ||
+        (n_loci > 0 && (!ref_id || !start || !end || !kind || !alt_offset || !alt_bases)))
+        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: bad argument");
+    *out = nullptr;
+    if (window < 1 || window > VLR_INDELPILEUP_MAX_WINDOW)
+        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: window %d outside 1 .. %d (a read window must fit the 128 bases of the kernels)", window,
+                     VLR_INDELPILEUP_MAX_WINDOW);
+    if (mode != VLR_INDELPILEUP_EXACT && mode != VLR_INDELPILEUP_FAST && mode != VLR_INDELPILEUP_HOMOPOLYMER)
+        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: unknown mode %d", mode);
+    for (int k = 0; k < 4; ++k)
+        if (gap[k] != gap[k] || gap[k] > 0.0) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: gap[%d] is not a log probability", k);
+    if (std::exp(gap[0]) + std::exp(gap[1]) > 1.0 + 1e-12) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: P(gap in x) + P(gap in y) exceeds one");
+    if (mode == VLR_INDELPILEUP_HOMOPOLYMER) {
+        if (!hop) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: null hop parameters");
+        for (int k = 0; k < 16; ++k)
+            if (!(hop[k] <= 0.0)) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: hop parameter %d is not a ln probability", k);
+    }
+    int64_t max_len = 0;
+    for (int64_t k = 0; k < n_loci; ++k) {
+        if (kind[k] > VLR_INDELPILEUP_REPLACEMENT || ref_id[k] < 0 || start[k] < 0 || end[k] <= start[k] || alt_offset[k + 1] < alt_offset[k] || (k == 0 && alt_offset[0] != 0))
+            return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: locus %lld: kind %d, [%lld, %lld), or its alt window's offsets", (long long)k, (int)kind[k],
+                         (long long)start[k], (long long)end[k]);
+        if (k > 0 && (ref_id[k] < ref_id[k - 1] || (ref_id[k] == ref_id[k - 1] && start[k] < start[k - 1])))
+            return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: loci are not sorted by (ref_id, start) at %lld", (long long)k);
+        max_len = std::max(max_len, end[k] - start[k]);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || ndev <= device) return bfail(VLR_ERR_NO_DEVICE, "no HIP device %d (the engine has no CPU path)", device);
+    IP_HIP_OK(hipSetDevice(device));
+    vlr_indelpileup* s = new vlr_indelpileup();
+    s->device = device;
+    s->window = window; s->mode = mode; s->keep_pairs = keep_pairs != 0;
+    for (int k = 0; k < 4; ++k) s->gap[k] = gap[k];
+    for (int k = 0; k < 16; ++k) s->hop[k] = hop && mode == VLR_INDELPILEUP_HOMOPOLYMER ? hop[k] : -HUGE_VAL;
+    s->n_loci = n_loci;
+    s->capacity = (uint64_t)hit_capacity;
+    if (window_bytes > 0) s->window_bytes = (size_t)window_bytes;
+    // tuning / test knob: the pair bytes a record sub-range may hold (the uint32 offsets need at most 2^31)
+    if (const char* v = getenv("VLR_INDELPILEUP_PAIR_BYTES")) {
+        const unsigned long long x = strtoull(v, nullptr, 10);
+        if (x >= 1 && x <= kPairByteLimit) s->pair_byte_limit = x;
+    }
+    s->fasta = fasta_path;
+    s->h_ref_id.assign(ref_id, ref_id + n_loci);
+    const uint64_t zero = 0;
+    const size_t hit_bytes = ((size_t)s->capacity + kGuardHits) * sizeof(vlr_indelpileup_hit);
+    int rc = read_fai(s);
+    auto step = [&](int r) { if (rc == VLR_OK) rc = r; };
+    step(upload(s->d_ref_id, ref_id, (size_t)n_loci));
+    step(upload(s->d_start, start, (size_t)n_loci));
+    step(upload(s->d_end, end, (size_t)n_loci));
+    step(n_loci ? upload(s->d_alt_off, alt_offset, (size_t)n_loci + 1) : upload(s->d_alt_off, &zero, 1));
+    step(upload(s->d_altb, alt_bases, n_loci ? (size_t)alt_offset[n_loci] : 0));
+    step(upload(s->d_counters, (const unsigned long long*)s->counters, (size_t)C_N));
+    auto hip = [&](hipError_t e, const char* what) { if (rc == VLR_OK && e != hipSuccess) rc = bfail(e == hipErrorOutOfMemory ? VLR_ERR_OUT_OF_MEMORY : VLR_ERR_HIP, "%s: %s", what, hipGetErrorString(e)); };
+    if (rc == VLR_OK) hip(hipMalloc((void**)&s->d_total, K_N * 8), "hipMalloc");
+    if (rc == VLR_OK) hip(hipMalloc((void**)&s->d_hits, hit_bytes), "hipMalloc of the hit buffer");
+    if (rc == VLR_OK) hip(hipMemset((void*)(s->d_hits + s->capacity), kGuardByte, kGuardHits * sizeof(vlr_indelpileup_hit)), "hipMemset");
+    if (rc != VLR_OK) { vlr_indelpileup_close(s); return rc; }
+    s->loci = Loci{n_loci, s->d_ref_id, s->d_start, s->d_end, s->d_alt_off, max_len, 0, nullptr};
+    *out = s;
+    return VLR_OK;
+}
+
+int vlr_indelpileup_add_bam(vlr_indelpileup* s, const char* bam_path) {
+    using namespace vlr_ip;
+    if (!s || !bam_path) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_add_bam: null");
+    if (s->collected) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_add_bam: the result was already read");
+    if (s->trunc_record >= 0) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_add_bam: the file before ended inside a record");
+    if (hipSetDevice(s->device) != hipSuccess) return bfail(VLR_ERR_HIP, "hipSetDevice(%d) failed", s->device);
+    vlr_bam::BamStream b;
+    b.device = s->device;
+    b.window = &s->window_bytes;
+    b.t_read = &s->t[0]; b.t_feed = &s->t[1]; b.t_split = &s->t[2]; b.t_inflate = &s->t[10]; b.t_total = &s->t[9];
+    b.on_header = [s, bam_path](const std::vector<std::string>& names) { return on_header(s, names, bam_path); };
+    b.on_chunk = [s](vlr_dev_file* df, int64_t n, uint64_t, const std::vector<std::string>&, const char*, void* st) { return run_chunk(s, df, n, (hipStream_t)st); };
+    // a file that ends inside a record: malformed input, reported in the status word; the records in front of it are scored
+    b.on_truncated = [s](uint64_t) { s->trunc_record = (int64_t)s->n_records; return (int)VLR_OK; };
+    return vlr_bam::stream_bam(b, bam_path);
+}
+
+int vlr_indelpileup_result(vlr_indelpileup* s, vlr_indelpileup_counts* r) {
+    using namespace vlr_ip;
+    if (!s || !r) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_result: null");
+    IP_HIP_OK(hipSetDevice(s->device));
+    if (!s->collected) {
+        const double t0 = now_s();
+        IP_HIP_OK(hipMemcpy(s->counters, s->d_counters, sizeof s->counters, hipMemcpyDeviceToHost));
+        uint8_t guard[kGuardHits * sizeof(vlr_indelpileup_hit)];
+        IP_HIP_OK(hipMemcpy(guard, (const void*)(s->d_hits + s->capacity), sizeof guard, hipMemcpyDeviceToHost));
+        for (uint8_t g : guard) if (g != (uint8_t)kGuardByte) s->status |= VLR_INDELPILEUP_GUARD_DAMAGED;
+        if (s->counters[C_BAD] || s->trunc_record >= 0) s->status |= VLR_INDELPILEUP_BAD_RECORD;
+        if (s->overflow) s->status |= VLR_INDELPILEUP_OVERFLOW;
+        else if (s->n_total) {
+            // record-major on the device -> locus-major, record order kept within a locus: a stable counting sort
+            std::vector<vlr_indelpileup_hit> raw((size_t)s->n_total);
+            IP_HIP_OK(hipMemcpy(raw.data(), s->d_hits, raw.size() * sizeof(vlr_indelpileup_hit), hipMemcpyDeviceToHost));
+            std::vector<uint64_t> first((size_t)s->n_loci + 1, 0);
+            for (const auto& h : raw) if ((int64_t)h.locus < s->n_loci) ++first[(size_t)h.locus + 1];
+            for (size_t k = 0; k < (size_t)s->n_loci; ++k) first[k + 1] += first[k];
+            s->hits.resize((size_t)first[(size_t)s->n_loci]);
+            s->perm.resize(s->hits.size());
+            for (size_t k = 0; k < raw.size(); ++k) {
+                const auto& h = raw[k];
+                if ((int64_t)h.locus >= s->n_loci) continue;
+                const size_t at = (size_t)first[h.locus]++;
+                s->hits[at] = h;
+                s->perm[at] = k;
+            }
+        }
+        s->t[8] += now_s() - t0;
+        s->collected = true;
+    }
+    r->n_hits = (int64_t)s->hits.size();
+    r->n_records = (int64_t)s->n_records;
+    r->n_rejected = (int64_t)s->counters[C_REJECTED];
+    r->n_pairs = 2 * r->n_hits;
+    r->x_bytes = s->overflow ? 0 : (int64_t)s->x_total;
+    r->y_bytes = s->overflow ? 0 : (int64_t)s->y_total;
+    r->status = s->status;
+    r->needed_capacity = (int64_t)s->n_total;
+    r->first_bad_record = s->counters[C_BAD] ? (int64_t)s->counters[C_FIRST_BAD] : -1;
+    if (s->trunc_record >= 0 && (r->first_bad_record < 0 || s->trunc_record < r->first_bad_record)) r->first_bad_record = s->trunc_record;
+    for (int k = 0; k < 12; ++k) r->seconds[k] = s->t[k];
+    return VLR_OK;
+}
+
+int vlr_indelpileup_read(vlr_indelpileup* s, vlr_indelpileup_hit* hits, int64_t n) {
+    using namespace vlr_ip;
+    if (!s || !s->collected) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_read: call vlr_indelpileup_result first");
+    if (n != (int64_t)s->hits.size() || (n > 0 && !hits)) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_read: size differs from vlr_indelpileup_result");
+    if (n) memcpy(hits, s->hits.data(), (size_t)n * sizeof(vlr_indelpileup_hit));
+    return VLR_OK;
+}
+
+int vlr_indelpileup_read_pairs(vlr_indelpileup* s, uint32_t* x_offset, uint8_t* x_bases, int64_t x_bytes, uint32_t* y_offset, uint8_t* y_bases, uint8_t* y_quals,
+                               int64_t y_bytes, int32_t* band, int64_t n_pairs) {
+    using namespace vlr_ip;
+    if (!s || !s->collected) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_read_pairs: call vlr_indelpileup_result first");
+    if (!s->keep_pairs) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_read_pairs: the session was opened without keep_pairs");
+    if (s->overflow) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_read_pairs: the hit buffer overflowed");
+    const size_t np = 2 * s->hits.size();
+    if (n_pairs != (int64_t)np || x_bytes != (int64_t)s->x_total || y_bytes != (int64_t)s->y_total || !x_offset || !y_offset || (np && !band) ||
+        (x_bytes && !x_bases) || (y_bytes && (!y_bases || !y_quals)))
+        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_read_pairs: sizes differ from vlr_indelpileup_result");
+    if (s->x_total >= (1ull << 32) || s->y_total >= (1ull << 32)) return bfail(VLR_ERR_UNSUPPORTED, "vlr_indelpileup_read_pairs: the pair bytes do not fit 32-bit offsets");
+    if (s->p_xlen.size() != 2 * (size_t)s->n_total) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_read_pairs: kept pairs and hits differ");
+    // record-major starts of every kept pair, then the pairs in hit order
+    std::vector<uint64_t> xs(s->p_xlen.size() + 1, 0), ys(s->p_ylen.size() + 1, 0);
+    for (size_t p = 0; p < s->p_xlen.size(); ++p) { xs[p + 1] = xs[p] + s->p_xlen[p]; ys[p + 1] = ys[p] + s->p_ylen[p]; }
+    uint64_t x = 0, y = 0;
+    for (size_t k = 0; k < s->hits.size(); ++k)
+        for (size_t j = 0; j < 2; ++j) {
+            const size_t from = 2 * (size_t)s->perm[k] + j, to = 2 * k + j;
+            const uint32_t xl = s->p_xlen[from], yl = s->p_ylen[from];
+            if (x + xl > (uint64_t)x_bytes || y + yl > (uint64_t)y_bytes) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_read_pairs: kept pairs and sizes differ");
+            x_offset[to] = (uint32_t)x; y_offset[to] = (uint32_t)y;
+            band[to] = s->p_band[from];
+            if (xl) memcpy(x_bases + x, s->p_xb.data() + xs[from], xl);
+            if (yl) { memcpy(y_bases + y, s->p_yb.data() + ys[from], yl); memcpy(y_quals + y, s->p_yq.data() + ys[from], yl); }
+            x += xl; y += yl;
+        }
+    x_offset[np] = (uint32_t)x; y_offset[np] = (uint32_t)y;
+    return VLR_OK;
+}
+
+void vlr_indelpileup_close(vlr_indelpileup* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    void* p[] = {s->d_ref_id, s->d_start, s->d_end, s->d_alt_off, s->d_altb, (void*)s->d_ctg, s->d_ctg_len, s->d_hits, s->d_cnt, s->d_off, s->d_counters, s->d_total,
+                 s->d_src, s->d_xoff, s->d_yoff, s->d_band, s->d_dist, s->d_lnp, s->d_xb, s->d_yb, s->d_yq};
+    for (void* q : p) if (q) (void)hipFree(q);
+    for (auto& c : s->contigs) if (c.second.first) (void)hipFree(c.second.first);
+    delete s;
+}
+
+}  // extern "C"

@@ -16,8 +16,11 @@ per-read supports that come out of the edit-distance and pair-HMM kernels (`real
   alt allele windows                          types/deletion.rs:117-137, types/insertion.rs:92-113, types/replacement.rs:73-103
   Realigner::allele_support (single locus)    realignment/mod.rs:161-424: edit-distance hit -> banded pair HMM -> normalisation
 
-NOT mirrored (callers must know): fragments — a read pair is two single-end observations here, without the insert-size support of
-deletion.rs:232-258 —, alternative variants at the locus, the read-inferred third allele (mod.rs:311-349), `prob_sample_alt`.
+NOT mirrored (callers must know): fragments — a read pair is two single-end observations here, without mate merging and the
+insert-size support of deletion.rs:232-258 —, alternative variants at the locus (`alt_variants`), the read-inferred third allele
+(mod.rs:311-349), merged multi-locus regions (mod.rs:201-240), `homopolymer_indel_len`, SI:Z strand information over an interval,
+`prob_sample_alt`.  `evidence` / `device_supports` (the device path: csrc/vlr_indelpileup.hip, vlr_indelpileup_* of include/vlr.h) take
+the reference's record filter and keep no-overlap reads; `evidence_windows` keeps its older filter.
 SNVs / MNVs are scored base by base in the reference, without realignment: that path is varlociraptor_amd/basecalls.py.  A minimal
 BAM / FASTA reader is included (BGZF members are gzip members): the reference reads through htslib.
 """
@@ -281,3 +284,186 @@ def allele_supports(reads: list, alt_allele: bytes, gap=None, hop=None, device: 
     for k in range(n):
         pr[k], pa[k] = realign.normalize_support(float(lnp[2 * k]), float(lnp[2 * k + 1]))
     return pa, pr, pb
+
+
+# ---------------------------------------------------------------------------------------------- the device path (vlr_indelpileup_*)
+NO_OVERLAP, LEADING_REFSKIP = 1, 2     # Evidence.status / the status byte of a vlr_indelpileup_hit (abi.INDELPILEUP_HIT_*)
+MODES = {"exact": 0, "fast": 1, "homopolymer": 2}
+
+
+@dataclass
+class Evidence:
+    """One (record, locus) pair the realignment sees.  status 0: the windows to realign; NO_OVERLAP: the candidate region does not
+    overlap (supports ln 0.5 / ln 0.5, mod.rs:186-199); LEADING_REFSKIP: read_pos fails on a CIGAR that begins with N.  A status other
+    than 0 comes with empty windows and intervals."""
+    record: int                        # ordinal of the record
+    status: int
+    read_interval: Tuple[int, int]
+    ref_interval: Tuple[int, int]
+    read_window: bytes
+    quals: bytes
+    ref_allele: bytes                  # the ref allele window, upper case
+    flag: int                          # FLAG & (0x1 | 0x10 | 0x40)
+    mapq: int
+
+    def key(self):
+        return (self.record, self.status, self.read_interval, self.ref_interval, self.flag, self.mapq)
+
+
+def evidence(records: List[BamRecord], ref_seq: bytes, locus: IndelLocus, window: int = 64, first_ordinal: int = 0,
+             ref_id: Optional[int] = None) -> List[Evidence]:
+    """What csrc/vlr_indelpileup.h computes per record, restated: every valid record (basecalls.is_valid_record, sample.rs:281-286:
+    unmapped, secondary, duplicate and QC-fail records dropped, supplementary ones kept) on the locus's contig (`ref_id`, the index
+    in the BAM header; None = every record lies on it) whose alignment with its soft clips overlaps [start, end), with the windows
+    of its candidate region.  Differs from evidence_windows in the filter and in keeping no-overlap reads."""
+    from . import realign
+    from .basecalls import is_valid_record
+    out = []
+    n = len(ref_seq)
+    for k, r in enumerate(records):
+        if not is_valid_record(r.flag) or r.ref_id < 0 or r.pos < 0 or (ref_id is not None and r.ref_id != ref_id):
+            continue
+        if not overlaps(r, locus.start, locus.end):
+            continue
+        flag = r.flag & (0x1 | 0x10 | 0x40)
+        try:
+            reg = candidate_region(r, locus.start, locus.end, n, window)
+        except ValueError:
+            out.append(Evidence(first_ordinal + k, LEADING_REFSKIP, (0, 0), (0, 0), b"", b"", b"", flag, r.mapq))
+            continue
+        if not reg.overlap:
+            out.append(Evidence(first_ordinal + k, NO_OVERLAP, (0, 0), (0, 0), b"", b"", b"", flag, r.mapq))
+            continue
+        ro, re_ = reg.read_interval
+        if re_ - ro < 1:
+            continue
+        rb, re2 = reg.ref_interval
+        rb = min(rb, re2)          # (a breakpoint behind the contig's end: an empty window)
+        out.append(Evidence(first_ordinal + k, 0, (ro, re_), (rb, re2), r.seq[ro:re_].upper(), bytes(r.qual[ro:re_]),
+                            realign.ref_allele(ref_seq, rb, re2).upper(), flag, r.mapq))
+    return out
+
+
+class IndelPileupError(ValueError):
+    pass
+
+
+@dataclass
+class PairArrays:
+    """the pair arrays of a session opened with keep_pairs, in hit order: the layout of realign.PairBatch.arrays()"""
+    x_offset: "object"
+    x_bases: "object"
+    y_offset: "object"
+    y_bases: "object"
+    y_quals: "object"
+    band: "object"
+
+    def arrays(self):
+        return self.x_offset, self.x_bases, self.y_offset, self.y_bases, self.y_quals, self.band
+
+
+def device_hits(bams, fasta: str, ref_id, loci: List[IndelLocus], mode: str = "exact", gap=None, hop=None, window: int = 64, device: int = 0,
+                hit_capacity: Optional[int] = None, window_bytes: int = 0, keep_pairs: bool = False, retry: bool = True):
+    """(hits as a numpy array of abi.INDELPILEUP_HIT_DTYPE, locus-major; abi.IndelPileupCounts; PairArrays or None) from the kernels.
+    `bams`: one path or a list of them (one session, records counted through).  `loci` with their `ref_id` (index of the contig in the
+    BAM header), sorted by (ref_id, start).  An overflow of `hit_capacity` is retried once with the needed capacity unless retry=False
+    (then the counts carry INDELPILEUP_OVERFLOW and the array is empty)."""
+    import ctypes as C
+    import numpy as np
+    from . import abi, engine, realign
+    L = engine.bind_indelpileup()
+    if mode not in MODES:
+        raise ValueError("mode must be one of %s" % ", ".join(MODES))
+    n = len(loci)
+    kinds = {"deletion": abi.INDELPILEUP_DELETION, "insertion": abi.INDELPILEUP_INSERTION, "replacement": abi.INDELPILEUP_REPLACEMENT}
+    rid = np.array(list(ref_id), np.int32)
+    start = np.array([l.start for l in loci], np.int64)
+    end = np.array([l.end for l in loci], np.int64)
+    kind = np.array([kinds[l.kind] for l in loci], np.uint8)
+    alt_off = np.zeros(n + 1, np.uint64)
+    alt_off[1:] = np.cumsum([len(l.alt_allele) for l in loci])
+    altb = np.frombuffer(b"".join(bytes(l.alt_allele) for l in loci) or b"\0", np.uint8).copy()
+    g = (gap or realign.GapParams()).as_array()
+    if mode == "homopolymer":
+        h_ = (hop or realign.HopParams()).as_array()
+    else:
+        h_ = None
+    cap = int(hit_capacity) if hit_capacity is not None else max(1 << 16, 64 * n)
+    paths = [bams] if isinstance(bams, str) else list(bams)
+    while True:
+        h = C.c_void_p()
+        engine._check(L.vlr_indelpileup_open(int(device), fasta.encode(), n, rid.ctypes.data, start.ctypes.data, end.ctypes.data, kind.ctypes.data,
+                                             alt_off.ctypes.data, altb.ctypes.data, int(window), MODES[mode], g, h_, int(bool(keep_pairs)), cap,
+                                             int(window_bytes), C.byref(h)))
+        try:
+            for p in paths:
+                engine._check(L.vlr_indelpileup_add_bam(h, p.encode()))
+            res = abi.IndelPileupCounts()
+            engine._check(L.vlr_indelpileup_result(h, C.byref(res)))
+            if res.status & abi.INDELPILEUP_GUARD_DAMAGED:
+                raise IndelPileupError("the guard words behind the hit buffer changed")
+            if res.status & abi.INDELPILEUP_OVERFLOW and retry:
+                cap = int(res.needed_capacity)
+                retry = False
+                continue
+            hits = np.zeros(int(res.n_hits), abi.INDELPILEUP_HIT_DTYPE)
+            engine._check(L.vlr_indelpileup_read(h, hits.ctypes.data, int(res.n_hits)))
+            pairs = None
+            if keep_pairs and not res.status & abi.INDELPILEUP_OVERFLOW:
+                npairs, nx, ny = int(res.n_pairs), int(res.x_bytes), int(res.y_bytes)
+                xo, yo = np.zeros(npairs + 1, np.uint32), np.zeros(npairs + 1, np.uint32)
+                xb, yb, qb = np.zeros(max(nx, 1), np.uint8), np.zeros(max(ny, 1), np.uint8), np.zeros(max(ny, 1), np.uint8)
+                band = np.zeros(npairs, np.int32)
+                engine._check(L.vlr_indelpileup_read_pairs(h, xo.ctypes.data, xb.ctypes.data, nx, yo.ctypes.data, yb.ctypes.data, qb.ctypes.data, ny,
+                                                           band.ctypes.data, npairs))
+                pairs = PairArrays(xo, xb, yo, yb, qb, band)
+            return hits, res, pairs
+        finally:
+            L.vlr_indelpileup_close(h)
+
+
+@dataclass
+class LocusSupports:
+    """the evidences of one candidate: its locus, its hits (abi.INDELPILEUP_HIT_DTYPE, record order) and the normalised supports"""
+    locus: IndelLocus
+    hits: "object"
+    prob_alt: "object"
+    prob_ref: "object"
+
+
+def device_supports(bam: str, fasta: str, candidates, mode: str = "exact", gap=None, hop=None, window: int = 64, device: int = 0,
+                    hit_capacity: Optional[int] = None, window_bytes: int = 0, keep_pairs: bool = False):
+    """Per candidate (contig, 0-based position, REF, ALT), in the order given, the supports of every evidence from BAM records on the
+    device (vlr_indelpileup_*): (ln P(read | alt), ln P(read | ref)) normalised as mod.rs:359-385, (ln 0.5, ln 0.5) for a read without
+    overlap.  An overflow of the hit buffer is retried once with the needed capacity.  A record whose CIGAR begins with a reference
+    skip raises the ValueError read_pos raises.  Returns a list of LocusSupports (with keep_pairs: (list, PairArrays in the
+    session's locus order))."""
+    import numpy as np
+    from . import abi, alignprops, realign
+    seqs = read_fasta(fasta)
+    contigs, _ = alignprops.bam_header(alignprops.inflate_bgzf(bam), bam)
+    tid = {name: k for k, (name, _) in enumerate(contigs)}
+    loci, rid = [], []
+    for c, pos, ref, alt in candidates:
+        if c not in tid or c not in seqs:
+            raise ValueError("contig %s is not in the BAM header and the reference" % c)
+        loci.append(indel_locus(seqs[c].upper(), int(pos), ref, alt, window))
+        rid.append(tid[c])
+    order = sorted(range(len(loci)), key=lambda k: (rid[k], loci[k].start))
+    arr, res, pairs = device_hits(bam, fasta, [rid[k] for k in order], [loci[k] for k in order], mode, gap, hop, window, device, hit_capacity, window_bytes,
+                                  keep_pairs)
+    if res.status & abi.INDELPILEUP_BAD_RECORD:
+        raise IndelPileupError("%s: record %d is malformed" % (bam, int(res.first_bad_record)))
+    if res.status & abi.INDELPILEUP_OVERFLOW:
+        raise IndelPileupError("%s: %d hits do not fit the hit buffer" % (bam, int(res.needed_capacity)))
+    if (arr["status"] & LEADING_REFSKIP).any():
+        raise ValueError("leading reference skip")
+    out: List[Optional[LocusSupports]] = [None] * len(loci)
+    first = np.searchsorted(arr["locus"], np.arange(len(loci) + 1))
+    for j, k in enumerate(order):
+        hs = arr[first[j]:first[j + 1]]
+        pa, pr = np.empty(len(hs)), np.empty(len(hs))
+        for i, h in enumerate(hs):
+            pr[i], pa[i] = realign.normalize_support(float(h["ln_ref"]), float(h["ln_alt"]))
+        out[k] = LocusSupports(loci[k], hs, pa, pr)
+    return (out, pairs) if keep_pairs else out
