@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define VLR_ABI_VERSION 12  /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
+#define VLR_ABI_VERSION 13  /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
                              * 5: sharded device reader, calls-file parts, vlr_ingest_device_trim, CRC32 of BGZF members checked by both readers;
                              * 6: calls emission on the device — vlr_results.afd_text (FORMAT/AFD text), OBS text in the observation summaries,
                              *    vlr_obs_table_summaries;
@@ -44,7 +44,8 @@ extern "C" {
                              *    (`filter-calls posterior-odds`, `estimate mutational-burden`);
                              * 10: vlr_basepileup_* (SNV / MNV allele supports from BAM records);
                              * 11: vlr_plan_fused_counters (the fused coefficient pass of the lean call kernel);
-                             * 12: vlr_indelpileup_* (indel allele supports from BAM records) */
+                             * 12: vlr_indelpileup_* (indel allele supports from BAM records);
+                             * 13: vlr_fragpileup_* (fragment observations of SNV / MNV candidates from BAM records) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -678,6 +679,97 @@ int  vlr_indelpileup_read(vlr_indelpileup* s, vlr_indelpileup_hit* hits, int64_t
 int  vlr_indelpileup_read_pairs(vlr_indelpileup* s, uint32_t* x_offset, uint8_t* x_bases, int64_t x_bytes, uint32_t* y_offset, uint8_t* y_bases,
                                 uint8_t* y_quals, int64_t y_bytes, int32_t* band, int64_t n_pairs);
 void vlr_indelpileup_close(vlr_indelpileup* s);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fragment observations of SNV / MNV candidates from BAM records: Variant::extract_observations (variants/types/mod.rs:283-407) with
+ * Snv / Mnv::is_valid_evidence and allele_support, Evidence::read_orientation / softclipped / len / is_paired, min_mapq and
+ * major_read_position (read_observation.rs), restated in varlociraptor_amd/fragments.py.  Two stages:
+ *   member pass (vlr_fragpileup_add_bam, per chunk of the device reader): one thread per record; a valid record (the flag rule of
+ *     vlr_basepileup_*) whose START lies in [start - window, end) of a locus on its contig is a member of that locus — the test is on
+ *     the start position alone, as rust-htslib's RecordBuffer::fetch keeps records.  A member carries the record's features (FLAG, MAPQ,
+ *     l_seq, soft-clip test, orientation from RO:Z or the flags, whether it has an XA:Z tag) and, where the record encloses the locus,
+ *     its allele support (the scoring of vlr_basepileup_*).  Members and the QNAMEs of records with members accumulate on the device
+ *     at places that are prefix sums over the record order.
+ *   fragment pass (vlr_fragpileup_result): the members are brought locus-major; one workgroup per locus sorts its members in LDS by
+ *     (QNAME bytes, record ordinal), takes per run of equal names the first record as `left` and the last one that the
+ *     first-and-last-in-template condition (mod.rs:329-334) does not skip as `right`, drops pairs with a MAPQ of 0 and fragments of
+ *     which no record encloses the locus, merges the supports (AlleleSupport::merge), drops a merged strand of None, and writes the
+ *     observations in name order; the mode of the read positions of alt-supporting observations (calc_major_feature) sets
+ *     VLR_FRAGPILEUP_READPOS_MAJOR.  A locus with more than VLR_FRAGPILEUP_MAX_MEMBERS members comes back with
+ *     VLR_FRAGPILEUP_LOCUS_TOO_MANY_MEMBERS and no observations: the caller finishes it.
+ *   The XA:Z entries of a member record (ExactAltLoci::from, read_observation.rs:167-210) go into a key pool as (64-bit FNV-1a of the
+ *     contig bytes, position bucketed to 10 x max_read_len: locus_to_bucket) — two contig names that collide in 64 bits would be merged —;
+ *     the fragment pass takes the mode of the keys of all observations of a locus (major_alt_locus) and writes each observation's
+ *     alt_locus class (ReadObservation::process).  A locus whose observations carry more than VLR_FRAGPILEUP_MAX_MEMBERS keys comes
+ *     back with VLR_FRAGPILEUP_LOCUS_TOO_MANY_ALT_LOCI and no observations.
+ * Left to the caller (two libm calls per observation and a sequential ln_sum_exp): prob_hit_base = -ln(len_sum) and the MAPQ
+ *   adjustment, from len_sum and min_mapq (fragments.py).
+ * Loci, realign_indel_reads, window_bytes: as for vlr_basepileup_open.  window: bases in front of a locus' start in which a member may
+ *   start (>= 0).  max_mapq: the alignment properties' value (is_max_mapq).  max_read_len <= 0 is an invalid argument.
+ * member_capacity / name_capacity / key_capacity: members, QNAME bytes and alt-locus keys the session's device buffers hold.  More than
+ *   that: nothing is written past a buffer, the status word carries VLR_FRAGPILEUP_MEMBER_OVERFLOW / _NAME_OVERFLOW / _KEY_OVERFLOW and
+ *   needed_members / needed_name_bytes / needed_keys the exact need — open again with them.  Guard words sit behind every buffer (VLR_FRAGPILEUP_GUARD_DAMAGED is never expected).
+ * vlr_fragpileup_result: seconds [0] file read, [1] upload + inflate, [2] record split, [3] member pass kernels, [4] fragment pass
+ *   kernels, [5] total of add_bam, [6] inflate kernels alone, [7] observations to the host.
+ * vlr_fragpileup_read: n_obs observations locus-major (name order within a locus) and n_loci locus records.  Bit-identical from run to
+ *   run, for every window_bytes and for every split of the input into files. */
+#define VLR_FRAGPILEUP_MAX_MEMBERS 4096   /* LDS per workgroup: 4 B sort index + 2 B rank per member + scan cells = 26 KiB, six workgroups per CU */
+/* status word of a session */
+#define VLR_FRAGPILEUP_BAD_RECORD      (1u << 0)
+#define VLR_FRAGPILEUP_MEMBER_OVERFLOW (1u << 1)
+#define VLR_FRAGPILEUP_NAME_OVERFLOW   (1u << 2)
+#define VLR_FRAGPILEUP_GUARD_DAMAGED   (1u << 3)
+#define VLR_FRAGPILEUP_KEY_OVERFLOW    (1u << 4)
+/* status of a locus */
+#define VLR_FRAGPILEUP_LOCUS_TOO_MANY_MEMBERS  (1u << 0)
+#define VLR_FRAGPILEUP_LOCUS_TOO_MANY_ALT_LOCI (1u << 1)
+/* status byte of an observation: the VLR_BASEPILEUP_HIT_* bits of its records' hits, and */
+#define VLR_FRAGPILEUP_OBS_INVALID_RO  (1u << 4)   /* an RO:Z value that names no orientation (Error::InvalidReadOrientationInfo) */
+/* bits of an observation */
+#define VLR_FRAGPILEUP_SOFTCLIPPED    (1u << 0)
+#define VLR_FRAGPILEUP_PAIRED         (1u << 1)
+#define VLR_FRAGPILEUP_MAX_MAPQ       (1u << 2)
+#define VLR_FRAGPILEUP_READPOS_MAJOR  (1u << 3)
+#define VLR_FRAGPILEUP_HAS_XA         (1u << 4)
+/* orientation: F1R2 = 0, F2R1 = 1 and None = 8 as the observation format writes them; the order of the other six is this ABI's own */
+enum { VLR_FRAG_F1R2 = 0, VLR_FRAG_F2R1 = 1, VLR_FRAG_R1F2 = 2, VLR_FRAG_R2F1 = 3, VLR_FRAG_F1F2 = 4, VLR_FRAG_R1R2 = 5, VLR_FRAG_F2F1 = 6,
+       VLR_FRAG_R2R1 = 7, VLR_FRAG_ORIENT_NONE = 8 };
+#define VLR_FRAGPILEUP_NO_RECORD 0xffffffffffffffffull
+typedef struct {
+    double   prob_ref, prob_alt;   /* merged supports                                                                                  */
+    uint64_t left, right;          /* record ordinals; right = VLR_FRAGPILEUP_NO_RECORD for a single read                              */
+    uint32_t read_position;        /* VLR_BASEPILEUP_NO_READ_POSITION = none                                                           */
+    uint32_t third_allele;         /* summed third-allele evidence, 0 = none                                                           */
+    uint32_t len_sum;              /* l_seq(left) + l_seq(right)                                                                       */
+    uint8_t  min_mapq;
+    uint8_t  orientation;          /* VLR_FRAG_*                                                                                       */
+    uint8_t  strand;               /* VLR_STRAND_*                                                                                     */
+    uint8_t  bits;                 /* VLR_FRAGPILEUP_SOFTCLIPPED ... _HAS_XA                                                           */
+    uint8_t  status;
+    uint8_t  alt_locus;            /* VLR_ALTLOCUS_*                                                                                   */
+    uint8_t  pad[6];
+} vlr_fragpileup_obs;
+typedef struct {
+    int64_t  obs_offset;           /* first observation of the locus                                                                   */
+    uint32_t n_members, n_obs;
+    uint32_t major_read_position;  /* VLR_BASEPILEUP_NO_READ_POSITION = none                                                           */
+    uint32_t status;               /* VLR_FRAGPILEUP_LOCUS_*                                                                           */
+} vlr_fragpileup_locus;
+typedef struct vlr_fragpileup vlr_fragpileup;
+typedef struct {
+    int64_t  n_obs, n_members, n_records, n_rejected, n_loci_too_deep;
+    uint64_t status;
+    int64_t  needed_members, needed_name_bytes, needed_keys;
+    int64_t  first_bad_record;     /* -1 = none */
+    double   seconds[8];
+} vlr_fragpileup_counts;
+int  vlr_fragpileup_open(int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int32_t* len, const uint8_t* kind,
+                         const uint8_t* ref_bases, const uint8_t* alt_bases, int realign_indel_reads, int64_t window, int max_mapq, int max_read_len,
+                         int64_t member_capacity, int64_t name_capacity, int64_t key_capacity, int64_t window_bytes, vlr_fragpileup** out);
+int  vlr_fragpileup_add_bam(vlr_fragpileup* s, const char* bam_path);
+int  vlr_fragpileup_result(vlr_fragpileup* s, vlr_fragpileup_counts* out);
+int  vlr_fragpileup_read(vlr_fragpileup* s, vlr_fragpileup_obs* obs, int64_t n_obs, vlr_fragpileup_locus* loci, int64_t n_loci);
+void vlr_fragpileup_close(vlr_fragpileup* s);
 
 /* The whole of `varlociraptor filter-calls control-fdr` (/root/reference/src/filtration/fdr.rs:36-158, record typing
  * src/utils/collect_variants.rs:44-304, probability sums and the filtering pass src/utils/mod.rs:169-374): read the calls BCF

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 MAX_SAMPLES = 16
 N_BIAS = 6
 
@@ -200,3 +200,27 @@ class IndelPileupCounts(C.Structure):
     """vlr_indelpileup_counts"""
     _fields_ = [("n_hits", C.c_int64), ("n_records", C.c_int64), ("n_rejected", C.c_int64), ("n_pairs", C.c_int64), ("x_bytes", C.c_int64),
                 ("y_bytes", C.c_int64), ("status", C.c_uint64), ("needed_capacity", C.c_int64), ("first_bad_record", C.c_int64), ("seconds", C.c_double * 12)]
+
+
+# vlr_fragpileup_* (fragment observations of SNV / MNV candidates from BAM records, ABI 13)
+FRAGPILEUP_MAX_MEMBERS = 4096
+FRAGPILEUP_BAD_RECORD, FRAGPILEUP_MEMBER_OVERFLOW, FRAGPILEUP_NAME_OVERFLOW, FRAGPILEUP_GUARD_DAMAGED, FRAGPILEUP_KEY_OVERFLOW = 1, 2, 4, 8, 16
+FRAGPILEUP_ANY_OVERFLOW = FRAGPILEUP_MEMBER_OVERFLOW | FRAGPILEUP_NAME_OVERFLOW | FRAGPILEUP_KEY_OVERFLOW
+FRAGPILEUP_LOCUS_TOO_MANY_MEMBERS, FRAGPILEUP_LOCUS_TOO_MANY_ALT_LOCI = 1, 2
+FRAGPILEUP_OBS_INVALID_RO = 16
+FRAGPILEUP_SOFTCLIPPED, FRAGPILEUP_PAIRED, FRAGPILEUP_MAX_MAPQ, FRAGPILEUP_READPOS_MAJOR, FRAGPILEUP_HAS_XA = 1, 2, 4, 8, 16
+FRAG_F1R2, FRAG_F2R1, FRAG_R1F2, FRAG_R2F1, FRAG_F1F2, FRAG_R1R2, FRAG_F2F1, FRAG_R2R1, FRAG_ORIENT_NONE = range(9)
+FRAGPILEUP_NO_RECORD = 0xFFFFFFFFFFFFFFFF
+
+FRAGPILEUP_OBS_DTYPE = np.dtype([("prob_ref", "<f8"), ("prob_alt", "<f8"), ("left", "<u8"), ("right", "<u8"), ("read_position", "<u4"),
+                                 ("third_allele", "<u4"), ("len_sum", "<u4"), ("min_mapq", "u1"), ("orientation", "u1"), ("strand", "u1"),
+                                 ("bits", "u1"), ("status", "u1"), ("alt_locus", "u1"), ("pad", "u1", (6,))])
+FRAGPILEUP_LOCUS_DTYPE = np.dtype([("obs_offset", "<i8"), ("n_members", "<u4"), ("n_obs", "<u4"), ("major_read_position", "<u4"), ("status", "<u4")])
+assert FRAGPILEUP_OBS_DTYPE.itemsize == 56 and FRAGPILEUP_LOCUS_DTYPE.itemsize == 24
+
+
+class FragPileupCounts(C.Structure):
+    """vlr_fragpileup_counts"""
+    _fields_ = [("n_obs", C.c_int64), ("n_members", C.c_int64), ("n_records", C.c_int64), ("n_rejected", C.c_int64), ("n_loci_too_deep", C.c_int64),
+                ("status", C.c_uint64), ("needed_members", C.c_int64), ("needed_name_bytes", C.c_int64), ("needed_keys", C.c_int64), ("first_bad_record", C.c_int64),
+                ("seconds", C.c_double * 8)]

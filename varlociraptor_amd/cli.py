@@ -1,6 +1,6 @@
 """`python -m varlociraptor_amd call variants generic --scenario S.yaml --obs name=path.vcf ... [> calls.vcf]`
-(also `filter-calls control-fdr`, `filter-calls posterior-odds` (odds.py), `estimate contamination` (contamination.py) and
-`estimate mutational-burden` (burden.py))
+(also `filter-calls control-fdr`, `filter-calls posterior-odds` (odds.py), `estimate contamination` (contamination.py),
+`estimate mutational-burden` (burden.py) and `preprocess variants` for SNV / MNV candidates (fragments.py))
 
 Mirror of the reference's `call variants` surface (src/cli.rs:684-735) for text observation VCFs (format v15):
 `generic` with a scenario YAML (grammar/mod.rs:129-144) and `tumor-normal --tumor --normal --purity`
@@ -165,8 +165,32 @@ def main(argv=None):
     ec.add_argument("--output-plot", help="vega-lite plot of the prior and posterior densities of purity (JSON)")
     ec.add_argument("--output-max-vaf-variants", help="chrom,pos of the observations at the maximum MAP VAF (CSV)")
     ec.add_argument("--device", type=int, default=0)
+    pre = sub.add_parser("preprocess").add_subparsers(dest="what", required=True)
+    pv = pre.add_parser("variants", help="observations of SNV / MNV candidates from a BAM file, one per fragment (cli.rs:241-390)")
+    pv.add_argument("reference", help="FASTA file of the reference genome")
+    pv.add_argument("--candidates", required=True, help="candidate variants (VCF or BCF)")
+    pv.add_argument("--bam", required=True)
+    pv.add_argument("--alignment-properties", help="JSON of `estimate alignment-properties` (default: estimated from --bam on the device)")
+    pv.add_argument("--atomic-candidate-variants", action="store_true", help="required: every candidate on its own (no realignment against the others)")
+    pv.add_argument("--omit-mapq-adjustment", action="store_true")
+    pv.add_argument("--max-depth", type=int, default=200, help="loci above it are counted in a warning and processed whole")
+    pv.add_argument("--score-indel-reads-from-alignment", action="store_true",
+                    help="score a read with an insertion or deletion as it is aligned (the reference realigns it; without this flag such a read is an error)")
+    pv.add_argument("--device", default="0", help="HIP device index, or 'cpu' for the Python restatement")
+    pv.add_argument("--output", required=True, help="observation BCF")
     a = ap.parse_args(argv)
     import os
+    if a.cmd == "preprocess":
+        from . import fragments
+        try:
+            n = fragments.preprocess_variants(a.reference, a.candidates, a.bam, a.output, a.alignment_properties, "cpu" if a.device == "cpu" else int(a.device),
+                                              a.atomic_candidate_variants, a.omit_mapq_adjustment, a.max_depth, a.score_indel_reads_from_alignment,
+                                              warn=lambda m: print(f"[WARN] {m}", file=sys.stderr))
+        except (fragments.PreprocessError, fragments.FragPileupError, fragments.InvalidReadOrientationInfo) as e:
+            print(f"error: {e}", file=sys.stderr)
+            sys.exit(1)
+        print(f"{n} records written", file=sys.stderr)
+        return
     if a.cmd == "call" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # one process per GPU (torchrun): `nccl` is RCCL on ROCm; VLR_DIST_BACKEND=gloo for hosts with fewer GPUs than ranks
         import torch

@@ -401,13 +401,35 @@ def concat_parts(path: str, parts: Sequence[str]):
     _check(L.vlr_calls_concat_parts(path.encode(), arr, len(parts)))
 
 
-def write_observations(path: str, batch: PileupBatch, sample: int, threads: int = 0, third_allele_evidence: Optional[np.ndarray] = None):
-    """vlr_obs_write: the observation BCF of one sample of a host batch (synthetic sites)."""
+def write_observations(path: str, batch: PileupBatch, sample: int, threads: int = 0, third_allele_evidence: Optional[np.ndarray] = None,
+                       sites: Optional[Sequence[Tuple[str, int, str, str, str]]] = None):
+    """vlr_obs_write: the observation BCF of one sample of a host batch.  `sites`: (CHROM, 1-based POS, ID, REF, ALT) per locus;
+    without them the sites are synthetic (contig "1", positions 1.., alleles from the batch's variant type and bases)."""
     bs = batch.as_struct()
     third = None
     if third_allele_evidence is not None:
         third = np.ascontiguousarray(third_allele_evidence, np.int32)
-    _check(_lib().vlr_obs_write(path.encode(), C.byref(bs), int(sample), None, third.ctypes.data if third is not None else None, int(threads)))
+    st, keep = None, None
+    if sites is not None:
+        if len(sites) != batch.n_loci:
+            raise ValueError("%d sites for %d loci" % (len(sites), batch.n_loci))
+        names = list(dict.fromkeys(c for c, *_ in sites))
+        blob, offs = bytearray(), [[], [], []]
+        for _, _, rid, ref, alt in sites:
+            for k, v in enumerate((rid or ".", ref, alt)):
+                offs[k].append(len(blob))
+                blob += v.encode() + b"\0"
+        arr = (C.c_char_p * len(names))(*[n.encode() for n in names])
+        contig = np.array([names.index(c) for c, *_ in sites], np.int32)
+        pos = np.array([p for _, p, *_ in sites], np.int64)
+        oid, oref, oalt = (np.array(o, np.uint64) for o in offs)
+        strings = C.create_string_buffer(bytes(blob), len(blob) + 1)
+        keep = (arr, contig, pos, oid, oref, oalt, strings)
+        st = ObsSites(n_loci=batch.n_loci, n_contigs=len(names), contig_names=arr, contig=contig.ctypes.data, pos=pos.ctypes.data,
+                      strings=C.addressof(strings), id_offset=oid.ctypes.data, ref_offset=oref.ctypes.data, alt_offset=oalt.ctypes.data)
+    _check(_lib().vlr_obs_write(path.encode(), C.byref(bs), int(sample), C.byref(st) if st is not None else None,
+                                third.ctypes.data if third is not None else None, int(threads)))
+    del keep
 
 
 def write_calls(path: str, header_text: str, table: ObsTable, results: CallResults, out_names: List[str], threads: int = 0):

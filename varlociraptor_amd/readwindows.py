@@ -51,6 +51,7 @@ class BamRecord:
     mate_pos: int
     tlen: int
     aux: bytes = b""  # the raw aux fields behind the qualities
+    raw_name: Optional[bytes] = None  # the QNAME's bytes as the record holds them (read_bam)
 
     @property
     def reverse(self) -> bool:
@@ -85,7 +86,8 @@ def read_bam(path: str) -> Tuple[List[Tuple[str, int]], List[BamRecord]]:
         block_size, = struct.unpack_from("<i", d, o)
         ref_id, pos, l_read_name, mapq, _bin, n_cigar, flag, l_seq, mate_ref, mate_pos, tlen = struct.unpack_from("<iiBBHHHiiii", d, o + 4)
         p = o + 36
-        qname = d[p:p + l_read_name - 1].decode()
+        raw_name = bytes(d[p:p + l_read_name - 1])
+        qname = raw_name.decode("utf-8", "replace")
         p += l_read_name
         cigar = []
         for k in range(n_cigar):
@@ -99,7 +101,7 @@ def read_bam(path: str) -> Tuple[List[Tuple[str, int]], List[BamRecord]]:
             seq[i] = ord(SEQ_CODE[(b >> 4) if (i & 1) == 0 else (b & 0xf)])
         p += (l_seq + 1) // 2
         qual = d[p:p + l_seq]
-        recs.append(BamRecord(qname, flag, ref_id, pos, mapq, cigar, bytes(seq), bytes(qual), mate_ref, mate_pos, tlen, bytes(d[p + l_seq:o + 4 + block_size])))
+        recs.append(BamRecord(qname, flag, ref_id, pos, mapq, cigar, bytes(seq), bytes(qual), mate_ref, mate_pos, tlen, bytes(d[p + l_seq:o + 4 + block_size]), raw_name))
         o += 4 + block_size
     return contigs, recs
 
