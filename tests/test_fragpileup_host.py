@@ -6,7 +6,6 @@ the synthetic inputs of tests/fragment_cases.py and the fixtures — its observa
 on the program's own tables — and over the hand records cut at every byte of their name and aux area and with their RO / XA values
 overwritten: those must come back as bad records (or as records with other features) without a report."""
 import os
-import shutil
 import struct
 import subprocess
 
@@ -15,39 +14,14 @@ import pytest
 
 import basecall_cases as bc
 import fragment_cases as fc
+import host_program
 from varlociraptor_amd import abi, alignprops, basecalls, fragments
 from varlociraptor_amd.readwindows import read_bam, read_fasta
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "varlociraptor_amd", "csrc")
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.skip("no system C++ compiler")
-    out = os.path.join(CSRC, "build", "host")
-    try:
-        os.makedirs(out, exist_ok=True)
-        open(os.path.join(out, ".w"), "w").close()
-    except OSError:
-        out = str(tmp_path_factory.mktemp("host_build"))
-    probe = os.path.join(out, "probe_frag.cpp")
-    with open(probe, "w") as f:
-        f.write("int main() { return 0; }\n")
-    # the sanitizer runtimes linked statically where the compiler can (nothing preloaded into the process can then come before them)
-    for static in (["-static-libasan", "-static-libubsan"], []):
-        flags = SAN + static
-        r = subprocess.run([cxx] + flags + [probe, "-o", os.path.join(out, "probe_frag")], capture_output=True, text=True)
-        if r.returncode == 0 and subprocess.run([os.path.join(out, "probe_frag")], capture_output=True).returncode == 0:
-            break
-    else:
-        pytest.skip("the system compiler has no usable -fsanitize=address,undefined: " + r.stderr[-200:])
-    exe = os.path.join(out, "vlr_fragpileup_host")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-ffp-contract=off"] + flags + [os.path.join(CSRC, "vlr_fragpileup_host.cpp"), "-o", exe])
-    return exe
+    return host_program.build(tmp_path_factory, "vlr_fragpileup_host")
 
 
 def run(program, tmp, loci, records, props, realign=False):

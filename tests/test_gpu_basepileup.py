@@ -101,6 +101,21 @@ def test_synthetic_bam_equals_the_restatement(synth, tables):
     check(synth["bam"], synth["loci"], tables, realign=True)
 
 
+@pytest.mark.parametrize("n_records", [1023, 1024, 1025, 2049])
+def test_one_chunk_around_the_scan_width_equals_the_restatement(tables, tmp_path, n_records):
+    """The prefix sum over a chunk's per-record counts (vlr_bam::scan_kernel of csrc/vlr_bamsession.h, 1024 threads, u32 counts) where a
+    thread's slice holds one record with trailing threads empty (1023), exactly one (1024), two with the threads of the upper half
+    empty (1025: slices of 2, 513 of them used) and three (2049): one chunk of n_records records (the default window_bytes holds the
+    whole file), every hit's place checked against the restatement.  The module's 300-record input never gives a thread two records.
+    The same kernel scans the fragment session's three count arrays; tests/test_gpu_fragpileup.py's module input has more than 3000
+    records in one chunk and 120 loci, so slices of three and four records and the per-locus scans are covered there."""
+    contigs, cands, recs = bc.synthetic(n_records=n_records, n_loci=200)
+    loci = bc.loci_of(cands, contigs)
+    bam, _ = bc.write_case(tmp_path, "scan%d" % n_records, contigs, recs)
+    arr, res = check(bam, loci, tables)
+    assert res.n_records == n_records and res.n_hits > 1000 and res.n_rejected > 50
+
+
 def test_hits_do_not_depend_on_the_feeds_or_the_run(synth):
     base, _ = basecalls.device_hits(synth["bam"], synth["loci"])
     again, _ = basecalls.device_hits(synth["bam"], synth["loci"])

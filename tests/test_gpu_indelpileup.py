@@ -109,6 +109,17 @@ def test_synthetic_set_fields_scores_and_pairs(synth, mode):
     assert res.n_hits > 200 and list(arr["locus"]) == sorted(arr["locus"]) and {synth.rid[k] for k in set(arr["locus"])} == {0, 1}
 
 
+def test_one_chunk_wider_than_the_scan_fields_scores_and_pairs(tmp_path):
+    """The prefix sums over a chunk's three u64 count arrays (vlr_bam::scan_kernel of csrc/vlr_bamsession.h, 1024 threads, one workgroup
+    per array) where a thread's slice holds two records and the threads of the upper half have none: 1100 records in one chunk (the
+    default window_bytes holds the whole file).  The module's 260-record input never gives a thread two records.  Exact mode; the
+    comparison of test_synthetic_set_fields_scores_and_pairs: every hit's place, score and pair bytes."""
+    contigs, cands, recs = ic.synthetic(n_records=1100)
+    c = Case(tmp_path, "scan1100", contigs, list(contigs), cands, recs)
+    arr, res = c.check("exact")
+    assert res.n_records == 1100 and res.n_hits > 800 and list(arr["locus"]) == sorted(arr["locus"])
+
+
 def test_hits_do_not_depend_on_feeds_files_or_sub_ranges(synth, monkeypatch):
     base, _, _ = synth.hits()
     assert len(base) == len(synth.exp)

@@ -449,18 +449,7 @@ def device_hits(bam: str, loci: Sequence[Locus], device: int = 0, realign_indel_
     retry=False (then the counts carry BASEPILEUP_OVERFLOW and the array is empty)."""
     import ctypes as C
     from . import engine
-    L = engine.lib()
-    L.vlr_basepileup_open.restype = C.c_int
-    L.vlr_basepileup_open.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
-                                      C.POINTER(C.c_void_p)]
-    L.vlr_basepileup_add_bam.restype = C.c_int
-    L.vlr_basepileup_add_bam.argtypes = [C.c_void_p, C.c_char_p]
-    L.vlr_basepileup_result.restype = C.c_int
-    L.vlr_basepileup_result.argtypes = [C.c_void_p, C.POINTER(abi.BasePileupCounts)]
-    L.vlr_basepileup_read.restype = C.c_int
-    L.vlr_basepileup_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.vlr_basepileup_close.restype = None
-    L.vlr_basepileup_close.argtypes = [C.c_void_p]
+    L = engine.bind_basepileup()
     n = len(loci)
     ref_id = np.array([l.ref_id for l in loci], np.int32)
     start = np.array([l.start for l in loci], np.int64)

@@ -35,9 +35,7 @@
 
 #include <zlib.h>
 
-#include "../../include/vlr.h"
-#include "vlr_gpuio.h"
-#include "vlr_bamstream.h"
+#include "vlr_bamsession.h"
 
 extern "C" void vlr_set_error(const char* msg);  // vlr_host.cpp: the text behind vlr_last_error()
 
@@ -397,22 +395,14 @@ int bfail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define BAM_HIP_OK(call)                                                                          \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) return bfail(VLR_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-struct FaiEntry { uint64_t len, off, lb, lw; };
 
 }  // namespace vlr_bam
 
 struct vlr_bamstats {
     int device = 0;
     std::string fasta;
-    std::map<std::string, vlr_bam::FaiEntry> fai;
+    vlr_bam::Fai fai;
     int64_t cap = 0;             // records to analyse in all (--num-records or the default count)
     size_t window = vlr_bam::kWindow;
     uint64_t n_taken = 0, n_skipped = 0;
@@ -422,7 +412,7 @@ struct vlr_bamstats {
     int64_t* d_tlen = nullptr;
     size_t rec_cap = 0, used_cap = 0;
     const uint8_t** d_ctg = nullptr; uint64_t* d_ctg_len = nullptr; size_t ctg_cap = 0;
-    std::map<std::string, std::pair<uint8_t*, uint64_t>> contigs;   // uploaded contigs by name
+    vlr_bam::Contigs contigs;   // uploaded contigs by name
     std::vector<int64_t> tlens;
     std::vector<uint64_t> hop_keys, hop_vals;
     bool collected = false;
@@ -431,57 +421,48 @@ struct vlr_bamstats {
 
 namespace vlr_bam {
 
-int read_fai(vlr_bamstats* s) {
-    const std::string path = s->fasta + ".fai";
+int read_fai(const std::string& fasta, Fai& fai) {
+    const std::string path = fasta + ".fai";
     FILE* f = fopen(path.c_str(), "r");
-    if (!f) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: no .fai index (index the reference with samtools faidx)", s->fasta.c_str());
+    if (!f) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: no .fai index (index the reference with samtools faidx)", fasta.c_str());
     char line[4096];
     while (fgets(line, sizeof line, f)) {
         char name[2048];
         unsigned long long a, b, c, d;
-        if (sscanf(line, "%2047[^\t]\t%llu\t%llu\t%llu\t%llu", name, &a, &b, &c, &d) == 5 && c > 0 && d >= c) s->fai[name] = {a, b, c, d};
+        if (sscanf(line, "%2047[^\t]\t%llu\t%llu\t%llu\t%llu", name, &a, &b, &c, &d) == 5 && c > 0 && d >= c) fai[name] = {a, b, c, d};
     }
     fclose(f);
     return VLR_OK;
 }
 
-// the bases of one contig, case preserved (bio's IndexedReader through the .fai)
-int load_contig(vlr_bamstats* s, const std::string& name, const char* bam, std::pair<uint8_t*, uint64_t>& out) {
-    auto it = s->contigs.find(name);
-    if (it != s->contigs.end()) { out = it->second; return VLR_OK; }
-    auto e = s->fai.find(name);
-    if (e == s->fai.end()) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: contig %s (of %s) is missing from the reference", s->fasta.c_str(), name.c_str(), bam);
+// the bases of one contig through the .fai, on the device (see vlr_bamstream.h)
+int load_contig(const std::string& fasta, const Fai& fai, Contigs& cache, const std::string& name, const char* bam, bool upper_case, std::pair<uint8_t*, uint64_t>& out) {
+    auto it = cache.find(name);
+    if (it != cache.end()) { out = it->second; return VLR_OK; }
+    auto e = fai.find(name);
+    if (e == fai.end()) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: contig %s (of %s) is missing from the reference", fasta.c_str(), name.c_str(), bam);
     const FaiEntry& x = e->second;
     std::vector<uint8_t> seq(x.len);
     if (x.len) {
         const uint64_t nlines = (x.len - 1) / x.lb + 1;
         const uint64_t raw_n = (nlines - 1) * x.lw + (x.len - (nlines - 1) * x.lb);
         std::vector<uint8_t> raw(raw_n);
-        FILE* f = fopen(s->fasta.c_str(), "rb");
-        if (!f) return bfail(VLR_ERR_INVALID_ARGUMENT, "cannot open %s", s->fasta.c_str());
+        FILE* f = fopen(fasta.c_str(), "rb");
+        if (!f) return bfail(VLR_ERR_INVALID_ARGUMENT, "cannot open %s", fasta.c_str());
         const bool ok = fseeko(f, (off_t)x.off, SEEK_SET) == 0 && fread(raw.data(), 1, raw_n, f) == raw_n;
         fclose(f);
-        if (!ok) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: contig %s shorter than its .fai entry", s->fasta.c_str(), name.c_str());
+        if (!ok) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: contig %s shorter than its .fai entry", fasta.c_str(), name.c_str());
         for (uint64_t l = 0, k = 0; l < nlines; ++l) {
             const uint64_t m = std::min<uint64_t>(x.lb, x.len - k);
             memcpy(seq.data() + k, raw.data() + l * x.lw, m);
             k += m;
         }
+        if (upper_case) for (auto& c : seq) if (c >= 'a' && c <= 'z') c = (uint8_t)(c - 32);
     }
     uint8_t* d = nullptr;
-    BAM_HIP_OK(hipMalloc(&d, x.len + 1));
-    if (x.len) BAM_HIP_OK(hipMemcpy(d, seq.data(), x.len, hipMemcpyHostToDevice));
-    out = s->contigs[name] = {d, x.len};
-    return VLR_OK;
-}
-
-template <class T> int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return VLR_OK;
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-    const size_t ncap = need + need / 4 + 1024;
-    if (hipMalloc((void**)&p, ncap * sizeof(*p)) != hipSuccess) { (void)hipGetLastError(); cap = 0; return bfail(VLR_ERR_OUT_OF_MEMORY, "out of device memory (%zu records)", ncap); }
-    cap = ncap;
+    VLR_HIP_OK(hipMalloc(&d, x.len + 1));
+    if (x.len) VLR_HIP_OK(hipMemcpy(d, seq.data(), x.len, hipMemcpyHostToDevice));
+    out = cache[name] = {d, x.len};
     return VLR_OK;
 }
 
@@ -518,19 +499,19 @@ bool index_members(const uint8_t* b, size_t n, std::vector<Member>& out, size_t*
 }
 
 int alloc_state(vlr_bamstats* s) {
-    BAM_HIP_OK(hipMalloc(&s->d_trans, 256 * 8));
-    BAM_HIP_OK(hipMalloc(&s->d_dense, kDense * 8));
-    BAM_HIP_OK(hipMalloc(&s->d_hkeys, (size_t)kHashSlots * 8));
-    BAM_HIP_OK(hipMalloc(&s->d_hvals, (size_t)kHashSlots * 8));
-    BAM_HIP_OK(hipMalloc(&s->d_misc, M_N * 8));
-    BAM_HIP_OK(hipMalloc(&s->d_out, 2 * 8));
-    BAM_HIP_OK(hipMemset(s->d_trans, 0, 256 * 8));
-    BAM_HIP_OK(hipMemset(s->d_dense, 0, kDense * 8));
-    BAM_HIP_OK(hipMemset(s->d_hkeys, 0xff, (size_t)kHashSlots * 8));
-    BAM_HIP_OK(hipMemset(s->d_hvals, 0, (size_t)kHashSlots * 8));
-    BAM_HIP_OK(hipMemset(s->d_misc, 0, M_N * 8));
+    VLR_HIP_OK(hipMalloc(&s->d_trans, 256 * 8));
+    VLR_HIP_OK(hipMalloc(&s->d_dense, kDense * 8));
+    VLR_HIP_OK(hipMalloc(&s->d_hkeys, (size_t)kHashSlots * 8));
+    VLR_HIP_OK(hipMalloc(&s->d_hvals, (size_t)kHashSlots * 8));
+    VLR_HIP_OK(hipMalloc(&s->d_misc, M_N * 8));
+    VLR_HIP_OK(hipMalloc(&s->d_out, 2 * 8));
+    VLR_HIP_OK(hipMemset(s->d_trans, 0, 256 * 8));
+    VLR_HIP_OK(hipMemset(s->d_dense, 0, kDense * 8));
+    VLR_HIP_OK(hipMemset(s->d_hkeys, 0xff, (size_t)kHashSlots * 8));
+    VLR_HIP_OK(hipMemset(s->d_hvals, 0, (size_t)kHashSlots * 8));
+    VLR_HIP_OK(hipMemset(s->d_misc, 0, M_N * 8));
     const uint64_t none = ~0ull;
-    BAM_HIP_OK(hipMemcpy(s->d_misc + M_ERR_REC, &none, 8, hipMemcpyHostToDevice));
+    VLR_HIP_OK(hipMemcpy(s->d_misc + M_ERR_REC, &none, 8, hipMemcpyHostToDevice));
     return VLR_OK;
 }
 
@@ -541,25 +522,25 @@ int run_chunk(vlr_bamstats* s, vlr_dev_file* df, int64_t n, uint64_t rec0, const
     if (rc != VLR_OK) return rc;
     size_t c1 = s->rec_cap, c2 = s->rec_cap, c3 = s->rec_cap;
     if ((size_t)n > s->rec_cap) {
-        BAM_HIP_OK(hipStreamSynchronize(st));
+        VLR_HIP_OK(hipStreamSynchronize(st));
         if ((rc = grow(s->d_take, c1, (size_t)n)) || (rc = grow(s->d_sel, c2, (size_t)n)) || (rc = grow(s->d_tlen, c3, (size_t)n))) return rc;
         s->rec_cap = c1;
     }
     const size_t n_refs = names.size();
     double t0 = now_s();
     hipLaunchKernelGGL(bam_take_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_base, d_starts, n, s->d_take);
-    BAM_HIP_OK(hipMemsetAsync(s->d_used, 0, n_refs ? n_refs : 1, st));
-    BAM_HIP_OK(hipMemsetAsync(s->d_out, 0, 16, st));
+    VLR_HIP_OK(hipMemsetAsync(s->d_used, 0, n_refs ? n_refs : 1, st));
+    VLR_HIP_OK(hipMemsetAsync(s->d_out, 0, 16, st));
     const uint64_t remaining = (uint64_t)s->cap - s->n_taken;
     hipLaunchKernelGGL(bam_select_kernel, dim3(1), dim3(kSelThreads), 0, st, d_base, d_starts, n, s->d_take, remaining, (int)n_refs, rec0, s->d_sel,
                        s->d_used, s->d_out, s->d_misc);
     uint64_t out[2], err[2];
     std::vector<uint8_t> used(n_refs ? n_refs : 1);
-    BAM_HIP_OK(hipMemcpyAsync(out, s->d_out, 16, hipMemcpyDeviceToHost, st));
-    BAM_HIP_OK(hipMemcpyAsync(err, s->d_misc + M_ERR_CODE, 16, hipMemcpyDeviceToHost, st));
-    BAM_HIP_OK(hipMemcpyAsync(used.data(), s->d_used, used.size(), hipMemcpyDeviceToHost, st));
-    BAM_HIP_OK(hipStreamSynchronize(st));
-    BAM_HIP_OK(hipGetLastError());
+    VLR_HIP_OK(hipMemcpyAsync(out, s->d_out, 16, hipMemcpyDeviceToHost, st));
+    VLR_HIP_OK(hipMemcpyAsync(err, s->d_misc + M_ERR_CODE, 16, hipMemcpyDeviceToHost, st));
+    VLR_HIP_OK(hipMemcpyAsync(used.data(), s->d_used, used.size(), hipMemcpyDeviceToHost, st));
+    VLR_HIP_OK(hipStreamSynchronize(st));
+    VLR_HIP_OK(hipGetLastError());
     s->t[3] += now_s() - t0;
     if (err[0]) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: record %llu: %s", path, (unsigned long long)err[1],
                              (err[0] & E_MALFORMED) ? "malformed record (fields overrun block_size)" : "reference id out of range");
@@ -572,22 +553,22 @@ int run_chunk(vlr_bamstats* s, vlr_dev_file* df, int64_t n, uint64_t rec0, const
         std::pair<uint8_t*, uint64_t> c{nullptr, 0};
         auto it = s->contigs.find(names[k]);
         if (it != s->contigs.end()) c = it->second;
-        else if (used[k] && (rc = load_contig(s, names[k], path, c)) != VLR_OK) return rc;
+        else if (used[k] && (rc = load_contig(s->fasta, s->fai, s->contigs, names[k], path, false, c)) != VLR_OK) return rc;
         ptr[k] = c.first; len[k] = c.second;
     }
     if (n_refs) {
-        BAM_HIP_OK(hipMemcpyAsync((void*)s->d_ctg, ptr.data(), n_refs * sizeof(void*), hipMemcpyHostToDevice, st));
-        BAM_HIP_OK(hipMemcpyAsync(s->d_ctg_len, len.data(), n_refs * 8, hipMemcpyHostToDevice, st));
+        VLR_HIP_OK(hipMemcpyAsync((void*)s->d_ctg, ptr.data(), n_refs * sizeof(void*), hipMemcpyHostToDevice, st));
+        VLR_HIP_OK(hipMemcpyAsync(s->d_ctg_len, len.data(), n_refs * 8, hipMemcpyHostToDevice, st));
     }
-    BAM_HIP_OK(hipStreamSynchronize(st));
+    VLR_HIP_OK(hipStreamSynchronize(st));
     s->t[4] += now_s() - t0;
     t0 = now_s();
     const int64_t blocks = std::min<int64_t>((n + kWaves - 1) / kWaves, 1024);
     hipLaunchKernelGGL(bam_stats_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, d_base, d_starts, n, s->d_sel, s->d_ctg, s->d_ctg_len, rec0,
                        s->d_trans, s->d_dense, s->d_hkeys, s->d_hvals, s->d_misc, s->d_tlen);
-    BAM_HIP_OK(hipMemcpyAsync(err, s->d_misc + M_ERR_CODE, 16, hipMemcpyDeviceToHost, st));
-    BAM_HIP_OK(hipStreamSynchronize(st));
-    BAM_HIP_OK(hipGetLastError());
+    VLR_HIP_OK(hipMemcpyAsync(err, s->d_misc + M_ERR_CODE, 16, hipMemcpyDeviceToHost, st));
+    VLR_HIP_OK(hipStreamSynchronize(st));
+    VLR_HIP_OK(hipGetLastError());
     s->t[5] += now_s() - t0;
     if (err[0]) {
         const char* what = (err[0] & E_CIGAR_RANGE) ? "CIGAR runs past the contig or the read" : (err[0] & E_MALFORMED) ? "malformed record (unknown CIGAR operation)"
@@ -596,8 +577,8 @@ int run_chunk(vlr_bamstats* s, vlr_dev_file* df, int64_t n, uint64_t rec0, const
     }
     t0 = now_s();
     std::vector<int64_t> tl((size_t)n);
-    BAM_HIP_OK(hipMemcpyAsync(tl.data(), s->d_tlen, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    BAM_HIP_OK(hipStreamSynchronize(st));
+    VLR_HIP_OK(hipMemcpyAsync(tl.data(), s->d_tlen, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    VLR_HIP_OK(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n; ++i) if (tl[(size_t)i] >= 0) s->tlens.push_back(tl[(size_t)i]);
     s->t[6] += now_s() - t0;
     s->n_taken += out[0];
@@ -787,15 +768,14 @@ int vlr_bamstats_open(int device, const char* fasta_path, int64_t max_records, i
     using namespace vlr_bam;
     if (!out || !fasta_path || max_records < 0 || window_bytes < 0) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_bamstats_open: bad argument");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || ndev <= device) return bfail(VLR_ERR_NO_DEVICE, "no HIP device %d (the engine has no CPU path)", device);
-    BAM_HIP_OK(hipSetDevice(device));
+    int rc = use_device(device);
+    if (rc != VLR_OK) return rc;
     vlr_bamstats* s = new vlr_bamstats();
     s->device = device;
     s->fasta = fasta_path;
     s->cap = max_records;
     if (window_bytes > 0) s->window = (size_t)window_bytes;
-    int rc = read_fai(s);
+    rc = read_fai(s->fasta, s->fai);
     if (rc == VLR_OK) rc = alloc_state(s);
     if (rc != VLR_OK) { vlr_bamstats_close(s); return rc; }
     *out = s;
@@ -812,12 +792,12 @@ int vlr_bamstats_add_bam(vlr_bamstats* s, const char* bam_path) {
 int vlr_bamstats_result(vlr_bamstats* s, vlr_bamstats_counts* r) {
     using namespace vlr_bam;
     if (!s || !r) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_bamstats_result: null");
-    BAM_HIP_OK(hipSetDevice(s->device));
+    VLR_HIP_OK(hipSetDevice(s->device));
     if (!s->collected) {
         std::vector<uint64_t> dense(kDense), hk(kHashSlots), hv(kHashSlots);
-        BAM_HIP_OK(hipMemcpy(dense.data(), s->d_dense, kDense * 8, hipMemcpyDeviceToHost));
-        BAM_HIP_OK(hipMemcpy(hk.data(), s->d_hkeys, (size_t)kHashSlots * 8, hipMemcpyDeviceToHost));
-        BAM_HIP_OK(hipMemcpy(hv.data(), s->d_hvals, (size_t)kHashSlots * 8, hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(dense.data(), s->d_dense, kDense * 8, hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(hk.data(), s->d_hkeys, (size_t)kHashSlots * 8, hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(hv.data(), s->d_hvals, (size_t)kHashSlots * 8, hipMemcpyDeviceToHost));
         std::map<uint64_t, uint64_t> all;
         static const char kBase[8] = {'A', 'C', 'G', 'T', 'a', 'c', 'g', 't'};
         for (int b = 0; b < 8; ++b)
@@ -833,8 +813,8 @@ int vlr_bamstats_result(vlr_bamstats* s, vlr_bamstats_counts* r) {
         s->collected = true;
     }
     uint64_t misc[M_N];
-    BAM_HIP_OK(hipMemcpy(r->transitions, s->d_trans, 256 * 8, hipMemcpyDeviceToHost));
-    BAM_HIP_OK(hipMemcpy(misc, s->d_misc, M_N * 8, hipMemcpyDeviceToHost));
+    VLR_HIP_OK(hipMemcpy(r->transitions, s->d_trans, 256 * 8, hipMemcpyDeviceToHost));
+    VLR_HIP_OK(hipMemcpy(misc, s->d_misc, M_N * 8, hipMemcpyDeviceToHost));
     r->n_taken = (int64_t)s->n_taken; r->n_skipped = (int64_t)s->n_skipped;
     r->n_not_usable = (int64_t)misc[M_NOT_USABLE]; r->n_softclips = (int64_t)misc[M_SOFT];
     r->n_not_paired = (int64_t)misc[M_NOT_PAIRED]; r->n_not_first = (int64_t)misc[M_NOT_FIRST];

@@ -1,10 +1,14 @@
-// vlr_bamstream.h — one BAM file through the device reader (vlr_bamstats.hip: stream_bam), shared by the passes that consume split
-// BAM records on the device: vlr_bamstats_add_bam and vlr_basepileup_add_bam.  Internal to the engine's translation units.
+// vlr_bamstream.h — one BAM file through the device reader (vlr_bamstats.hip: stream_bam) and the reference's contigs through its .fai,
+// shared by the passes that consume split BAM records on the device: vlr_bamstats_add_bam, vlr_basepileup_add_bam,
+// vlr_indelpileup_add_bam and vlr_fragpileup_add_bam (the three sessions through vlr_bamsession.h).  Internal to the engine's
+// translation units.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 struct vlr_dev_file;
@@ -27,5 +31,15 @@ struct BamStream {
 int stream_bam(const BamStream& b, const char* path);
 int bfail(int code, const char* fmt, ...);
 double now_s();
+
+// the reference FASTA through its .fai index: the entries by contig name, and the contigs uploaded so far (device pointer, length)
+struct FaiEntry { uint64_t len, off, lb, lw; };
+using Fai = std::map<std::string, FaiEntry>;
+using Contigs = std::map<std::string, std::pair<uint8_t*, uint64_t>>;
+
+int read_fai(const std::string& fasta, Fai& fai);
+// the bases of one contig on the device, once per name; case preserved (bio's IndexedReader) or upper-cased (the reference's buffer
+// for realignment hands out upper case).  `bam` names the file whose header asked for it, for the refusal.
+int load_contig(const std::string& fasta, const Fai& fai, Contigs& cache, const std::string& name, const char* bam, bool upper_case, std::pair<uint8_t*, uint64_t>& out);
 
 }  // namespace vlr_bam

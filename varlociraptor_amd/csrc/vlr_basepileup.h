@@ -273,8 +273,9 @@ VLR_BP_HD inline bool score(const Tables& t, const Loci& L, int64_t li, const Re
     return true;
 }
 
-// first locus at or behind (ref_id, pos) in the sorted loci
-VLR_BP_HD inline int64_t lower_bound(const Loci& L, int32_t ref_id, int64_t pos) {
+// first locus at or behind (ref_id, pos) in the sorted loci (any Loci with n, ref_id and start: also vlr_ip::Loci)
+template <class L_>
+VLR_BP_HD inline int64_t lower_bound(const L_& L, int32_t ref_id, int64_t pos) {
     int64_t lo = 0, hi = L.n;
     while (lo < hi) {
         const int64_t mid = lo + (hi - lo) / 2;

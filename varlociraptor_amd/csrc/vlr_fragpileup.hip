@@ -6,14 +6,14 @@
 //   frag_count_kernel    thread i decodes record i, finds the loci whose window holds its start: cnt[i] = members, and when it is a member
 //                        of any locus nbytes[i] = bytes of its QNAME, nxa[i] = alt-locus keys of its XA:Z tag; rejected and bad records go
 //                        to integer counters
-//   frag_scan_kernel     one workgroup, exclusive prefix sum (run for cnt, nbytes and nxa)
+//   vlr_bam::scan_kernel one workgroup per count array (cnt, nbytes, nxa; vlr_bamsession.h, u32 counts): exclusive prefix sums
 //   frag_fill_kernel     thread i builds the members of record i again and writes them at members[base + off[i] ...), its name at
 //                        names[name_base + noff[i] ...), its keys at keys[key_base + xoff[i] ...); what would lie behind a capacity is
 //                        not written.  It adds the record's members
 //                        to the per-locus counters (sums: order-independent)
 // so the places of members, names and keys are functions of the record order alone.
 // Fragment pass, at vlr_fragpileup_result:
-//   frag_scan_kernel     per-locus member counts -> the loci's first slots
+//   vlr_bam::scan_kernel per-locus member counts -> the loci's first slots
 //   frag_scatter_kernel  member m takes the next free slot of its locus (an atomic cursor: the placement within a locus is not stable and
 //                        need not be, the sort below is on a total key)
 //   frag_locus_kernel    one workgroup per locus: the member indices go to LDS, a bitonic sort orders them by (QNAME bytes, record ordinal),
@@ -22,7 +22,7 @@
 //                        major_read_position are sorted in the same LDS array and thread 0 takes their mode; then the indices of the
 //                        alt-locus keys of all observations are laid out by a second prefix sum, sorted in that array by (contig hash,
 //                        bucket), and thread 0 takes major_alt_locus
-//   frag_scan_kernel     per-locus observation counts -> the loci's offsets
+//   vlr_bam::scan_kernel per-locus observation counts -> the loci's offsets
 //   frag_gather_kernel   one workgroup per locus writes its observations at the offset, in rank order, with VLR_FRAGPILEUP_READPOS_MAJOR
 //                        and the alt_locus class (vlr_fp::alt_locus_class)
 // No atomic decides a place or an order that reaches the output: the cursors only fill the sort's input.
@@ -32,18 +32,11 @@
 // Bounds: a record is read only after vlr_bp::decode checked it; members[k] is written for k < member capacity, names[k] for
 // k < name capacity, keys[k] for k < key capacity; perm / tmp / rank / the pair arrays are sized by the member count and every index into
 // them is below a locus' count, which sums to it; the output is sized by the scanned observation count; guard bytes behind every one of
-// these buffers are checked at the end.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <algorithm>
+// these buffers are checked at the end (vlr_bam::guarded / guard_intact).  The session's common state, the wiring of a file into the
+// device reader and the SNV / MNV loci on the device are vlr_bamsession.h's.
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/vlr.h"
-#include "vlr_gpuio.h"
-#include "vlr_bamstream.h"
+#include "vlr_bamsession.h"
 #include "vlr_fragpileup.h"
 
 static_assert(sizeof(vlr_fragpileup_obs) == 56, "observation layout");
@@ -53,15 +46,16 @@ static_assert(sizeof(vlr_fp::AltKey) == 16, "key layout");
 
 namespace vlr_fp {
 
-enum Counter { C_REJECTED, C_BAD, C_FIRST_BAD, C_N };
+using vlr_bam::C_BAD;
+using vlr_bam::C_FIRST_BAD;
+using vlr_bam::C_REJECTED;
+using vlr_bam::kScanThreads;
+enum { K_MEMBERS = 0, K_NAME = 1, K_XA = 2, K_N = 3 };   // the three counts of a record
 constexpr int kThreads = 256;
-constexpr int kScanThreads = 1024;
 constexpr int kLocusThreads = 256;
 constexpr uint32_t kMax = VLR_FRAGPILEUP_MAX_MEMBERS;
 constexpr uint32_t kSentinel = 0xffffffffu;
 constexpr uint16_t kNoRank = 0xffffu;
-constexpr size_t kGuardBytes = 256;
-constexpr int kGuardByte = 0xA5;
 
 __global__ __launch_bounds__(kThreads) void frag_count_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
                                                               vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
@@ -76,27 +70,6 @@ __global__ __launch_bounds__(kThreads) void frag_count_kernel(const uint8_t* __r
     nxa[i] = r.n_xa;
     if (r.cls == vlr_bp::REC_REJECTED) atomicAdd(&counters[C_REJECTED], 1ull);
     if (r.cls == vlr_bp::REC_BAD) { atomicAdd(&counters[C_BAD], 1ull); atomicMin(&counters[C_FIRST_BAD], (unsigned long long)(rec0 + (uint64_t)i)); }
-}
-
-// one workgroup: thread t sums the slice [t * per, (t + 1) * per) of cnt, the sums are scanned in LDS, then the slice's offsets written
-__global__ __launch_bounds__(kScanThreads) void frag_scan_kernel(const uint32_t* __restrict__ cnt, int64_t n, uint64_t* __restrict__ off, uint64_t* __restrict__ total) {
-    __shared__ uint64_t s[2][kScanThreads];
-    const int t = (int)threadIdx.x;
-    const int64_t per = (n + kScanThreads - 1) / kScanThreads;
-    const int64_t lo = std::min<int64_t>((int64_t)t * per, n), hi = std::min<int64_t>(lo + per, n);
-    uint64_t sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += cnt[i];
-    s[0][t] = sum;
-    __syncthreads();
-    int cur = 0;
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        s[cur ^ 1][t] = s[cur][t] + (t >= d ? s[cur][t - d] : 0ull);
-        cur ^= 1;
-        __syncthreads();
-    }
-    uint64_t run = s[cur][t] - sum;   // exclusive
-    for (int64_t i = lo; i < hi; ++i) { off[i] = run; run += cnt[i]; }
-    if (t == kScanThreads - 1) *total = s[cur][t];
 }
 
 __global__ __launch_bounds__(kThreads) void frag_fill_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
@@ -308,119 +281,65 @@ __global__ __launch_bounds__(kLocusThreads) void frag_gather_kernel(const Member
 
 }  // namespace vlr_fp
 
-struct vlr_fragpileup {
-    int device = 0;
+struct vlr_fragpileup : vlr_bam::Session {
     int realign = 0;
     int64_t n_loci = 0;
     int64_t win = 0;
     uint32_t max_mapq = 0;
     uint64_t member_cap = 0, name_cap = 0, key_cap = 0, coeff = 1;
-    size_t window = (size_t)64 << 20;
-    // device state
-    int32_t* d_ref_id = nullptr; int64_t* d_start = nullptr; int32_t* d_len = nullptr; uint8_t* d_kind = nullptr; uint64_t* d_base_off = nullptr;
-    uint8_t *d_refb = nullptr, *d_altb = nullptr;
-    double* d_tables = nullptr;
+    // device state (the record arrays of the base: [K_N][rec_cap] u32 counts and their offsets; d_total[K_N])
+    vlr_bp::DeviceLoci dl;
     vlr_fp::Member* d_members = nullptr;
     uint8_t* d_names = nullptr;
     vlr_fp::AltKey *d_keys = nullptr, *d_major_key = nullptr;
     uint32_t* d_have_key = nullptr;
-    uint32_t *d_cnt = nullptr, *d_nbytes = nullptr, *d_nxa = nullptr; uint64_t *d_off = nullptr, *d_noff = nullptr, *d_xoff = nullptr; size_t rec_cap = 0;
-    unsigned long long* d_counters = nullptr; uint64_t* d_total = nullptr;   // d_total[3]
     uint32_t *d_lcnt = nullptr, *d_cursor = nullptr, *d_nobs = nullptr, *d_major = nullptr, *d_lstatus = nullptr;
     uint64_t *d_loff = nullptr, *d_obsoff = nullptr;
-    vlr_bp::Tables tables{};
-    vlr_bp::Loci loci{};
     // host state
-    uint64_t n_members = 0, n_name_bytes = 0, n_keys = 0, n_records = 0;
-    uint64_t status = 0;
-    int64_t trunc_record = -1;
-    bool collected = false;
+    uint64_t n_members = 0, n_name_bytes = 0, n_keys = 0;
     std::vector<vlr_fragpileup_obs> obs;
     std::vector<vlr_fragpileup_locus> locus_rec;
     int64_t n_too_deep = 0;
-    uint64_t counters[vlr_fp::C_N] = {0, 0, ~0ull};
     double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace vlr_fp {
 using vlr_bam::bfail;
+using vlr_bam::guard_intact;
+using vlr_bam::guarded;
 using vlr_bam::now_s;
-
-#define FP_HIP_OK(call)                                                                          \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) return bfail(VLR_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T> int upload(T*& d, const T* h, size_t n) {
-    FP_HIP_OK(hipMalloc((void**)&d, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n) FP_HIP_OK(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
-    return VLR_OK;
-}
-template <class T> int zeros(T*& d, size_t n) {
-    FP_HIP_OK(hipMalloc((void**)&d, std::max<size_t>(n, 1) * sizeof(T)));
-    FP_HIP_OK(hipMemset((void*)d, 0, std::max<size_t>(n, 1) * sizeof(T)));
-    return VLR_OK;
-}
-// a buffer of n items with guard bytes behind it
-template <class T> int guarded(T*& d, size_t n) {
-    FP_HIP_OK(hipMalloc((void**)&d, n * sizeof(T) + kGuardBytes));
-    FP_HIP_OK(hipMemset((void*)((uint8_t*)d + n * sizeof(T)), kGuardByte, kGuardBytes));
-    return VLR_OK;
-}
-template <class T> int guard_intact(const T* d, size_t n, bool* ok) {
-    uint8_t g[kGuardBytes];
-    FP_HIP_OK(hipMemcpy(g, (const uint8_t*)d + n * sizeof(T), kGuardBytes, hipMemcpyDeviceToHost));
-    for (uint8_t b : g) if (b != (uint8_t)kGuardByte) *ok = false;
-    return VLR_OK;
-}
+using vlr_bam::zeros;
 
 int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
     const uint8_t* d_base; const uint64_t* d_starts;
     int rc = vlr_dev_file_split_view(df, &d_base, &d_starts);
-    if (rc != VLR_OK) return rc;
-    if ((size_t)n > s->rec_cap) {
-        FP_HIP_OK(hipStreamSynchronize(st));
-        void* old[] = {s->d_cnt, s->d_nbytes, s->d_nxa, s->d_off, s->d_noff, s->d_xoff};
-        for (void* q : old) if (q) (void)hipFree(q);
-        s->d_cnt = s->d_nbytes = s->d_nxa = nullptr; s->d_off = s->d_noff = s->d_xoff = nullptr; s->rec_cap = 0;
-        const size_t cap = (size_t)n + (size_t)n / 4 + 1024;
-        FP_HIP_OK(hipMalloc((void**)&s->d_cnt, cap * 4));
-        FP_HIP_OK(hipMalloc((void**)&s->d_nbytes, cap * 4));
-        FP_HIP_OK(hipMalloc((void**)&s->d_off, cap * 8));
-        FP_HIP_OK(hipMalloc((void**)&s->d_noff, cap * 8));
-        FP_HIP_OK(hipMalloc((void**)&s->d_nxa, cap * 4));
-        FP_HIP_OK(hipMalloc((void**)&s->d_xoff, cap * 8));
-        s->rec_cap = cap;
-    }
+    if (rc != VLR_OK || (rc = vlr_bam::reserve_records<uint32_t>(*s, n, K_N, st)) != VLR_OK) return rc;
     const double t0 = now_s();
     const unsigned blocks = (unsigned)((n + kThreads - 1) / kThreads);
     const uint64_t rec0 = s->n_records;
-    hipLaunchKernelGGL(frag_count_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->tables, s->loci, s->realign, s->win, s->coeff, s->d_cnt, s->d_nbytes,
-                       s->d_nxa, s->d_counters);
-    hipLaunchKernelGGL(frag_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, s->d_cnt, n, s->d_off, s->d_total);
-    hipLaunchKernelGGL(frag_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, s->d_nbytes, n, s->d_noff, s->d_total + 1);
-    hipLaunchKernelGGL(frag_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, s->d_nxa, n, s->d_xoff, s->d_total + 2);
-    uint64_t total[3] = {0, 0, 0};
-    FP_HIP_OK(hipMemcpyAsync(total, s->d_total, 24, hipMemcpyDeviceToHost, st));
-    FP_HIP_OK(hipStreamSynchronize(st));
-    FP_HIP_OK(hipGetLastError());
+    const size_t stride = s->rec_cap;
+    uint32_t *d_cnt = (uint32_t*)s->d_cnt, *d_nbytes = d_cnt + K_NAME * stride, *d_nxa = d_cnt + K_XA * stride;
+    hipLaunchKernelGGL(frag_count_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt, d_nbytes,
+                       d_nxa, s->d_counters);
+    uint64_t total[K_N] = {0, 0, 0};
+    if ((rc = vlr_bam::scan_records<uint32_t>(*s, n, K_N, total, st)) != VLR_OK) return rc;
     // once a buffer has overflowed nothing more is written: the session only counts on
     const bool fits = s->n_members <= s->member_cap && s->n_name_bytes <= s->name_cap && s->n_keys <= s->key_cap;
-    if (total[0] && fits && s->n_members < s->member_cap) {
-        hipLaunchKernelGGL(frag_fill_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->tables, s->loci, s->realign, s->win, s->coeff, s->d_cnt, s->d_nbytes,
-                           s->d_off, s->d_noff, s->d_xoff, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys, s->key_cap, s->d_members, s->d_names,
-                           s->d_keys, s->d_lcnt);
-        FP_HIP_OK(hipStreamSynchronize(st));
-        FP_HIP_OK(hipGetLastError());
+    if (total[K_MEMBERS] && fits && s->n_members < s->member_cap) {
+        hipLaunchKernelGGL(frag_fill_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt, d_nbytes,
+                           s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys, s->key_cap,
+                           s->d_members, s->d_names, s->d_keys, s->d_lcnt);
+        VLR_HIP_OK(hipStreamSynchronize(st));
+        VLR_HIP_OK(hipGetLastError());
     }
-    s->n_members += total[0];
-    s->n_name_bytes += total[1];
-    s->n_keys += total[2];
+    s->n_members += total[K_MEMBERS];
+    s->n_name_bytes += total[K_NAME];
+    s->n_keys += total[K_XA];
     s->n_records += (uint64_t)n;
     s->t[3] += now_s() - t0;
     return VLR_OK;
 }
+
 
 int fragment_pass(vlr_fragpileup* s) {
     const size_t nm = (size_t)s->n_members, nl = (size_t)s->n_loci;
@@ -434,23 +353,23 @@ int fragment_pass(vlr_fragpileup* s) {
     step(guarded(d_tmp, nm));
     auto body = [&]() -> int {
         uint64_t total_obs = 0;
-        hipLaunchKernelGGL(frag_scan_kernel, dim3(1), dim3(kScanThreads), 0, 0, s->d_lcnt, (int64_t)nl, s->d_loff, s->d_total);
+        hipLaunchKernelGGL(vlr_bam::scan_kernel<uint32_t>, dim3(1), dim3(kScanThreads), 0, 0, s->d_lcnt, (int64_t)nl, (int64_t)0, s->d_loff, s->d_total);
         hipLaunchKernelGGL(frag_scatter_kernel, dim3((unsigned)((nm + kThreads - 1) / kThreads)), dim3(kThreads), 0, 0, s->d_members, (uint64_t)nm, s->n_loci, s->d_loff,
                            s->d_lcnt, s->d_cursor, d_perm);
         hipLaunchKernelGGL(frag_locus_kernel, dim3((unsigned)nl), dim3(kLocusThreads), 0, 0, s->d_members, s->d_names, s->d_keys, d_perm, s->d_loff, s->d_lcnt, s->max_mapq,
                            d_tmp, d_left, d_right, d_rank, s->d_nobs, s->d_major, s->d_major_key, s->d_have_key, s->d_lstatus);
-        hipLaunchKernelGGL(frag_scan_kernel, dim3(1), dim3(kScanThreads), 0, 0, s->d_nobs, (int64_t)nl, s->d_obsoff, s->d_total + 1);
-        FP_HIP_OK(hipDeviceSynchronize());
-        FP_HIP_OK(hipGetLastError());
-        FP_HIP_OK(hipMemcpy(&total_obs, s->d_total + 1, 8, hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(vlr_bam::scan_kernel<uint32_t>, dim3(1), dim3(kScanThreads), 0, 0, s->d_nobs, (int64_t)nl, (int64_t)0, s->d_obsoff, s->d_total + 1);
+        VLR_HIP_OK(hipDeviceSynchronize());
+        VLR_HIP_OK(hipGetLastError());
+        VLR_HIP_OK(hipMemcpy(&total_obs, s->d_total + 1, 8, hipMemcpyDeviceToHost));
         if (total_obs > nm) return bfail(VLR_ERR_HIP, "vlr_fragpileup_result: more observations than members");
         // the output is sized by the observations, not by the members
         int r = guarded(d_out, (size_t)total_obs);
         if (r != VLR_OK) return r;
         hipLaunchKernelGGL(frag_gather_kernel, dim3((unsigned)nl), dim3(kLocusThreads), 0, 0, s->d_members, s->d_keys, d_tmp, d_left, d_right, d_rank, s->d_loff, s->d_lcnt,
                            s->d_nobs, s->d_obsoff, s->d_major, s->d_major_key, s->d_have_key, total_obs, d_out);
-        FP_HIP_OK(hipDeviceSynchronize());
-        FP_HIP_OK(hipGetLastError());
+        VLR_HIP_OK(hipDeviceSynchronize());
+        VLR_HIP_OK(hipGetLastError());
         bool ok = true;
         r = guard_intact(d_perm, nm, &ok);
         if (r == VLR_OK) r = guard_intact(d_rank, nm, &ok);
@@ -462,14 +381,14 @@ int fragment_pass(vlr_fragpileup* s) {
         if (!ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
         const double t1 = now_s();
         s->obs.resize((size_t)total_obs);
-        if (total_obs) FP_HIP_OK(hipMemcpy(s->obs.data(), d_out, (size_t)total_obs * sizeof(vlr_fragpileup_obs), hipMemcpyDeviceToHost));
+        if (total_obs) VLR_HIP_OK(hipMemcpy(s->obs.data(), d_out, (size_t)total_obs * sizeof(vlr_fragpileup_obs), hipMemcpyDeviceToHost));
         std::vector<uint32_t> lcnt(nl), nobs(nl), major(nl), lst(nl);
         std::vector<uint64_t> ooff(nl);
-        FP_HIP_OK(hipMemcpy(lcnt.data(), s->d_lcnt, nl * 4, hipMemcpyDeviceToHost));
-        FP_HIP_OK(hipMemcpy(nobs.data(), s->d_nobs, nl * 4, hipMemcpyDeviceToHost));
-        FP_HIP_OK(hipMemcpy(major.data(), s->d_major, nl * 4, hipMemcpyDeviceToHost));
-        FP_HIP_OK(hipMemcpy(lst.data(), s->d_lstatus, nl * 4, hipMemcpyDeviceToHost));
-        FP_HIP_OK(hipMemcpy(ooff.data(), s->d_obsoff, nl * 8, hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(lcnt.data(), s->d_lcnt, nl * 4, hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(nobs.data(), s->d_nobs, nl * 4, hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(major.data(), s->d_major, nl * 4, hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(lst.data(), s->d_lstatus, nl * 4, hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(ooff.data(), s->d_obsoff, nl * 8, hipMemcpyDeviceToHost));
         for (size_t k = 0; k < nl; ++k) {
             s->locus_rec[k] = vlr_fragpileup_locus{(int64_t)ooff[k], lcnt[k], nobs[k], major[k], lst[k]};
             if (lst[k]) ++s->n_too_deep;
@@ -497,21 +416,10 @@ int vlr_fragpileup_open(int device, int64_t n_loci, const int32_t* ref_id, const
         return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_open: bad argument");
     if (max_read_len <= 0) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_open: max_read_len must be positive");
     *out = nullptr;
-    std::vector<uint64_t> base_off((size_t)n_loci + 1, 0);
-    for (int64_t k = 0; k < n_loci; ++k) {
-        const bool snv = kind[k] == VLR_BASEPILEUP_SNV;
-        if ((!snv && kind[k] != VLR_BASEPILEUP_MNV) || ref_id[k] < 0 || start[k] < 0 || (snv ? len[k] != 1 : (len[k] < 2 || len[k] > VLR_BASEPILEUP_MAX_LEN)))
-            return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_open: locus %lld: kind %d with %d bases (an SNV has 1, an MNV 2 .. %d)", (long long)k, (int)kind[k],
-                         (int)len[k], VLR_BASEPILEUP_MAX_LEN);
-        if (k > 0 && (ref_id[k] < ref_id[k - 1] || (ref_id[k] == ref_id[k - 1] && start[k] < start[k - 1])))
-            return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_open: loci are not sorted by (ref_id, start) at %lld", (long long)k);
-        base_off[(size_t)k + 1] = base_off[(size_t)k] + (uint64_t)len[k];
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || ndev <= device) return bfail(VLR_ERR_NO_DEVICE, "no HIP device %d (the engine has no CPU path)", device);
-    FP_HIP_OK(hipSetDevice(device));
+    std::vector<uint64_t> base_off;
+    int rc = vlr_bp::check_snv_mnv_loci("vlr_fragpileup_open", n_loci, ref_id, start, len, kind, base_off);
+    if (rc != VLR_OK || (rc = vlr_bam::use_device(device)) != VLR_OK) return rc;
     vlr_fragpileup* s = new vlr_fragpileup();
-    s->device = device;
     s->realign = realign_indel_reads ? 1 : 0;
     s->n_loci = n_loci;
     s->win = window;
@@ -521,22 +429,10 @@ int vlr_fragpileup_open(int device, int64_t n_loci, const int32_t* ref_id, const
     s->key_cap = (uint64_t)key_capacity;
     s->coeff = 10ull * (uint64_t)max_read_len;
     s->locus_rec.assign((size_t)n_loci, vlr_fragpileup_locus{0, 0, 0, VLR_BASEPILEUP_NO_READ_POSITION, 0});
-    if (window_bytes > 0) s->window = (size_t)window_bytes;
-    std::vector<double> tab(3 * 256);
-    vlr_bp::fill_tables(tab.data(), tab.data() + 256, tab.data() + 512);
-    const size_t nb = (size_t)base_off[(size_t)n_loci], nl = (size_t)n_loci;
-    int rc = VLR_OK;
+    const size_t nl = (size_t)n_loci;
     auto step = [&](int r) { if (rc == VLR_OK) rc = r; };
-    step(upload(s->d_ref_id, ref_id, nl));
-    step(upload(s->d_start, start, nl));
-    step(upload(s->d_len, len, nl));
-    step(upload(s->d_kind, kind, nl));
-    step(upload(s->d_base_off, base_off.data(), nl + 1));
-    step(upload(s->d_refb, ref_bases, nb));
-    step(upload(s->d_altb, alt_bases, nb));
-    step(upload(s->d_tables, tab.data(), tab.size()));
-    step(upload(s->d_counters, (const unsigned long long*)s->counters, (size_t)C_N));
-    step(zeros(s->d_total, 3));
+    step(vlr_bam::open_session(*s, device, window_bytes, K_N));
+    step(s->dl.upload(n_loci, ref_id, start, len, kind, base_off, ref_bases, alt_bases));
     step(zeros(s->d_major_key, nl)); step(zeros(s->d_have_key, nl));
     step(zeros(s->d_lcnt, nl)); step(zeros(s->d_cursor, nl)); step(zeros(s->d_nobs, nl)); step(zeros(s->d_major, nl)); step(zeros(s->d_lstatus, nl));
     step(zeros(s->d_loff, nl)); step(zeros(s->d_obsoff, nl));
@@ -544,41 +440,29 @@ int vlr_fragpileup_open(int device, int64_t n_loci, const int32_t* ref_id, const
     step(guarded(s->d_names, (size_t)s->name_cap));
     step(guarded(s->d_keys, (size_t)s->key_cap));
     if (rc != VLR_OK) { vlr_fragpileup_close(s); return rc; }
-    s->tables = vlr_bp::Tables{s->d_tables, s->d_tables + 256, s->d_tables + 512, vlr_bp::ln_confusion(), vlr_bp::ln_any()};
-    s->loci = vlr_bp::Loci{n_loci, s->d_ref_id, s->d_start, s->d_len, s->d_kind, s->d_base_off, s->d_refb, s->d_altb};
     *out = s;
     return VLR_OK;
 }
 
 int vlr_fragpileup_add_bam(vlr_fragpileup* s, const char* bam_path) {
-    using namespace vlr_fp;
-    if (!s || !bam_path) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_add_bam: null");
-    if (s->collected) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_add_bam: the result was already read");
-    if (s->trunc_record >= 0) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_add_bam: the file before ended inside a record");
-    if (hipSetDevice(s->device) != hipSuccess) return bfail(VLR_ERR_HIP, "hipSetDevice(%d) failed", s->device);
-    vlr_bam::BamStream b;
-    b.device = s->device;
-    b.window = &s->window;
-    b.t_read = &s->t[0]; b.t_feed = &s->t[1]; b.t_split = &s->t[2]; b.t_inflate = &s->t[6]; b.t_total = &s->t[5];
-    b.on_chunk = [s](vlr_dev_file* df, int64_t n, uint64_t, const std::vector<std::string>&, const char*, void* st) { return run_chunk(s, df, n, (hipStream_t)st); };
-    // a file that ends inside a record: malformed input, reported in the status word; the records in front of it count
-    b.on_truncated = [s](uint64_t) { s->trunc_record = (int64_t)s->n_records; return (int)VLR_OK; };
-    return vlr_bam::stream_bam(b, bam_path);
+    if (!s) return vlr_bam::bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_add_bam: null");
+    return vlr_bam::add_bam(*s, bam_path, "vlr_fragpileup_add_bam", {&s->t[0], &s->t[1], &s->t[2], &s->t[6], &s->t[5]}, nullptr,
+                            [s](vlr_dev_file* df, int64_t n, hipStream_t st) { return vlr_fp::run_chunk(s, df, n, st); });
 }
 
 int vlr_fragpileup_result(vlr_fragpileup* s, vlr_fragpileup_counts* r) {
     using namespace vlr_fp;
     if (!s || !r) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_result: null");
-    FP_HIP_OK(hipSetDevice(s->device));
+    VLR_HIP_OK(hipSetDevice(s->device));
     if (!s->collected) {
-        FP_HIP_OK(hipMemcpy(s->counters, s->d_counters, sizeof s->counters, hipMemcpyDeviceToHost));
         bool ok = true;
-        int rc = guard_intact(s->d_members, (size_t)s->member_cap, &ok);
+        int rc = vlr_bam::read_counters(*s);
+        if (rc == VLR_OK) rc = guard_intact(s->d_members, (size_t)s->member_cap, &ok);
         if (rc == VLR_OK) rc = guard_intact(s->d_names, (size_t)s->name_cap, &ok);
         if (rc == VLR_OK) rc = guard_intact(s->d_keys, (size_t)s->key_cap, &ok);
         if (rc != VLR_OK) return rc;
         if (!ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
-        if (s->counters[C_BAD] || s->trunc_record >= 0) s->status |= VLR_FRAGPILEUP_BAD_RECORD;
+        if (vlr_bam::bad_record_seen(*s)) s->status |= VLR_FRAGPILEUP_BAD_RECORD;
         if (s->n_members > s->member_cap) s->status |= VLR_FRAGPILEUP_MEMBER_OVERFLOW;
         if (s->n_name_bytes > s->name_cap) s->status |= VLR_FRAGPILEUP_NAME_OVERFLOW;
         if (s->n_keys > s->key_cap) s->status |= VLR_FRAGPILEUP_KEY_OVERFLOW;
@@ -600,8 +484,7 @@ int vlr_fragpileup_result(vlr_fragpileup* s, vlr_fragpileup_counts* r) {
     r->needed_members = (int64_t)s->n_members;
     r->needed_name_bytes = (int64_t)s->n_name_bytes;
     r->needed_keys = (int64_t)s->n_keys;
-    r->first_bad_record = s->counters[C_BAD] ? (int64_t)s->counters[C_FIRST_BAD] : -1;
-    if (s->trunc_record >= 0 && (r->first_bad_record < 0 || s->trunc_record < r->first_bad_record)) r->first_bad_record = s->trunc_record;
+    r->first_bad_record = vlr_bam::first_bad_record(*s);
     for (int k = 0; k < 8; ++k) r->seconds[k] = s->t[k];
     return VLR_OK;
 }
@@ -619,10 +502,12 @@ int vlr_fragpileup_read(vlr_fragpileup* s, vlr_fragpileup_obs* obs, int64_t n_ob
 void vlr_fragpileup_close(vlr_fragpileup* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    void* p[] = {s->d_ref_id, s->d_start, s->d_len, s->d_kind, s->d_base_off, s->d_refb, s->d_altb, s->d_tables, s->d_members, s->d_names, s->d_keys, s->d_major_key, s->d_have_key, s->d_cnt, s->d_nbytes,
-                 s->d_nxa, s->d_off, s->d_noff, s->d_xoff, s->d_counters, s->d_total, s->d_lcnt, s->d_cursor, s->d_nobs, s->d_major, s->d_lstatus, s->d_loff, s->d_obsoff};
+    vlr_bam::close_session(*s);
+    s->dl.free();
+    void* p[] = {s->d_members, s->d_names, s->d_keys, s->d_major_key, s->d_have_key, s->d_lcnt, s->d_cursor, s->d_nobs, s->d_major, s->d_lstatus, s->d_loff, s->d_obsoff};
     for (void* q : p) if (q) (void)hipFree(q);
     delete s;
 }
 
 }  // extern "C"
+

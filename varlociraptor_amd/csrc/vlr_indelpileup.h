@@ -22,6 +22,7 @@
 namespace vlr_ip {
 
 using vlr_bp::ld32;
+using vlr_bp::lower_bound;
 using vlr_bp::Rec;
 using vlr_bp::RecClass;
 using vlr_bp::REC_BAD;
@@ -145,17 +146,6 @@ VLR_BP_HD inline Region candidate_region(const Rec& r, int64_t locus_start, int6
     g.ref_begin = min64(max64(0, breakpoint - ref_window), g.ref_end);
     g.read_end = max64(g.read_end, g.read_begin);
     return g;
-}
-
-// first locus at or behind (ref_id, pos) in the sorted loci
-VLR_BP_HD inline int64_t lower_bound(const Loci& L, int32_t ref_id, int64_t pos) {
-    int64_t lo = 0, hi = L.n;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        const bool less = L.ref_id[mid] < ref_id || (L.ref_id[mid] == ref_id && L.start[mid] < pos);
-        if (less) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // Byte k of a window.  WB_READ_BASE: base begin + k of the 4-bit SEQ at src (src_len = l_seq), decoded — upper case by construction;

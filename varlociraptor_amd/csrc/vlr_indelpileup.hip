@@ -7,7 +7,8 @@
 //   indelpileup_count_kernel    one record per thread: decode and validate (vlr_bp::decode), find the loci the alignment with its clips
 //                               overlaps, candidate region of each -> evidences and x / y bytes of the record (nothing else is written);
 //                               rejected and bad records go to integer counters (sums and a minimum: order-independent)
-//   indelpileup_scan_kernel     one workgroup per count array: exclusive prefix sums -> offsets, the chunk's totals
+//   vlr_bam::scan_kernel        one workgroup per count array: exclusive prefix sums -> offsets, the chunk's totals (vlr_bamsession.h,
+//                               u64 counts)
 //   indelpileup_fill_kernel     one record per thread: the same text again writes the evidence descriptors (the hits, scores unset) at
 //                               hits[hit0 + ev_off[i] ...) and the x_offset / y_offset entries of pairs 2e (ref allele, read) and 2e + 1
 //                               (alt allele, read) from the scanned byte offsets
@@ -19,25 +20,18 @@
 // A hit's place and a pair's bytes are functions of the record order alone: no atomics decide a position, and how the file was cut
 // into feeds and chunks (window_bytes) cannot change the output.  The pair offsets are uint32: a chunk whose x or y bytes pass
 // kPairByteLimit is processed in record sub-ranges cut at the scanned offsets.  The hits leave the device record-major;
-// vlr_indelpileup_result puts them locus-major with a stable counting sort on the host.
+// vlr_indelpileup_result puts them locus-major with a stable counting sort on the host (vlr_bam::locus_major, which also keeps the
+// permutation for the kept pairs).  The session's common state, the wiring of a file into the device reader and the buffer helpers are
+// vlr_bamsession.h's; the contigs come through vlr_bam::load_contig (vlr_bamstream.h), upper-cased.
 //
 // Bounds: see vlr_indelpileup.h.  The fill pass runs only when all evidences of the chunk fit the hit buffer and writes hits[k] only for
-// k < capacity; guard words behind the buffer are checked at the end.  The pair buffers are sized from the scanned totals before the
+// k < capacity; guard bytes behind the buffer are checked at the end.  The pair buffers are sized from the scanned totals before the
 // fill pass, and the gather pass writes window k of a pair only below the pair's own length.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <string>
-#include <vector>
 
-#include "../../include/vlr.h"
-#include "vlr_gpuio.h"
-#include "vlr_bamstream.h"
+#include "vlr_bamsession.h"
 #include "vlr_indelpileup.h"
 
 static_assert(sizeof(vlr_indelpileup_hit) == 64, "hit layout");
@@ -49,13 +43,12 @@ extern "C" int vlr_launch_homopoly_kernel(const vlr_realign_batch_desc* b, const
 
 namespace vlr_ip {
 
-enum Counter { C_REJECTED, C_BAD, C_FIRST_BAD, C_N };
+using vlr_bam::C_BAD;
+using vlr_bam::C_FIRST_BAD;
+using vlr_bam::C_REJECTED;
 enum { K_EV = 0, K_X = 1, K_Y = 2, K_N = 3 };   // the three counts of a record
 constexpr int kThreads = 256;
-constexpr int kScanThreads = 1024;
 constexpr int kEditBand = 4;                 // pairhmm.rs:20
-constexpr size_t kGuardHits = 4;             // guard words behind the hit buffer: kGuardHits * sizeof(hit) bytes of kGuardByte
-constexpr int kGuardByte = 0xA5;
 constexpr uint64_t kPairByteLimit = 1ull << 31;
 
 // where the windows of an evidence come from (chunk-local, one per evidence of the sub-range)
@@ -75,30 +68,6 @@ __global__ __launch_bounds__(kThreads) void indelpileup_count_kernel(const uint8
     cnt[K_Y * stride + i] = r.y_bytes;
     if (r.cls == REC_REJECTED) atomicAdd(&counters[C_REJECTED], 1ull);
     if (r.cls == REC_BAD) { atomicAdd(&counters[C_BAD], 1ull); atomicMin(&counters[C_FIRST_BAD], (unsigned long long)(rec0 + (uint64_t)i)); }
-}
-
-// workgroup b scans count array b: thread t sums the slice [t * per, (t + 1) * per), the sums are scanned in LDS, then the slice's offsets written
-__global__ __launch_bounds__(kScanThreads) void indelpileup_scan_kernel(const uint64_t* __restrict__ cnt_all, int64_t n, int64_t stride, uint64_t* __restrict__ off_all,
-                                                                        uint64_t* __restrict__ total) {
-    __shared__ uint64_t s[2][kScanThreads];
-    const uint64_t* cnt = cnt_all + (int64_t)blockIdx.x * stride;
-    uint64_t* off = off_all + (int64_t)blockIdx.x * stride;
-    const int t = (int)threadIdx.x;
-    const int64_t per = (n + kScanThreads - 1) / kScanThreads;
-    const int64_t lo = std::min<int64_t>((int64_t)t * per, n), hi = std::min<int64_t>(lo + per, n);
-    uint64_t sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += cnt[i];
-    s[0][t] = sum;
-    __syncthreads();
-    int cur = 0;
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        s[cur ^ 1][t] = s[cur][t] + (t >= d ? s[cur][t - d] : 0ull);
-        cur ^= 1;
-        __syncthreads();
-    }
-    uint64_t run = s[cur][t] - sum;   // exclusive
-    for (int64_t i = lo; i < hi; ++i) { off[i] = run; run += cnt[i]; }
-    if (t == kScanThreads - 1) total[blockIdx.x] = s[cur][t];
 }
 
 // records [i0, i1) of the chunk: their evidences are [e0, e0 + n_ev) of the chunk and go to hits[hit0 + (e - e0)], their pair bytes
@@ -176,120 +145,44 @@ __global__ __launch_bounds__(kThreads) void indelpileup_collect_kernel(const dou
     h->dist_ref = dist[2 * e]; h->dist_alt = dist[2 * e + 1];
 }
 
-struct FaiEntry { uint64_t len, off, lb, lw; };
-
 }  // namespace vlr_ip
 
-struct vlr_indelpileup {
-    int device = 0;
+struct vlr_indelpileup : vlr_bam::Session {
     int window = 64, mode = VLR_INDELPILEUP_EXACT;
     bool keep_pairs = false;
     double gap[4] = {0, 0, 0, 0};
     double hop[16];
     int64_t n_loci = 0;
     uint64_t capacity = 0;
-    size_t window_bytes = (size_t)64 << 20;
     uint64_t pair_byte_limit = vlr_ip::kPairByteLimit;
     std::string fasta;
-    std::map<std::string, vlr_ip::FaiEntry> fai;
-    std::vector<int32_t> h_ref_id;                                          // of the loci
-    std::map<std::string, std::pair<uint8_t*, int64_t>> contigs;            // uploaded contigs by name
-    // device state
+    vlr_bam::Fai fai;
+    std::vector<int32_t> h_ref_id;   // of the loci
+    vlr_bam::Contigs contigs;        // uploaded contigs by name
+    // device state (the record arrays of the base: [K_N][rec_cap] u64 counts and their offsets; d_total[K_N])
     int32_t* d_ref_id = nullptr; int64_t *d_start = nullptr, *d_end = nullptr; uint64_t* d_alt_off = nullptr; uint8_t* d_altb = nullptr;
     const uint8_t** d_ctg = nullptr; int64_t* d_ctg_len = nullptr; size_t ctg_cap = 0;
     vlr_indelpileup_hit* d_hits = nullptr;
-    uint64_t *d_cnt = nullptr, *d_off = nullptr; size_t rec_cap = 0;        // [K_N][rec_cap]
-    unsigned long long* d_counters = nullptr; uint64_t* d_total = nullptr;
     vlr_ip::Src* d_src = nullptr; uint32_t *d_xoff = nullptr, *d_yoff = nullptr; int32_t *d_band = nullptr, *d_dist = nullptr; double* d_lnp = nullptr; size_t ev_cap = 0;
     uint8_t *d_xb = nullptr, *d_yb = nullptr, *d_yq = nullptr; size_t x_cap = 0, y_cap = 0;
     vlr_ip::Loci loci{};
     // host state
     uint64_t n_total = 0;        // evidences the input produced so far
-    uint64_t n_records = 0;      // records of the files given so far
     uint64_t x_total = 0, y_total = 0;
-    uint64_t status = 0;
     bool overflow = false;
-    int64_t trunc_record = -1;   // a file ended inside this record
     std::vector<vlr_indelpileup_hit> hits;
     std::vector<uint64_t> perm;  // hits[k] is evidence perm[k] of the record-major order
     // kept pairs, record-major: per pair its lengths, the bytes one behind the other
     std::vector<uint32_t> p_xlen, p_ylen; std::vector<int32_t> p_band; std::vector<uint8_t> p_xb, p_yb, p_yq;
-    bool collected = false;
-    uint64_t counters[vlr_ip::C_N] = {0, 0, ~0ull};
     double t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace vlr_ip {
 using vlr_bam::bfail;
+using vlr_bam::grow;
 using vlr_bam::now_s;
+using vlr_bam::upload;
 
-#define IP_HIP_OK(call)                                                                          \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) return bfail(e_ == hipErrorOutOfMemory ? VLR_ERR_OUT_OF_MEMORY : VLR_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T> int upload(T*& d, const T* h, size_t n) {
-    IP_HIP_OK(hipMalloc((void**)&d, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n) IP_HIP_OK(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
-    return VLR_OK;
-}
-
-// device buffers only grow (the stream is idle when this runs: every stage below ends with a synchronisation)
-template <class T> int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return VLR_OK;
-    if (p) (void)hipFree((void*)p);
-    p = nullptr; cap = 0;
-    const size_t ncap = need + need / 4 + 1024;
-    IP_HIP_OK(hipMalloc((void**)&p, ncap * sizeof(T)));
-    cap = ncap;
-    return VLR_OK;
-}
-
-int read_fai(vlr_indelpileup* s) {
-    const std::string path = s->fasta + ".fai";
-    FILE* f = fopen(path.c_str(), "r");
-    if (!f) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: no .fai index (index the reference with samtools faidx)", s->fasta.c_str());
-    char line[4096];
-    while (fgets(line, sizeof line, f)) {
-        char name[2048];
-        unsigned long long a, b, c, d;
-        if (sscanf(line, "%2047[^\t]\t%llu\t%llu\t%llu\t%llu", name, &a, &b, &c, &d) == 5 && c > 0 && d >= c) s->fai[name] = {a, b, c, d};
-    }
-    fclose(f);
-    return VLR_OK;
-}
-
-// the bases of one contig through the .fai, upper-cased (the reference's buffer hands out upper case), on the device
-int load_contig(vlr_indelpileup* s, const std::string& name, const char* bam, std::pair<uint8_t*, int64_t>& out) {
-    auto it = s->contigs.find(name);
-    if (it != s->contigs.end()) { out = it->second; return VLR_OK; }
-    auto e = s->fai.find(name);
-    if (e == s->fai.end()) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: contig %s (of %s) is missing from the reference", s->fasta.c_str(), name.c_str(), bam);
-    const FaiEntry& x = e->second;
-    std::vector<uint8_t> seq(x.len);
-    if (x.len) {
-        const uint64_t nlines = (x.len - 1) / x.lb + 1;
-        const uint64_t raw_n = (nlines - 1) * x.lw + (x.len - (nlines - 1) * x.lb);
-        std::vector<uint8_t> raw(raw_n);
-        FILE* f = fopen(s->fasta.c_str(), "rb");
-        if (!f) return bfail(VLR_ERR_INVALID_ARGUMENT, "cannot open %s", s->fasta.c_str());
-        const bool ok = fseeko(f, (off_t)x.off, SEEK_SET) == 0 && fread(raw.data(), 1, raw_n, f) == raw_n;
-        fclose(f);
-        if (!ok) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: contig %s shorter than its .fai entry", s->fasta.c_str(), name.c_str());
-        for (uint64_t l = 0, k = 0; l < nlines; ++l) {
-            const uint64_t m = std::min<uint64_t>(x.lb, x.len - k);
-            memcpy(seq.data() + k, raw.data() + l * x.lw, m);
-            k += m;
-        }
-        for (auto& c : seq) if (c >= 'a' && c <= 'z') c = (uint8_t)(c - 32);
-    }
-    uint8_t* d = nullptr;
-    IP_HIP_OK(hipMalloc((void**)&d, x.len + 1));
-    if (x.len) IP_HIP_OK(hipMemcpy(d, seq.data(), x.len, hipMemcpyHostToDevice));
-    out = s->contigs[name] = {d, (int64_t)x.len};
-    return VLR_OK;
-}
 
 // the contig table of a file: entry k = contig k of its header when a locus lies on it
 int on_header(vlr_indelpileup* s, const std::vector<std::string>& names, const char* path) {
@@ -299,10 +192,10 @@ int on_header(vlr_indelpileup* s, const std::vector<std::string>& names, const c
     for (int32_t id : s->h_ref_id) {
         if ((size_t)id >= n) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: a locus lies on reference id %d, the header has %zu contigs", path, (int)id, n);
         if (len[(size_t)id] >= 0) continue;
-        std::pair<uint8_t*, int64_t> c;
-        const int rc = load_contig(s, names[(size_t)id], path, c);
+        std::pair<uint8_t*, uint64_t> c;
+        const int rc = vlr_bam::load_contig(s->fasta, s->fai, s->contigs, names[(size_t)id], path, true, c);
         if (rc != VLR_OK) return rc;
-        ctg[(size_t)id] = c.first; len[(size_t)id] = c.second;
+        ctg[(size_t)id] = c.first; len[(size_t)id] = (int64_t)c.second;
     }
     if (n + 1 > s->ctg_cap) {
         size_t c1 = s->ctg_cap, c2 = s->ctg_cap;
@@ -310,16 +203,16 @@ int on_header(vlr_indelpileup* s, const std::vector<std::string>& names, const c
         if ((rc = grow(s->d_ctg, c1, n + 1)) != VLR_OK || (rc = grow(s->d_ctg_len, c2, n + 1)) != VLR_OK) return rc;
         s->ctg_cap = std::min(c1, c2);
     }
-    IP_HIP_OK(hipMemcpy((void*)s->d_ctg, ctg.data(), (n + 1) * sizeof(uint8_t*), hipMemcpyHostToDevice));
-    IP_HIP_OK(hipMemcpy(s->d_ctg_len, len.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    VLR_HIP_OK(hipMemcpy((void*)s->d_ctg, ctg.data(), (n + 1) * sizeof(uint8_t*), hipMemcpyHostToDevice));
+    VLR_HIP_OK(hipMemcpy(s->d_ctg_len, len.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     s->loci.n_refs = (int64_t)n;
     s->loci.ctg_len = s->d_ctg_len;
     return VLR_OK;
 }
 
 int sync_stage(hipStream_t st, double& t, double& t0) {
-    IP_HIP_OK(hipStreamSynchronize(st));
-    IP_HIP_OK(hipGetLastError());
+    VLR_HIP_OK(hipStreamSynchronize(st));
+    VLR_HIP_OK(hipGetLastError());
     const double now = now_s();
     t += now - t0;
     t0 = now;
@@ -350,7 +243,7 @@ int run_range(vlr_indelpileup* s, const uint8_t* d_base, const uint64_t* d_start
     const int64_t stride = (int64_t)s->rec_cap;
     const unsigned rec_blocks = (unsigned)((g.i1 - g.i0 + kThreads - 1) / kThreads);
     const uint64_t hit0 = s->n_total;
-    hipLaunchKernelGGL(indelpileup_fill_kernel, dim3(rec_blocks), dim3(kThreads), 0, st, d_base, d_starts, rec0, s->loci, s->window, s->d_cnt, s->d_off, stride, g, hit0,
+    hipLaunchKernelGGL(indelpileup_fill_kernel, dim3(rec_blocks), dim3(kThreads), 0, st, d_base, d_starts, rec0, s->loci, s->window, (const uint64_t*)s->d_cnt, s->d_off, stride, g, hit0,
                        s->capacity, s->d_hits, s->d_src, s->d_xoff, s->d_yoff, s->d_band);
     const unsigned waves_per_block = kThreads / 64;
     hipLaunchKernelGGL(indelpileup_gather_kernel, dim3((unsigned)((ne + waves_per_block - 1) / waves_per_block)), dim3(kThreads), 0, st, d_base, (uint64_t)ne,
@@ -378,13 +271,13 @@ int run_range(vlr_indelpileup* s, const uint8_t* d_base, const uint64_t* d_start
         const size_t at = s->p_xlen.size(), ax = s->p_xb.size(), ay = s->p_yb.size();
         s->p_xlen.resize(at + np); s->p_ylen.resize(at + np); s->p_band.resize(at + np);
         s->p_xb.resize(ax + (size_t)g.x_bytes); s->p_yb.resize(ay + (size_t)g.y_bytes); s->p_yq.resize(ay + (size_t)g.y_bytes);
-        IP_HIP_OK(hipMemcpyAsync(xo.data(), s->d_xoff, (np + 1) * 4, hipMemcpyDeviceToHost, st));
-        IP_HIP_OK(hipMemcpyAsync(yo.data(), s->d_yoff, (np + 1) * 4, hipMemcpyDeviceToHost, st));
-        IP_HIP_OK(hipMemcpyAsync(s->p_band.data() + at, s->d_band, np * 4, hipMemcpyDeviceToHost, st));
-        if (g.x_bytes) IP_HIP_OK(hipMemcpyAsync(s->p_xb.data() + ax, s->d_xb, (size_t)g.x_bytes, hipMemcpyDeviceToHost, st));
-        if (g.y_bytes) IP_HIP_OK(hipMemcpyAsync(s->p_yb.data() + ay, s->d_yb, (size_t)g.y_bytes, hipMemcpyDeviceToHost, st));
-        if (g.y_bytes) IP_HIP_OK(hipMemcpyAsync(s->p_yq.data() + ay, s->d_yq, (size_t)g.y_bytes, hipMemcpyDeviceToHost, st));
-        IP_HIP_OK(hipStreamSynchronize(st));
+        VLR_HIP_OK(hipMemcpyAsync(xo.data(), s->d_xoff, (np + 1) * 4, hipMemcpyDeviceToHost, st));
+        VLR_HIP_OK(hipMemcpyAsync(yo.data(), s->d_yoff, (np + 1) * 4, hipMemcpyDeviceToHost, st));
+        VLR_HIP_OK(hipMemcpyAsync(s->p_band.data() + at, s->d_band, np * 4, hipMemcpyDeviceToHost, st));
+        if (g.x_bytes) VLR_HIP_OK(hipMemcpyAsync(s->p_xb.data() + ax, s->d_xb, (size_t)g.x_bytes, hipMemcpyDeviceToHost, st));
+        if (g.y_bytes) VLR_HIP_OK(hipMemcpyAsync(s->p_yb.data() + ay, s->d_yb, (size_t)g.y_bytes, hipMemcpyDeviceToHost, st));
+        if (g.y_bytes) VLR_HIP_OK(hipMemcpyAsync(s->p_yq.data() + ay, s->d_yq, (size_t)g.y_bytes, hipMemcpyDeviceToHost, st));
+        VLR_HIP_OK(hipStreamSynchronize(st));
         for (size_t p = 0; p < np; ++p) { s->p_xlen[at + p] = xo[p + 1] - xo[p]; s->p_ylen[at + p] = yo[p + 1] - yo[p]; }
     }
     if ((rc = sync_stage(st, s->t[7], t0)) != VLR_OK) return rc;
@@ -397,26 +290,15 @@ int run_range(vlr_indelpileup* s, const uint8_t* d_base, const uint64_t* d_start
 int run_chunk(vlr_indelpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
     const uint8_t* d_base; const uint64_t* d_starts;
     int rc = vlr_dev_file_split_view(df, &d_base, &d_starts);
-    if (rc != VLR_OK) return rc;
-    if ((size_t)n > s->rec_cap) {
-        IP_HIP_OK(hipStreamSynchronize(st));
-        if (s->d_cnt) (void)hipFree(s->d_cnt);
-        if (s->d_off) (void)hipFree(s->d_off);
-        s->d_cnt = nullptr; s->d_off = nullptr; s->rec_cap = 0;
-        const size_t cap = (size_t)n + (size_t)n / 4 + 1024;
-        IP_HIP_OK(hipMalloc((void**)&s->d_cnt, K_N * cap * 8));
-        IP_HIP_OK(hipMalloc((void**)&s->d_off, K_N * cap * 8));
-        s->rec_cap = cap;
-    }
-    double t0 = now_s();
-    const int64_t stride = (int64_t)s->rec_cap;
+    if (rc != VLR_OK || (rc = vlr_bam::reserve_records<uint64_t>(*s, n, K_N, st)) != VLR_OK) return rc;
+    const double t0 = now_s();
     const unsigned blocks = (unsigned)((n + kThreads - 1) / kThreads);
     const uint64_t rec0 = s->n_records;
-    hipLaunchKernelGGL(indelpileup_count_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->loci, s->window, s->d_cnt, stride, s->d_counters);
-    hipLaunchKernelGGL(indelpileup_scan_kernel, dim3(K_N), dim3(kScanThreads), 0, st, s->d_cnt, n, stride, s->d_off, s->d_total);
+    hipLaunchKernelGGL(indelpileup_count_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->loci, s->window, (uint64_t*)s->d_cnt, (int64_t)s->rec_cap,
+                       s->d_counters);
     uint64_t total[K_N] = {0, 0, 0};
-    IP_HIP_OK(hipMemcpyAsync(total, s->d_total, sizeof total, hipMemcpyDeviceToHost, st));
-    if ((rc = sync_stage(st, s->t[3], t0)) != VLR_OK) return rc;
+    if ((rc = vlr_bam::scan_records<uint64_t>(*s, n, K_N, total, st)) != VLR_OK) return rc;
+    s->t[3] += now_s() - t0;
     s->n_records += (uint64_t)n;
     if (total[K_EV] == 0) return VLR_OK;
     if (s->overflow || s->n_total + total[K_EV] > s->capacity) {   // counted, not written: the caller opens again with needed_capacity
@@ -428,7 +310,7 @@ int run_chunk(vlr_indelpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
         return run_range(s, d_base, d_starts, rec0, Range{0, n, 0, 0, 0, total[K_EV], total[K_X], total[K_Y]}, st);
     // sub-ranges of records whose pair bytes fit the uint32 offsets, cut at the scanned offsets
     std::vector<uint64_t> off((size_t)K_N * (size_t)n);
-    for (int k = 0; k < K_N; ++k) IP_HIP_OK(hipMemcpy(off.data() + (size_t)k * (size_t)n, s->d_off + (size_t)k * s->rec_cap, (size_t)n * 8, hipMemcpyDeviceToHost));
+    for (int k = 0; k < K_N; ++k) VLR_HIP_OK(hipMemcpy(off.data() + (size_t)k * (size_t)n, s->d_off + (size_t)k * s->rec_cap, (size_t)n * 8, hipMemcpyDeviceToHost));
     auto at = [&](int k, int64_t i) { return i < n ? off[(size_t)k * (size_t)n + (size_t)i] : total[k]; };
     for (int64_t i0 = 0; i0 < n;) {
         int64_t i1 = i0 + 1;
@@ -476,9 +358,8 @@ int vlr_indelpileup_open(int device, const char* fasta_path, int64_t n_loci, con
             return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: loci are not sorted by (ref_id, start) at %lld", (long long)k);
         max_len = std::max(max_len, end[k] - start[k]);
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || ndev <= device) return bfail(VLR_ERR_NO_DEVICE, "no HIP device %d (the engine has no CPU path)", device);
-    IP_HIP_OK(hipSetDevice(device));
+    int rc = vlr_bam::use_device(device);
+    if (rc != VLR_OK) return rc;
     vlr_indelpileup* s = new vlr_indelpileup();
     s->device = device;
     s->window = window; s->mode = mode; s->keep_pairs = keep_pairs != 0;
@@ -486,7 +367,6 @@ int vlr_indelpileup_open(int device, const char* fasta_path, int64_t n_loci, con
     for (int k = 0; k < 16; ++k) s->hop[k] = hop && mode == VLR_INDELPILEUP_HOMOPOLYMER ? hop[k] : -HUGE_VAL;
     s->n_loci = n_loci;
     s->capacity = (uint64_t)hit_capacity;
-    if (window_bytes > 0) s->window_bytes = (size_t)window_bytes;
     // tuning / test knob: the pair bytes a record sub-range may hold (the uint32 offsets need at most 2^31)
     if (const char* v = getenv("VLR_INDELPILEUP_PAIR_BYTES")) {
         const unsigned long long x = strtoull(v, nullptr, 10);
@@ -495,19 +375,15 @@ int vlr_indelpileup_open(int device, const char* fasta_path, int64_t n_loci, con
     s->fasta = fasta_path;
     s->h_ref_id.assign(ref_id, ref_id + n_loci);
     const uint64_t zero = 0;
-    const size_t hit_bytes = ((size_t)s->capacity + kGuardHits) * sizeof(vlr_indelpileup_hit);
-    int rc = read_fai(s);
+    rc = vlr_bam::read_fai(s->fasta, s->fai);
     auto step = [&](int r) { if (rc == VLR_OK) rc = r; };
     step(upload(s->d_ref_id, ref_id, (size_t)n_loci));
     step(upload(s->d_start, start, (size_t)n_loci));
     step(upload(s->d_end, end, (size_t)n_loci));
     step(n_loci ? upload(s->d_alt_off, alt_offset, (size_t)n_loci + 1) : upload(s->d_alt_off, &zero, 1));
     step(upload(s->d_altb, alt_bases, n_loci ? (size_t)alt_offset[n_loci] : 0));
-    step(upload(s->d_counters, (const unsigned long long*)s->counters, (size_t)C_N));
-    auto hip = [&](hipError_t e, const char* what) { if (rc == VLR_OK && e != hipSuccess) rc = bfail(e == hipErrorOutOfMemory ? VLR_ERR_OUT_OF_MEMORY : VLR_ERR_HIP, "%s: %s", what, hipGetErrorString(e)); };
-    if (rc == VLR_OK) hip(hipMalloc((void**)&s->d_total, K_N * 8), "hipMalloc");
-    if (rc == VLR_OK) hip(hipMalloc((void**)&s->d_hits, hit_bytes), "hipMalloc of the hit buffer");
-    if (rc == VLR_OK) hip(hipMemset((void*)(s->d_hits + s->capacity), kGuardByte, kGuardHits * sizeof(vlr_indelpileup_hit)), "hipMemset");
+    step(vlr_bam::open_session(*s, device, window_bytes, K_N));
+    step(vlr_bam::guarded(s->d_hits, (size_t)s->capacity));
     if (rc != VLR_OK) { vlr_indelpileup_close(s); return rc; }
     s->loci = Loci{n_loci, s->d_ref_id, s->d_start, s->d_end, s->d_alt_off, max_len, 0, nullptr};
     *out = s;
@@ -515,50 +391,28 @@ int vlr_indelpileup_open(int device, const char* fasta_path, int64_t n_loci, con
 }
 
 int vlr_indelpileup_add_bam(vlr_indelpileup* s, const char* bam_path) {
-    using namespace vlr_ip;
-    if (!s || !bam_path) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_add_bam: null");
-    if (s->collected) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_add_bam: the result was already read");
-    if (s->trunc_record >= 0) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_add_bam: the file before ended inside a record");
-    if (hipSetDevice(s->device) != hipSuccess) return bfail(VLR_ERR_HIP, "hipSetDevice(%d) failed", s->device);
-    vlr_bam::BamStream b;
-    b.device = s->device;
-    b.window = &s->window_bytes;
-    b.t_read = &s->t[0]; b.t_feed = &s->t[1]; b.t_split = &s->t[2]; b.t_inflate = &s->t[10]; b.t_total = &s->t[9];
-    b.on_header = [s, bam_path](const std::vector<std::string>& names) { return on_header(s, names, bam_path); };
-    b.on_chunk = [s](vlr_dev_file* df, int64_t n, uint64_t, const std::vector<std::string>&, const char*, void* st) { return run_chunk(s, df, n, (hipStream_t)st); };
-    // a file that ends inside a record: malformed input, reported in the status word; the records in front of it are scored
-    b.on_truncated = [s](uint64_t) { s->trunc_record = (int64_t)s->n_records; return (int)VLR_OK; };
-    return vlr_bam::stream_bam(b, bam_path);
+    if (!s) return vlr_bam::bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_add_bam: null");
+    return vlr_bam::add_bam(*s, bam_path, "vlr_indelpileup_add_bam", {&s->t[0], &s->t[1], &s->t[2], &s->t[10], &s->t[9]},
+                            [s, bam_path](const std::vector<std::string>& names) { return vlr_ip::on_header(s, names, bam_path); },
+                            [s](vlr_dev_file* df, int64_t n, hipStream_t st) { return vlr_ip::run_chunk(s, df, n, st); });
 }
 
 int vlr_indelpileup_result(vlr_indelpileup* s, vlr_indelpileup_counts* r) {
     using namespace vlr_ip;
     if (!s || !r) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_result: null");
-    IP_HIP_OK(hipSetDevice(s->device));
+    VLR_HIP_OK(hipSetDevice(s->device));
     if (!s->collected) {
         const double t0 = now_s();
-        IP_HIP_OK(hipMemcpy(s->counters, s->d_counters, sizeof s->counters, hipMemcpyDeviceToHost));
-        uint8_t guard[kGuardHits * sizeof(vlr_indelpileup_hit)];
-        IP_HIP_OK(hipMemcpy(guard, (const void*)(s->d_hits + s->capacity), sizeof guard, hipMemcpyDeviceToHost));
-        for (uint8_t g : guard) if (g != (uint8_t)kGuardByte) s->status |= VLR_INDELPILEUP_GUARD_DAMAGED;
-        if (s->counters[C_BAD] || s->trunc_record >= 0) s->status |= VLR_INDELPILEUP_BAD_RECORD;
+        bool intact = true;
+        int rc = vlr_bam::read_counters(*s);
+        if (rc != VLR_OK || (rc = vlr_bam::guard_intact(s->d_hits, (size_t)s->capacity, &intact)) != VLR_OK) return rc;
+        if (!intact) s->status |= VLR_INDELPILEUP_GUARD_DAMAGED;
+        if (vlr_bam::bad_record_seen(*s)) s->status |= VLR_INDELPILEUP_BAD_RECORD;
         if (s->overflow) s->status |= VLR_INDELPILEUP_OVERFLOW;
         else if (s->n_total) {
-            // record-major on the device -> locus-major, record order kept within a locus: a stable counting sort
             std::vector<vlr_indelpileup_hit> raw((size_t)s->n_total);
-            IP_HIP_OK(hipMemcpy(raw.data(), s->d_hits, raw.size() * sizeof(vlr_indelpileup_hit), hipMemcpyDeviceToHost));
-            std::vector<uint64_t> first((size_t)s->n_loci + 1, 0);
-            for (const auto& h : raw) if ((int64_t)h.locus < s->n_loci) ++first[(size_t)h.locus + 1];
-            for (size_t k = 0; k < (size_t)s->n_loci; ++k) first[k + 1] += first[k];
-            s->hits.resize((size_t)first[(size_t)s->n_loci]);
-            s->perm.resize(s->hits.size());
-            for (size_t k = 0; k < raw.size(); ++k) {
-                const auto& h = raw[k];
-                if ((int64_t)h.locus >= s->n_loci) continue;
-                const size_t at = (size_t)first[h.locus]++;
-                s->hits[at] = h;
-                s->perm[at] = k;
-            }
+            VLR_HIP_OK(hipMemcpy(raw.data(), s->d_hits, raw.size() * sizeof(vlr_indelpileup_hit), hipMemcpyDeviceToHost));
+            vlr_bam::locus_major(raw, s->n_loci, s->hits, &s->perm);
         }
         s->t[8] += now_s() - t0;
         s->collected = true;
@@ -571,8 +425,7 @@ int vlr_indelpileup_result(vlr_indelpileup* s, vlr_indelpileup_counts* r) {
     r->y_bytes = s->overflow ? 0 : (int64_t)s->y_total;
     r->status = s->status;
     r->needed_capacity = (int64_t)s->n_total;
-    r->first_bad_record = s->counters[C_BAD] ? (int64_t)s->counters[C_FIRST_BAD] : -1;
-    if (s->trunc_record >= 0 && (r->first_bad_record < 0 || s->trunc_record < r->first_bad_record)) r->first_bad_record = s->trunc_record;
+    r->first_bad_record = vlr_bam::first_bad_record(*s);
     for (int k = 0; k < 12; ++k) r->seconds[k] = s->t[k];
     return VLR_OK;
 }
@@ -619,7 +472,8 @@ int vlr_indelpileup_read_pairs(vlr_indelpileup* s, uint32_t* x_offset, uint8_t* 
 void vlr_indelpileup_close(vlr_indelpileup* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    void* p[] = {s->d_ref_id, s->d_start, s->d_end, s->d_alt_off, s->d_altb, (void*)s->d_ctg, s->d_ctg_len, s->d_hits, s->d_cnt, s->d_off, s->d_counters, s->d_total,
+    vlr_bam::close_session(*s);
+    void* p[] = {s->d_ref_id, s->d_start, s->d_end, s->d_alt_off, s->d_altb, (void*)s->d_ctg, s->d_ctg_len, s->d_hits,
                  s->d_src, s->d_xoff, s->d_yoff, s->d_band, s->d_dist, s->d_lnp, s->d_xb, s->d_yb, s->d_yq};
     for (void* q : p) if (q) (void)hipFree(q);
     for (auto& c : s->contigs) if (c.second.first) (void)hipFree(c.second.first);

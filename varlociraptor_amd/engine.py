@@ -37,7 +37,7 @@ EXPORTS = [
 SOURCES = tuple("csrc/" + f for f in (
     "vlr_kernels.hip", "vlr_kernels_lean.hip", "vlr_kernels_deep.hip", "vlr_kernels_wide.hip", "vlr_kernels_widedeep.hip", "vlr_realign.hip",
     "vlr_fdr.hip", "vlr_contam.hip", "vlr_callstats.hip", "vlr_bamstats.hip", "vlr_basepileup.hip", "vlr_indelpileup.hip", "vlr_fragpileup.hip", "vlr_inflate.hip", "vlr_decode.hip", "vlr_host.cpp", "vlr_ingest.cpp",
-    "vlr_plan.h", "vlr_gpuio.h", "vlr_callstats.h", "vlr_bamstream.h", "vlr_basepileup.h", "vlr_indelpileup.h", "vlr_fragpileup.h")) + ("../include/vlr.h", "../include/vlr_detmath.h")
+    "vlr_plan.h", "vlr_gpuio.h", "vlr_callstats.h", "vlr_bamstream.h", "vlr_bamsession.h", "vlr_basepileup.h", "vlr_indelpileup.h", "vlr_fragpileup.h")) + ("../include/vlr.h", "../include/vlr_detmath.h")
 
 
 class EngineError(RuntimeError):
@@ -140,6 +140,23 @@ def lib():
             raise EngineError(abi.ERR_INVALID_ARGUMENT, "ABI version mismatch")
         _LIB = L
     return _LIB
+
+
+def bind_basepileup():
+    """the library with the argument types of vlr_basepileup_* set (varlociraptor_amd/basecalls.py: device_hits)"""
+    L = lib()
+    L.vlr_basepileup_open.restype = C.c_int
+    L.vlr_basepileup_open.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                      C.POINTER(C.c_void_p)]
+    L.vlr_basepileup_add_bam.restype = C.c_int
+    L.vlr_basepileup_add_bam.argtypes = [C.c_void_p, C.c_char_p]
+    L.vlr_basepileup_result.restype = C.c_int
+    L.vlr_basepileup_result.argtypes = [C.c_void_p, C.POINTER(abi.BasePileupCounts)]
+    L.vlr_basepileup_read.restype = C.c_int
+    L.vlr_basepileup_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.vlr_basepileup_close.restype = None
+    L.vlr_basepileup_close.argtypes = [C.c_void_p]
+    return L
 
 
 def bind_indelpileup():
