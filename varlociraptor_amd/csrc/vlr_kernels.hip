@@ -51,6 +51,11 @@ constexpr bool kHasLfc = !VLR_LEAN;          // l2fc operands on the path and th
 // tables of at most 64 entries — walk_root only ever meets the last kind, from its root node, outside the probe pass.
 constexpr bool kHasGeneralWalk = !VLR_LEAN;
 constexpr bool kHasManySamples = !VLR_LEAN;  // plans above kXcdMapMaxSamples samples                                 (lean: S <= 2)
+// The nested root of the lean unit (a proper Range over one leaf Range, the only root its walk ever meets) is driven by outer_root
+// instead of walk_root: the state of the outer chain lives in wave-uniform registers across the batches (OuterSt), the pending points
+// are recomputed from it, and one straight block per round delivers, advances and sets up the next tasks — no Frame, RangeSt or
+// WalkSave round trips through LDS.  Same arithmetic, same order: the other units keep walk_root and are the reference for it.
+constexpr bool kRegOuter = VLR_LEAN;
 // The fused coefficient pass (phase B): one pass over the rows builds the coefficients of the first kFusedSets surviving artifact
 // hypotheses next to those of h = none and parks them in DevResults::parked.  The only trait that compiles something IN: the lean
 // unit alone has it (the other units keep one row pass per hypothesis); the host enables it per launch by passing `parked`.
@@ -2874,6 +2879,8 @@ __device__ inline void afd_emit_row(Ctx& c, int i, int s_in, int nq) {
 // The work is split in three steps around run_chain_batch, which the kernel's event loop runs on behalf of the
 // walk (bo_begin -> [bo_setup -> run_chain_batch -> bo_deliver]*): inlining the batch runner inside the walk kept
 // ~100 more VGPRs alive across it and made the compiler spill in its rounds.
+// (The lean unit runs the same three steps from registers: outer_begin / outer_setup / outer_deliver below, under kRegOuter.)
+#if !VLR_LEAN
 __device__ __forceinline__ void bo_begin(Ctx& c, RangeSt& r, int chn, alive_t alive_in) {
     PROF_ADD(c, 3);
     const DevPlan& p = *c.plan;
@@ -3037,6 +3044,7 @@ __device__ __forceinline__ bool bo_deliver(Ctx& c, const Frame& f, RangeSt& r, d
     VLR_SYNC();
     return false;
 }
+#endif  // !VLR_LEAN
 
 // Event-level deferral: an event root whose path is a chain of single-valued Sample nodes ending in a leaf Range
 // (tumor-normal: somatic_tumor, germline_het, germline_hom) contributes exactly one innermost chain.  Such chains of
@@ -3154,6 +3162,333 @@ __device__ __forceinline__ int leaf_range_child(const DevPlan& p, int fnode) {
     return ok ? chn : -1;
 }
 
+#if VLR_LEAN
+// ------------------------------------------------------------------------------------------------
+// The nested root of the lean unit (kRegOuter): an outer Range node over one leaf Range node, from the root, outside the probe pass —
+// the one shape vlr_plan_create admits to this unit besides the roots that are never walked.  What walk_root keeps in Frame / RangeSt
+// / WalkSave records and re-reads lane by lane in every round lives here in wave-uniform registers that the event loop carries across
+// its run_chain_batch site.  The values, their expressions and the order of every table entry are walk_root's (PC_DESCEND ->
+// PC_RANGE_ISSUE -> [PC_BO_PRE -> batch -> PC_BO_POST]* -> range_advance / range_finish): tests/test_gpu_outer_rounds.py and
+// tests/test_gpu_lean_instance.py compare the two bit for bit.
+struct OuterSt {
+    double lo, hi, res, L, R, vL, vR, mid;   // the outer chain (RangeSt of walk_root)
+    int phase, tn, npend;                    // (npend: 2 / 3 / 6 by phase, or the Simpson grid's size)
+    int c0, nt;                              // pending points [c0, c0 + nt) are the chains of the batch in flight
+    int fr;                                  // constants of the frame (BatchOuter of walk_root), packed: see the accessors
+};
+// OuterSt::fr: bits 0-3 inner sample, 4-7 outer sample, 8 inner range dead, 9 prior class of the outer sample known (outer_begin),
+// 16-31 mask of the samples that vary with the outer point
+// (kLdsSamples <= 16: one nibble per sample index)
+__device__ __forceinline__ int fr_s_in(const OuterSt& o) { return o.fr & 15; }
+__device__ __forceinline__ int fr_s_out(const OuterSt& o) { return (o.fr >> 4) & 15; }
+__device__ __forceinline__ bool fr_dead(const OuterSt& o) { return (o.fr >> 8) & 1; }
+__device__ __forceinline__ bool fr_cls_fast(const OuterSt& o) { return (o.fr >> 9) & 1; }
+__device__ __forceinline__ int fr_vary(const OuterSt& o) { return (int)((unsigned)o.fr >> 16); }
+// the frame's constants that the lanes read when they write their tasks; the record sits where walk_root keeps the frame's RangeSt
+struct OuterConst {
+    double ostart, oend, iostart, ioend;     // spectrum of the outer node / of its leaf child
+    int olex, orex, iolex, iorex;
+    alive_t ialive;                          // NODE_ALIVE of the child
+};
+static_assert(sizeof(OuterConst) <= sizeof(RangeSt), "OuterConst lives in the first RangeSt slot");
+static_assert(kRegOuter, "outer_root is the lean unit's driver");
+
+// pending point i of the round in flight, i per lane: range_advance's r.pend[i] / the Simpson grid of the frame set-up, same expressions.
+// (Computing the points one by one as uniform values and handing them to their lanes measured 3 % slower than this.)
+__device__ __forceinline__ double outer_pend(const OuterSt& o, int i) {
+    if (o.phase == RP_INIT) return i ? o.hi : o.lo;
+    if (o.phase == RP_SIMPSON) {
+        const double step = (o.hi - o.lo) / (double)(o.npend - 1);
+        return (i == 0) ? o.lo : (i == o.npend - 1) ? o.hi : lin_pt(o.lo, step, (double)i);
+    }
+    if (o.phase == RP_ROUND) return (i == 0) ? o.mid : (i == 1) ? (o.mid + o.L) / 2.0 : (o.R + o.mid) / 2.0;
+    const double lo3 = fmax(o.mid - o.res * 3.0, o.lo);
+    const double hi3 = fmin(o.mid + o.res * 3.0, o.hi);
+    const double sa = div3(o.mid - lo3), sb = div3(hi3 - o.mid);  // itertools_num::linspace step, n = 4
+    return (i < 3) ? lin_pt(lo3, sa, (double)i) : lin_pt(o.mid, sb, (double)(i - 2));
+}
+
+// range_advance on the register state, once the round is delivered; true when the chain is finished
+__device__ __forceinline__ bool outer_advance(OuterSt& o, const double* tv) {
+    if (o.phase == RP_SIMPSON || o.phase == RP_TAIL) return true;
+    const bool init = o.phase == RP_INIT;
+    if (init) {  // (once per frame: the two end points from the table)
+        o.L = o.lo; o.R = o.hi; o.vL = uni_d(tv[0]); o.vR = uni_d(tv[1]);
+    } else {  // RP_ROUND: argmax over {left, middle1, middle2, right}; lowest index wins ties.  The values of middle1 / middle2 are the
+        // last two table entries: one LDS round trip (carrying them in registers from the delivery cost two spilled VGPRs)
+        const double x0 = o.L, x1 = uni_d((o.mid + o.L) / 2.0), x2 = uni_d((o.R + o.mid) / 2.0), x3 = o.R;
+        const double v0 = o.vL, v1 = uni_d(tv[o.tn - 2]), v2 = uni_d(tv[o.tn - 1]), v3 = o.vR;
+        int k = 0;
+        double vb = v0;
+        if (v1 > vb) { k = 1; vb = v1; }
+        if (v2 > vb) { k = 2; vb = v2; }
+        if (v3 > vb) { k = 3; }
+        const double nl = (k <= 1) ? x0 : (k == 2) ? x1 : x2, vl = (k <= 1) ? v0 : (k == 2) ? v1 : v2;
+        const double nr = (k == 0) ? x1 : (k == 1) ? x2 : x3, vr = (k == 0) ? v1 : (k == 1) ? v2 : v3;
+        o.L = uni_d(nl); o.vL = uni_d(vl);
+        o.R = uni_d(nr); o.vR = uni_d(vr);
+    }
+    if ((((o.R - o.L) >= o.res) && o.L < o.R) || init) {  // (range_advance's have_mid: the first round is always run)
+        o.mid = uni_d((o.R + o.L) / 2.0);
+        o.npend = 3;
+        o.phase = RP_ROUND;
+        return false;
+    }
+    // tail: small interval around the optimum (the abandoned-arm point is a first-round point again: see range_advance)
+    o.npend = 6;
+    o.phase = RP_TAIL;
+    return false;
+}
+
+// range_finish on the register state
+__device__ __forceinline__ double outer_finish(Ctx& c, const OuterSt& o, const double* tx, const double* tv) {
+    if (o.phase == RP_SIMPSON) {  // bio LogProb::ln_simpsons_integrate_exp (modes/generic.rs:367-385)
+        const int n = o.npend;
+        double M = VLR_NEG_INF, S = 0.0;
+        for (int i = 1; i < n - 1; ++i) lse_add(M, S, tv[i] + log((double)(2 + (i % 2) * 2)));
+        lse_add(M, S, tv[0]);
+        lse_add(M, S, tv[n - 1]);
+        return lse_value(M, S) + log(o.hi - o.lo) - log((double)(n - 1)) - log(3.0);
+    }
+    return integrate_table(tx, tv, o.tn, c.sx, c.sv, c.lane);
+}
+
+// first round of the frame: what bo_begin keeps per frame, plus the spectra that bo_setup reloads in every round
+__device__ __forceinline__ void outer_begin(Ctx& c, OuterSt& o, const DevNode& nd, int chn, alive_t alive_in) {
+    PROF_ADD(c, 3);
+    const DevPlan& p = *c.plan;
+    WaveSt* w = c.w;
+    const DevNode ch = ld_node(p.nodes + chn);
+    const int s_in = ch.sample, s_out = fr_s_out(o), S = c.S;
+    const int n_obs = UNI(w->nkeep[s_in]);
+    const bool clear_ref = n_obs > 10 && UNI((int)w->all_posref[s_in]);
+    const RangeV vr{ch.vafs.start, ch.vafs.end, ch.vafs.lex, ch.vafs.rex};
+    const bool dead = clear_ref && vr.start > 0.0;  // generic.rs:342-347
+    const double res = p.resolution[s_in];
+    const double lo = uni_d(observable_min(vr, n_obs)), hi = uni_d(observable_max(vr, n_obs));
+    const int simpson = ((hi - lo) < res) ? 3 : (n_obs < 5 ? 11 : 0);
+    // samples whose likelihood is fixed during an inner chain: constant over the outer points, or varying with them
+    double fixed_const = 0.0;
+    int vary = 0;
+    for (int s = 0; s < S; ++s) {
+        int by = p.by[s];
+        if (s == s_in || by == s_in) continue;
+        if (s == s_out || by == s_out) vary |= 1 << s;
+        else fixed_const += sample_lik(c, s, w->ops_vaf[s], by >= 0 ? w->ops_vaf[by] : 0.0);
+    }
+    fixed_const = uni_d(fixed_const);
+    // cross-event MAP candidates: groups whose spectra for the outer sample miss the whole outer range need no per-point test
+    const alive_t alive0 = alive_restrict(c, alive_in, s_out, o.lo, o.hi);
+    VLR_SYNC();
+    if (c.lane == 0) {
+        BatchOuter& B = w->bo;
+        B.alive0 = alive0;
+        B.lo = lo; B.hi = hi; B.res = res; B.fixed_const = fixed_const;
+        B.simpson = simpson;  // (dead, vary, the samples and the point counters of the round are in OuterSt)
+        OuterConst& K = *(OuterConst*)c.rs;
+        K.ostart = nd.vafs.start; K.oend = nd.vafs.end; K.olex = nd.vafs.lex; K.orex = nd.vafs.rex;
+        K.iostart = ch.vafs.start; K.ioend = ch.vafs.end; K.iolex = ch.vafs.lex; K.iorex = ch.vafs.rex;
+        K.ialive = NODE_ALIVE(ch);
+    }
+    VLR_SYNC();
+    // prior class of the outer sample, decided the way run_chain_batch's cls_fast decides it for the integrated one: if one Range
+    // spectrum of a uniform-prior universe covers [lo, hi] of the outer chain, every outer point is inside the universe
+    bool cls_fast = false;
+    if (p.prior_kind[s_out] == PK_UNIFORM)
+        for (int u = p.uni_off[s_out]; u < p.uni_off[s_out + 1]; ++u) {
+            const DevSpectrum sp = ld_spec(p.universe + u);
+            if (sp.kind == 1) {
+                RangeV ur{sp.start, sp.end, sp.lex, sp.rex};
+                cls_fast = cls_fast || (range_contains(ur, o.lo) && range_contains(ur, o.hi));
+            }
+        }
+    o.fr = UNI(s_in | (s_out << 4) | (dead ? 1 << 8 : 0) | (cls_fast ? 1 << 9 : 0) | (vary << 16));
+}
+
+// tasks of the pending outer points [c0, c0 + kRows) (bo_setup); returns false if the inner range is dead (no chains to run)
+__device__ __forceinline__ bool outer_setup(Ctx& c, OuterSt& o) {
+    const DevPlan& p = *c.plan;
+    WaveSt* w = c.w;
+    const BatchOuter& B = w->bo;
+    const OuterConst& K = *(const OuterConst*)c.rs;
+    const int lane = fresh_lane(c.lane), S = c.S;
+    const int s_in = fr_s_in(o), s_out = fr_s_out(o);
+    const bool dead = fr_dead(o), ocls = fr_cls_fast(o);
+    const int free_rows = kRows - c.nhold;  // held event-level chains keep the top rows (they ride along with this batch)
+    const int nt = UNI((o.npend - o.c0) < free_rows ? (o.npend - o.c0) : free_rows);
+    o.nt = nt;
+    PROF_ADD(c, 18);  // outer batch: entry (fixed samples) / delivery of the previous pass
+    VLR_SYNC();
+    const double xp = outer_pend(o, o.c0 + lane);  // (every lane: the phase branches stay uniform)
+    if (lane < nt) {
+        const RangeV oorig{K.ostart, K.oend, K.olex, K.orex};
+        const double x = xp;
+        ChainTask& T = w->task[lane];
+        T.lo = B.lo; T.hi = B.hi; T.res = B.res;
+        T.ostart = K.iostart; T.oend = K.ioend; T.olex = K.iolex; T.orex = K.iorex;
+        T.simpson_n = B.simpson;
+        T.contained = range_contains(oorig, x) ? 1 : 0;  // (the frame is the root's: nothing above it to be contained in)
+        T.alive = alive_update(c, UNI_A(B.alive0), s_out, x) & K.ialive;  // (& the groups that can contain a VAF of the inner node)
+        int pidx = 0;
+        for (int s = 0; s < S; ++s) {
+            double v = (s == s_out) ? x : w->ops_vaf[s];
+            c.tvaf[lane * S + s] = v;
+            // (a tail point may exceed [lo, hi] by an ulp: it takes the spectrum walk, so that the class is prior_class's in every case)
+            const bool in_univ = ocls && s == s_out && v >= o.lo && v <= o.hi;
+            if (s != s_in) pidx += (in_univ ? (v == 0.0 ? 0 : 1) : prior_class(p, s, v)) * p.class_stride[s];
+        }
+        T.pidx = pidx;
+        T.fixed = B.fixed_const;
+        T.group = c.group; T.disc = c.disc & ~(1 << s_in);
+        T.result = VLR_NEG_INF; T.haveBest = 0; T.n = 0; T.bestJ = VLR_NEG_INF; T.bestX = 0.0;
+    }
+    VLR_SYNC();
+    PROF_ADD(c, 16);  // outer batch: task setup
+    int vm = fr_vary(o);
+    while (vm && !dead) {
+        int s = __builtin_ctz(vm);
+        vm &= vm - 1;
+        int by = p.by[s];
+        if (lane < nt) {
+            double a = c.tvaf[lane * S + s];
+            double b = by >= 0 ? c.tvaf[lane * S + by] : 0.0;
+            double al, be;
+            alpha_beta(p, s, a, b, al, be);
+            w->bpend[1][lane] = al;  // scratch: the row buffers are rewritten by the chain batch that follows
+            w->bpend[2][lane] = be;
+        }
+        VLR_SYNC();
+        int off = UNI(w->soff[s]), D = UNI(w->nkeep[s]);
+        eval_pileup(c.coef + 2 * off, ecoef_of(c, s, off), D, (w->fastok >> s) & 1, nt, w->bpend[1], w->bpend[2], w->bpend[3], lane);
+        VLR_SYNC();
+        if (__builtin_expect(ones_any(c), 0) && ones_risk(c, s)) {
+            if (lane < nt && is_all_ones(p, s, c.tvaf[lane * S + s], by >= 0 ? c.tvaf[lane * S + by] : 0.0)) {
+                double Pm; int Em;
+                ones_load(c, s, Pm, Em);
+                w->bpend[3][lane] = ln_product_mantissa(Pm) + (double)Em * kLn2;
+            }
+            VLR_SYNC();
+        }
+        if (lane < nt) w->task[lane].fixed += w->bpend[3][lane] + (double)kshift(c)[s] * kLn2;
+        if (lane == 0) { w->work[0] += (unsigned long long)nt; w->work[1] += (unsigned long long)nt * (unsigned long long)D; }
+        VLR_SYNC();
+    }
+    PROF_ADD(c, 17);  // outer batch: likelihoods of the samples that vary with the outer point
+    c.bt_nt = nt;
+    c.bt_inner = s_in;
+    return !dead;
+}
+
+// hand the finished chains [c0, c0 + nt) to the outer table and to the MAP candidates (bo_deliver)
+__device__ __forceinline__ void outer_deliver(Ctx& c, OuterSt& o, double* txo, double* tvo) {
+    WaveSt* w = c.w;
+    const int lane = fresh_lane(c.lane);
+    const int c0 = o.c0, nt = o.nt, s_in = fr_s_in(o), s_out = fr_s_out(o);
+    const bool dead = fr_dead(o);
+    PROF_ADD(c, 24);  // resume up to the delivery
+    VLR_SYNC();
+    // lane i < nt fetches the results of chain i and its outer point (the task's operand of the outer sample, written by outer_setup)
+    // and records the point in one go; the row loop below then reads lanes instead of making an LDS round trip per field and row
+    const int li = lane < nt ? lane : 0;
+    const ChainTask& Tl = w->task[li];
+    const double xl = c.tvaf[li * c.S + s_out], resl = Tl.result, bJl = Tl.bestJ, bXl = Tl.bestX;
+    const int hbl = Tl.haveBest, contl = Tl.contained, nl = Tl.n;
+    const alive_t alivel = Tl.alive;
+    const int tn0 = o.tn;
+    const double vl = dead ? VLR_NEG_INF : resl;
+    if (lane < nt) { txo[tn0 + c0 + lane] = xl; tvo[tn0 + c0 + lane] = vl; }
+    PROF_ADD(c, 25);  // delivery: fetch + outer table
+    for (int i = 0; i < nt; ++i) {
+        const double x = lane_d(xl, i);
+        VLR_SYNC();
+        if (lane == 0) w->ops_vaf[s_out] = x;
+        VLR_SYNC();
+        if (__builtin_expect(dead, 0)) continue;
+        const int hb = VLR_RDLANE(hbl, i), n_i = VLR_RDLANE(nl, i);
+        if (hb & 1) map_consider(c, lane_d(bJl, i), s_in, lane_d(bXl, i));
+        // rare: candidates for other groups / containment via another path (also of a visited excluded range end)
+        const alive_t al_i = VLR_RDLANE(alivel, i);
+        const int co_i = VLR_RDLANE(contl, i);
+        if (__builtin_expect(al_i != 0 || !co_i || (hb & 2), 0)) {
+            const ChainTask& T = w->task[i];
+            const RangeV io{uni_d(T.ostart), uni_d(T.oend), UNI(T.olex), UNI(T.orex)};
+            scan_chain_candidates(c, c.rowX + i * c.cap, c.rowV + i * c.cap, n_i, io, co_i, al_i, s_in);
+        }
+    }
+    PROF_ADD(c, 26);  // delivery: MAP candidates per chain
+    VLR_SYNC();
+}
+
+// GenericPosterior::density (modes/generic.rs:190-423) for one (hypothesis, nested root).  resume == 0: enter the root; resume != 0:
+// the event loop ran the chain batch this driver asked for (c.need_batch).  Returns the density once the outer chain is finished.
+__device__ __forceinline__ double outer_root(Ctx& c, OuterSt& o, int root, int resume) {
+    const DevPlan& p = *c.plan;
+    WaveSt* w = c.w;
+    double* tx = c.tabX;
+    double* tv = c.tabV;
+    bool post = resume != 0;
+    if (!post) {
+        c.present = 0; c.disc = 0; c.contained = 1; c.afd_mute = 0;
+        c.alive = ALIVE_FULL(p.n_named + 1) & ~ALIVE_BIT(c.group);
+        const DevNode nd = ld_node(p.nodes + UNI(root));
+        const int s = nd.sample;
+        const int n_obs = UNI(w->nkeep[s]);
+        const bool clear_ref = n_obs > 10 && UNI((int)w->all_posref[s]);  // 270-291
+        const RangeV vr{nd.vafs.start, nd.vafs.end, nd.vafs.lex, nd.vafs.rex};
+        PROF_ADD(c, 32);  // Sample node, bounds
+        if (range_is_empty(vr) || (clear_ref && vr.start > 0.0)) return VLR_NEG_INF;  // 331-347
+        const int lchild = (nd.n_children != 0) ? leaf_range_child(p, UNI(root)) : -1;
+        // (a frame the host's proof excludes — no room for it, a leaf Range, no leaf Range child — ends the locus with a status bit)
+        if (c.nframes <= 0 || p.max_range_depth <= 0 || lchild < 0) { c.status |= VLR_LOCUS_TABLE_FULL; return __builtin_nan(""); }
+        const double min_vaf = uni_d(observable_min(vr, n_obs)), max_vaf = uni_d(observable_max(vr, n_obs));
+        o.lo = min_vaf; o.hi = max_vaf; o.res = uni_d(p.resolution[s]);
+        o.L = min_vaf; o.R = max_vaf; o.vL = VLR_NEG_INF; o.vR = VLR_NEG_INF; o.mid = min_vaf;
+        o.tn = 0; o.c0 = 0; o.nt = 0; o.fr = UNI(s) << 4;
+        const int simpson = ((max_vaf - min_vaf) < o.res) ? 3 : (n_obs < 5 ? 11 : 0);  // 367-394
+        if (simpson) { o.npend = simpson; o.phase = RP_SIMPSON; }
+        else { o.npend = 2; o.phase = RP_INIT; }
+        c.present = 1 << s;
+        PROF_ADD(c, 33);  // Range frame set-up (observable bounds)
+        if (o.npend > c.cap) { c.status |= VLR_LOCUS_TABLE_FULL; c.present = 0; return __builtin_nan(""); }
+        PROF_ADD(c, 29);  // outer: round issue
+        outer_begin(c, o, nd, lchild, c.alive & NODE_ALIVE(nd));
+        PROF_ADD(c, 30);
+    }
+    for (;;) {
+        if (post) {
+            outer_deliver(c, o, tx, tv);
+            const int c1 = o.c0 + o.nt;
+            if (c1 < o.npend) o.c0 = c1;
+            else {
+                // all points of the round are recorded: advance the outer chain right here
+                PROF_ADD(c, 18);
+                o.tn += o.npend;
+                VLR_SYNC();
+                const bool done = outer_advance(o, tv);
+                PROF_ADD(c, 27);  // outer: advance
+                if (done) {
+                    const double rv = uni_d(outer_finish(c, o, tx, tv));
+                    PROF_ADD(c, 28);  // outer: finish
+                    c.present = 0;
+                    return rv;
+                }
+                if (o.tn + o.npend > c.cap) {  // room for the points of the next round
+                    c.status |= VLR_LOCUS_TABLE_FULL;
+                    c.present = 0;
+                    return __builtin_nan("");
+                }
+                o.c0 = 0;
+                PROF_ADD(c, 29);  // outer: round issue
+            }
+        }
+        if (outer_setup(c, o)) {
+            c.need_batch = 1;
+            return 0.0;
+        }
+        post = true;
+    }
+}
+#else  // !VLR_LEAN
 // GenericPosterior::density (modes/generic.rs:190-423) for one (hypothesis, root): explicit-stack walk.
 __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
     const DevPlan& p = *c.plan;
@@ -3497,6 +3832,7 @@ __device__ __forceinline__ double walk_root(Ctx& c, int root, int resume) {
         }
     }
 }
+#endif  // VLR_LEAN
 
 // ------------------------------------------------------------------------------------------------
 // FORMAT/AFD from the log of the call pass (calling.rs:889-928): one wave per locus filters the logged operand sets with the
@@ -4547,6 +4883,9 @@ __global__ void __launch_bounds__(64, WPE) vlr_call_kernel(const DevPlan plan_ar
             int r1 = (e < 0) ? 1 : ldc(p.root_off + e + 1);
             int u = 0, root = 0, resume = 0;
             bool fresh = true;  // (e, ri) not yet considered
+#if VLR_LEAN
+            OuterSt os;         // the nested root's outer chain, alive across the batch site below (kRegOuter)
+#endif
             for (;;) {
                 // run_kind 1: batch of the walk (+ held chains riding along in its free rows), 2: a full set of deferred chains, then
                 // the same root again, 3: the held chains that found no batch to ride along with, at the end of pass 1
@@ -4639,7 +4978,11 @@ __global__ void __launch_bounds__(64, WPE) vlr_call_kernel(const DevPlan plan_ar
                     PROF_ADD(c, 20);  // root entry (slot state, discrete roots are counted apart)
                 }
                 if (st == IT_WALK) {
+#if VLR_LEAN
+                    const double dens = uni_d(outer_root(c, os, root, resume));
+#else
                     const double dens = uni_d(walk_root(c, root, resume));
+#endif
                     PROF_ADD(c, 21);  // walk (descent, frames; the outer-batch steps are counted apart)
                     if (c.need_batch) {
                         c.need_batch = 0; run_kind = 1; run_mask = (1 << c.bt_nt) - 1; run_inner = c.bt_inner;
