@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define VLR_ABI_VERSION 13  /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
+#define VLR_ABI_VERSION 14  /* 3: vlr_plan_reserve takes the AFD capacity, 30 named events, vlr_node_*, homopolymer realignment; 4: device front door;
                              * 5: sharded device reader, calls-file parts, vlr_ingest_device_trim, CRC32 of BGZF members checked by both readers;
                              * 6: calls emission on the device — vlr_results.afd_text (FORMAT/AFD text), OBS text in the observation summaries,
                              *    vlr_obs_table_summaries;
@@ -45,7 +45,9 @@ extern "C" {
                              * 10: vlr_basepileup_* (SNV / MNV allele supports from BAM records);
                              * 11: vlr_plan_fused_counters (the fused coefficient pass of the lean call kernel);
                              * 12: vlr_indelpileup_* (indel allele supports from BAM records);
-                             * 13: vlr_fragpileup_* (fragment observations of SNV / MNV candidates from BAM records) */
+                             * 13: vlr_fragpileup_* (fragment observations of SNV / MNV candidates from BAM records);
+                             * 14: vlr_fragpileup_open_realign / _realign_result / _read_realigned (indel-bearing reads over SNV / MNV
+                             *     candidates realigned inside the fragment session) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -648,6 +650,7 @@ enum { VLR_INDELPILEUP_EXACT = 0, VLR_INDELPILEUP_FAST = 1, VLR_INDELPILEUP_HOMO
 /* status byte of a hit */
 #define VLR_INDELPILEUP_HIT_NO_OVERLAP      (1u << 0)
 #define VLR_INDELPILEUP_HIT_LEADING_REFSKIP (1u << 1)
+#define VLR_INDELPILEUP_HIT_STRAND_INFO     (1u << 2)  /* vlr_fragpileup_open_realign only: the record carries an SI:Z tag (not scored) */
 typedef struct {
     double   ln_ref, ln_alt;       /* ln P(read window | ref allele), ln P(read window | alt allele): raw kernel outputs               */
     uint64_t record;               /* ordinal of the record                                                                            */
@@ -712,7 +715,33 @@ void vlr_indelpileup_close(vlr_indelpileup* s);
  * vlr_fragpileup_result: seconds [0] file read, [1] upload + inflate, [2] record split, [3] member pass kernels, [4] fragment pass
  *   kernels, [5] total of add_bam, [6] inflate kernels alone, [7] observations to the host.
  * vlr_fragpileup_read: n_obs observations locus-major (name order within a locus) and n_loci locus records.  Bit-identical from run to
- *   run, for every window_bytes and for every split of the input into files. */
+ *   run, for every window_bytes and for every split of the input into files.
+ *
+ * Realignment of indel-bearing reads (vlr_fragpileup_open_realign; snv.rs:72-86, mnv.rs:83, Realigner::allele_support, realignment/
+ *   mod.rs:161-424): a session opened through this entry does not hand a record that encloses a locus and carries an I or D operation
+ *   back flagged, it realigns it in the same pass over the file.  The arguments of vlr_fragpileup_open (realign_indel_reads = 0 scores every read from its alignment, as there)
+ *   and fasta_path / realign_window (--indel-window, 1 .. VLR_INDELPILEUP_MAX_WINDOW) / mode / gap / hop as for vlr_indelpileup_open,
+ *   evidence_capacity (realigned evidences the device buffers hold; the pair bytes are sized from it) and pair_byte_limit (pair bytes
+ *   scored in one launch, 0 = 2^31: the uint32 offsets of vlr_realign_batch_desc; a smaller value only cuts the evidences into more
+ *   ranges).  Per chunk the member pass counts the record's evidences and their pair bytes beside its members (a fourth prefix sum
+ *   over the record order decides an evidence's place: no atomic), writes each as a vlr_indelpileup_hit — the candidate region
+ *   (mod.rs:58-153) on [start, start + len), the ref allele window = the region's ref interval —, and one wave per evidence gathers
+ *   the read window, the ref allele window from the upper-cased contig and the alt allele window of Snv / MnvEmissionParams
+ *   ([max(0, start - rw), min(start + len + rw, contig length)), rw = realign_window * 3 / 2, the locus bytes replaced by the ALT
+ *   allele) into pair arrays that accumulate over the session.  vlr_fragpileup_result scores them once per range (edit distance,
+ *   band = distance + 4 except in fast mode, the pair HMM of `mode`: the kernels of vlr_realign_batch), brings the raw scores to the
+ *   host, normalises them (mod.rs:358-376; std::log1p / std::exp), and a small kernel writes them into the members: strand = the
+ *   record's when the supports differ, else none (mod.rs:409-413), no read position, no third-allele evidence.  The fragment pass
+ *   behind it is the one of every session.  An evidence without overlap or with an empty read window gets ln 0.5 / ln 0.5.
+ *   Refused, as a status of the observation: a CIGAR that begins with N (VLR_BASEPILEUP_HIT_LEADING_REFSKIP) and a record with an
+ *   SI:Z tag (VLR_FRAGPILEUP_OBS_REALIGN_STRAND_INFO).  NOT mirrored: the read-inferred third allele (mod.rs:317-348), alt_variants,
+ *   homopolymer_indel_len.  More evidences than evidence_capacity: VLR_FRAGPILEUP_EVIDENCE_OVERFLOW, nothing is written past a buffer,
+ *   vlr_fragpileup_realign_result gives the exact need.  The observations do not depend on window_bytes, the split into files or
+ *   pair_byte_limit, bit for bit.
+ * vlr_fragpileup_realign_result (after vlr_fragpileup_result): the evidence counts; seconds [0] window gather kernels, [1]
+ *   edit-distance + band kernels, [2] pair-HMM kernels, [3] collect, normalisation on the host and the kernel that writes the members.
+ * vlr_fragpileup_read_realigned: the n_evidences realigned evidences in record order (loci ascending within a record) as
+ *   vlr_indelpileup_hit: raw scores, distances, window coordinates, status. */
 #define VLR_FRAGPILEUP_MAX_MEMBERS 4096   /* LDS per workgroup: 4 B sort index + 2 B rank per member + scan cells = 26 KiB, six workgroups per CU */
 /* status word of a session */
 #define VLR_FRAGPILEUP_BAD_RECORD      (1u << 0)
@@ -720,11 +749,13 @@ void vlr_indelpileup_close(vlr_indelpileup* s);
 #define VLR_FRAGPILEUP_NAME_OVERFLOW   (1u << 2)
 #define VLR_FRAGPILEUP_GUARD_DAMAGED   (1u << 3)
 #define VLR_FRAGPILEUP_KEY_OVERFLOW    (1u << 4)
+#define VLR_FRAGPILEUP_EVIDENCE_OVERFLOW (1u << 5)
 /* status of a locus */
 #define VLR_FRAGPILEUP_LOCUS_TOO_MANY_MEMBERS  (1u << 0)
 #define VLR_FRAGPILEUP_LOCUS_TOO_MANY_ALT_LOCI (1u << 1)
 /* status byte of an observation: the VLR_BASEPILEUP_HIT_* bits of its records' hits, and */
 #define VLR_FRAGPILEUP_OBS_INVALID_RO  (1u << 4)   /* an RO:Z value that names no orientation (Error::InvalidReadOrientationInfo) */
+#define VLR_FRAGPILEUP_OBS_REALIGN_STRAND_INFO (1u << 5)   /* a record that needs realignment carries an SI:Z tag: not scored */
 /* bits of an observation */
 #define VLR_FRAGPILEUP_SOFTCLIPPED    (1u << 0)
 #define VLR_FRAGPILEUP_PAIRED         (1u << 1)
@@ -770,6 +801,20 @@ int  vlr_fragpileup_add_bam(vlr_fragpileup* s, const char* bam_path);
 int  vlr_fragpileup_result(vlr_fragpileup* s, vlr_fragpileup_counts* out);
 int  vlr_fragpileup_read(vlr_fragpileup* s, vlr_fragpileup_obs* obs, int64_t n_obs, vlr_fragpileup_locus* loci, int64_t n_loci);
 void vlr_fragpileup_close(vlr_fragpileup* s);
+typedef struct {
+    int64_t  n_evidences;          /* realigned evidences (0 on VLR_FRAGPILEUP_EVIDENCE_OVERFLOW)                                      */
+    int64_t  needed_evidences;     /* evidences the input produces                                                                     */
+    int64_t  x_bytes, y_bytes;     /* bytes of the pair arrays                                                                         */
+    int64_t  n_ranges;             /* ranges the evidences were scored in                                                              */
+    double   seconds[4];
+} vlr_fragpileup_realign_counts;
+int  vlr_fragpileup_open_realign(int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int32_t* len, const uint8_t* kind,
+                                 const uint8_t* ref_bases, const uint8_t* alt_bases, int realign_indel_reads, int64_t window, int max_mapq,
+                                 int max_read_len, int64_t member_capacity, int64_t name_capacity, int64_t key_capacity, int64_t window_bytes, const char* fasta_path,
+                                 int realign_window, int mode, const double gap[4], const double* hop, int64_t evidence_capacity,
+                                 int64_t pair_byte_limit, vlr_fragpileup** out);
+int  vlr_fragpileup_realign_result(vlr_fragpileup* s, vlr_fragpileup_realign_counts* out);
+int  vlr_fragpileup_read_realigned(vlr_fragpileup* s, vlr_indelpileup_hit* hits, int64_t n);
 
 /* The whole of `varlociraptor filter-calls control-fdr` (/root/reference/src/filtration/fdr.rs:36-158, record typing
  * src/utils/collect_variants.rs:44-304, probability sums and the filtering pass src/utils/mod.rs:169-374): read the calls BCF

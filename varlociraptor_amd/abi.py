@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 MAX_SAMPLES = 16
 N_BIAS = 6
 
@@ -181,6 +181,7 @@ INDELPILEUP_DELETION, INDELPILEUP_INSERTION, INDELPILEUP_REPLACEMENT = 0, 1, 2
 INDELPILEUP_EXACT, INDELPILEUP_FAST, INDELPILEUP_HOMOPOLYMER = 0, 1, 2
 INDELPILEUP_BAD_RECORD, INDELPILEUP_OVERFLOW, INDELPILEUP_GUARD_DAMAGED = 1, 2, 4
 INDELPILEUP_HIT_NO_OVERLAP, INDELPILEUP_HIT_LEADING_REFSKIP = 1, 2
+INDELPILEUP_HIT_STRAND_INFO = 4   # vlr_fragpileup_open_realign only (ABI 14)
 
 
 class IndelPileupHit(C.Structure):
@@ -208,6 +209,8 @@ FRAGPILEUP_BAD_RECORD, FRAGPILEUP_MEMBER_OVERFLOW, FRAGPILEUP_NAME_OVERFLOW, FRA
 FRAGPILEUP_ANY_OVERFLOW = FRAGPILEUP_MEMBER_OVERFLOW | FRAGPILEUP_NAME_OVERFLOW | FRAGPILEUP_KEY_OVERFLOW
 FRAGPILEUP_LOCUS_TOO_MANY_MEMBERS, FRAGPILEUP_LOCUS_TOO_MANY_ALT_LOCI = 1, 2
 FRAGPILEUP_OBS_INVALID_RO = 16
+FRAGPILEUP_EVIDENCE_OVERFLOW = 32          # status word of a realigning session (ABI 14)
+FRAGPILEUP_OBS_REALIGN_STRAND_INFO = 32    # status byte of an observation (ABI 14)
 FRAGPILEUP_SOFTCLIPPED, FRAGPILEUP_PAIRED, FRAGPILEUP_MAX_MAPQ, FRAGPILEUP_READPOS_MAJOR, FRAGPILEUP_HAS_XA = 1, 2, 4, 8, 16
 FRAG_F1R2, FRAG_F2R1, FRAG_R1F2, FRAG_R2F1, FRAG_F1F2, FRAG_R1R2, FRAG_F2F1, FRAG_R2R1, FRAG_ORIENT_NONE = range(9)
 FRAGPILEUP_NO_RECORD = 0xFFFFFFFFFFFFFFFF
@@ -224,3 +227,9 @@ class FragPileupCounts(C.Structure):
     _fields_ = [("n_obs", C.c_int64), ("n_members", C.c_int64), ("n_records", C.c_int64), ("n_rejected", C.c_int64), ("n_loci_too_deep", C.c_int64),
                 ("status", C.c_uint64), ("needed_members", C.c_int64), ("needed_name_bytes", C.c_int64), ("needed_keys", C.c_int64), ("first_bad_record", C.c_int64),
                 ("seconds", C.c_double * 8)]
+
+
+class FragPileupRealignCounts(C.Structure):
+    """vlr_fragpileup_realign_counts"""
+    _fields_ = [("n_evidences", C.c_int64), ("needed_evidences", C.c_int64), ("x_bytes", C.c_int64), ("y_bytes", C.c_int64), ("n_ranges", C.c_int64),
+                ("seconds", C.c_double * 4)]

@@ -175,18 +175,28 @@ def main(argv=None):
     pv.add_argument("--omit-mapq-adjustment", action="store_true")
     pv.add_argument("--max-depth", type=int, default=200, help="loci above it are counted in a warning and processed whole")
     pv.add_argument("--score-indel-reads-from-alignment", action="store_true",
-                    help="score a read with an insertion or deletion as it is aligned (the reference realigns it; without this flag such a read is an error)")
+                    help="score a read with an insertion or deletion as it is aligned (the reference realigns it; without this flag or "
+                    "--realign-indel-reads such a read is an error)")
+    pv.add_argument("--realign-indel-reads", action="store_true",
+                    help="realign a read with an insertion or deletion against the ref and the alt allele, as the reference does by default")
+    pv.add_argument("--indel-window", type=int, default=64, help="bases of a read realigned on either side of the candidate (at most 64, cli.rs:877)")
+    pv.add_argument("--pairhmm-mode", choices=["exact", "fast", "homopolymer"], default="exact")
     pv.add_argument("--device", default="0", help="HIP device index, or 'cpu' for the Python restatement")
     pv.add_argument("--output", required=True, help="observation BCF")
     a = ap.parse_args(argv)
     import os
     if a.cmd == "preprocess":
         from . import fragments
+        if a.realign_indel_reads and a.score_indel_reads_from_alignment:
+            ap.error("--realign-indel-reads and --score-indel-reads-from-alignment exclude each other")
+        if not 1 <= a.indel_window <= fragments.MAX_INDEL_WINDOW:
+            ap.error("--indel-window must be 1 .. %d" % fragments.MAX_INDEL_WINDOW)
         try:
             n = fragments.preprocess_variants(a.reference, a.candidates, a.bam, a.output, a.alignment_properties, "cpu" if a.device == "cpu" else int(a.device),
                                               a.atomic_candidate_variants, a.omit_mapq_adjustment, a.max_depth, a.score_indel_reads_from_alignment,
-                                              warn=lambda m: print(f"[WARN] {m}", file=sys.stderr))
-        except (fragments.PreprocessError, fragments.FragPileupError, fragments.InvalidReadOrientationInfo) as e:
+                                              warn=lambda m: print(f"[WARN] {m}", file=sys.stderr),
+                                              realign=fragments.RealignSpec(a.indel_window, a.pairhmm_mode) if a.realign_indel_reads else None)
+        except (fragments.PreprocessError, fragments.FragPileupError, fragments.InvalidReadOrientationInfo, fragments.EngineError) as e:
             print(f"error: {e}", file=sys.stderr)
             sys.exit(1)
         print(f"{n} records written", file=sys.stderr)

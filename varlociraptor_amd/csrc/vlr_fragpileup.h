@@ -15,6 +15,20 @@
 //   the observation fields   read_observation.rs:644-670, mod.rs:255-281
 //   calc_major_feature       read_observation.rs:498-527 over sorted values (read positions, alt-locus keys) and the alt-locus class of
 //                            ReadObservation::process (:338-350)
+//   the realignment          snv.rs:72-86, mnv.rs:83 with Realigner::allele_support (realignment/mod.rs:161-424): a record that encloses
+//                            the locus and carries an I or D operation is not scored from its alignment but realigned.  Here: its
+//                            candidate region (vlr_ip::candidate_region, mod.rs:58-153) on [start, start + len), the ref allele window
+//                            (the region's ref_interval) and the alt allele window of Snv / MnvEmissionParams (snv.rs:157-178,
+//                            mnv.rs:224-233: [max(0, start - rw), min(start + len + rw, contig length)) with the locus bytes replaced,
+//                            rw = window * 3 / 2, clamped on its own) as a vlr_indelpileup_hit (`realign_evidence`), and the
+//                            normalisation of mod.rs:358-376 (`normalize_support`).  The strand is the record's when the normalised
+//                            supports differ, else none (mod.rs:409-413); read position and third-allele evidence are none.
+//                            NOT mirrored: the read-inferred third allele (mod.rs:317-348 needs the Myers traceback of the bio crate,
+//                            which the reference does not vendor), alt_variants (candidates are atomic, so an MNV is realigned only
+//                            for an indel operation), homopolymer_indel_len.  Two inputs are refused, each with a status of its own: a
+//                            CIGAR that begins with N (read_pos fails) and a record with an SI:Z tag (strand information over an
+//                            interval, mod.rs:381-387).  A region without overlap or with an empty read window gives ln 0.5 / ln 0.5
+//                            (mod.rs:186-199).
 // varlociraptor_amd/fragments.py is the same in Python.
 //
 // Bounds: `features` runs only on a record vlr_bp::decode accepted, so the fixed head, the name (l_read_name bytes behind the head) and
@@ -24,6 +38,7 @@
 #define VLR_FRAGPILEUP_H
 
 #include "vlr_basepileup.h"
+#include "vlr_indelpileup.h"
 
 namespace vlr_fp {
 
@@ -194,18 +209,80 @@ VLR_BP_HD inline bool member_of(const vlr_bp::Loci& L, int64_t li, int64_t pos, 
     return L.start[li] - window <= pos && pos < L.start[li] + (int64_t)L.len[li];
 }
 
-struct RecMembers { uint32_t n_members, name_bytes, n_xa; vlr_bp::RecClass cls; };
+struct RecMembers {
+    uint32_t n_members, name_bytes, n_xa;
+    vlr_bp::RecClass cls;
+    uint32_t n_ev, x_bytes, y_bytes;   // a realigning pass: the record's evidences and the bytes of their pairs (allele windows; read windows, twice)
+    uint32_t seq_off, qual_off, l_seq; // of an accepted record: where its packed SEQ and its QUAL start
+};
+
+// what a realigning pass knows beyond the loci: --indel-window and the contigs of the BAM header (-1: not loaded, no locus lies on it)
+struct Realign {
+    int64_t window;
+    int64_t n_refs;
+    const int64_t* ctg_len;
+};
+
+// the alt allele window of locus li on its contig: [*begin, *end), clamped on its own; byte k of it is `alt_window_byte`
+VLR_BP_HD inline void alt_window(const vlr_bp::Loci& L, int64_t li, int64_t contig_len, int64_t window, int64_t* begin, int64_t* end) {
+    const int64_t rw = window * 3 / 2;
+    *end = vlr_ip::max64(0, vlr_ip::min64(L.start[li] + (int64_t)L.len[li] + rw, contig_len));
+    *begin = vlr_ip::min64(vlr_ip::max64(0, L.start[li] - rw), *end);
+}
+VLR_BP_HD inline uint8_t alt_window_byte(const vlr_bp::Loci& L, int64_t li, const uint8_t* contig, int64_t contig_len, int64_t begin, uint32_t k) {
+    const int64_t i = begin + (int64_t)k - L.start[li];
+    if (i >= 0 && i < (int64_t)L.len[li]) return L.alt_bases[L.base_off[li] + (uint64_t)i];
+    return vlr_ip::window_byte(vlr_ip::WB_REF_BASE, contig, contig_len, begin, k);
+}
+
+// The evidence of a record that needs realignment at locus li: the windows of its candidate region, or a status.  *x_bytes / *y_bytes:
+// the bytes of its two pairs.
+VLR_BP_HD inline vlr_indelpileup_hit realign_evidence(const Realign& ra, const vlr_bp::Loci& L, int64_t li, const Rec& r, uint64_t ordinal, uint32_t* x_bytes,
+                                                      uint32_t* y_bytes) {
+    vlr_indelpileup_hit h;
+    h.ln_ref = 0.0; h.ln_alt = 0.0;
+    h.record = ordinal;
+    h.ref_begin = 0;
+    h.locus = (uint32_t)li;
+    h.ref_len = 0; h.read_begin = 0; h.read_len = 0;
+    h.dist_ref = -1; h.dist_alt = -1;
+    h.flag = (uint16_t)(r.flag & (0x1u | 0x10u | 0x40u));
+    h.mapq = (uint8_t)r.mapq;
+    h.status = 0;
+    for (int k = 0; k < 4; ++k) h.pad[k] = 0;
+    *x_bytes = 0; *y_bytes = 0;
+    const int64_t contig_len = (int64_t)r.ref_id < ra.n_refs ? ra.ctg_len[r.ref_id] : -1;
+    if (contig_len < 0) { h.status = VLR_INDELPILEUP_HIT_NO_OVERLAP; return h; }   // (every contig with a locus is loaded: not reached)
+    const int64_t ls = L.start[li], le = ls + (int64_t)L.len[li];
+    const vlr_ip::Region g = vlr_ip::candidate_region(r, ls, le, contig_len, ra.window);
+    if (g.error) h.status = VLR_INDELPILEUP_HIT_LEADING_REFSKIP;
+    else if (r.has_si) h.status = VLR_INDELPILEUP_HIT_STRAND_INFO;
+    else if (!g.overlap || g.read_end - g.read_begin < 1) h.status = VLR_INDELPILEUP_HIT_NO_OVERLAP;
+    else {
+        int64_t ab, ae;
+        alt_window(L, li, contig_len, ra.window, &ab, &ae);
+        h.ref_begin = g.ref_begin;
+        h.ref_len = (uint32_t)(g.ref_end - g.ref_begin);
+        h.read_begin = (uint32_t)g.read_begin;
+        h.read_len = (uint32_t)(g.read_end - g.read_begin);
+        *x_bytes = h.ref_len + (uint32_t)(ae - ab);
+        *y_bytes = 2u * h.read_len;
+    }
+    return h;
+}
 
 // Everything one record gives: its members, loci ascending, written to out[0 .. room) when out != nullptr, its name to
 // name_dst[0 .. name_len) when name_dst != nullptr and its alt-locus keys to xa_dst[0 .. xa_room) when xa_dst != nullptr.  The count pass
 // (out == nullptr) and the fill pass run the same text.
 VLR_BP_HD inline RecMembers record_members(const vlr_bp::Tables& t, const vlr_bp::Loci& L, const uint8_t* p, uint64_t size, uint64_t ordinal,
                                            bool realign_indel_reads, int64_t window, uint64_t coeff, Member* out, uint64_t room, uint64_t name_off, uint8_t* name_dst,
-                                           uint64_t xa_off, AltKey* xa_dst, uint64_t xa_room) {
-    RecMembers res = {0u, 0u, 0u, vlr_bp::REC_OK};
+                                           uint64_t xa_off, AltKey* xa_dst, uint64_t xa_room, const Realign* ra = nullptr, vlr_indelpileup_hit* ev_out = nullptr,
+                                           uint64_t ev_room = 0) {
+    RecMembers res = {0u, 0u, 0u, vlr_bp::REC_OK, 0u, 0u, 0u, 0u, 0u, 0u};
     Rec r;
     res.cls = vlr_bp::decode(p, size, r);
     if (res.cls != vlr_bp::REC_OK || r.ref_id < 0 || r.pos < 0) return res;
+    res.seq_off = r.seq_off; res.qual_off = r.qual_off; res.l_seq = r.l_seq;
     Feat f;
     bool have_f = false;
     for (int64_t li = first_candidate(L, r.ref_id, r.pos); in_reach(L, li, r.ref_id, r.pos, window); ++li) {
@@ -214,6 +291,15 @@ VLR_BP_HD inline RecMembers record_members(const vlr_bp::Tables& t, const vlr_bp
             features(r, size, f);
             have_f = true;
             if (f.has_xa) res.n_xa = xa_keys(p + f.xa_off, f.xa_len, coeff, xa_dst, xa_room);
+        }
+        // SingleLocus::overlap(read, false, 0, 0) == Enclosing
+        const bool enclosing = r.pos <= L.start[li] && r.end_pos >= L.start[li] + (int64_t)L.len[li];
+        // a realigning pass: the evidence of a record vlr_bp::score flags (the count pass and the fill pass see the same ones)
+        if (ra != nullptr && enclosing && realign_indel_reads && r.has_indel) {
+            uint32_t xb, yb;
+            const vlr_indelpileup_hit h = realign_evidence(*ra, L, li, r, ordinal, &xb, &yb);
+            if (ev_out != nullptr && (uint64_t)res.n_ev < ev_room) ev_out[res.n_ev] = h;
+            ++res.n_ev; res.x_bytes += xb; res.y_bytes += yb;
         }
         if (out != nullptr && (uint64_t)res.n_members < room) {
             Member m;
@@ -233,8 +319,7 @@ VLR_BP_HD inline RecMembers record_members(const vlr_bp::Tables& t, const vlr_bp
             m.strand = vlr_bp::STRAND_NONE;
             m.bits = (uint8_t)((f.softclipped ? M_SOFTCLIPPED : 0) | (f.has_xa ? M_HAS_XA : 0));
             m.status = 0;
-            // SingleLocus::overlap(read, false, 0, 0) == Enclosing
-            if (r.pos <= L.start[li] && r.end_pos >= L.start[li] + (int64_t)L.len[li]) {
+            if (enclosing) {
                 m.bits |= M_ENCLOSING;
                 vlr_basepileup_hit h;
                 if (vlr_bp::score(t, L, li, r, ordinal, realign_indel_reads, h)) {
@@ -255,6 +340,31 @@ VLR_BP_HD inline RecMembers record_members(const vlr_bp::Tables& t, const vlr_bp
         if (name_dst != nullptr) for (uint32_t k = 0; k < f.name_len; ++k) name_dst[k] = p[36 + k];
     }
     return res;
+}
+
+// mod.rs:358-376: both supports normalised by their sum when neither is ln 0; ln 0.5 each when both are.  Host only: std::log1p and
+// std::exp are the calls math.log1p / math.exp of realign.normalize_support make.
+inline void normalize_support(double* prob_ref, double* prob_alt) {
+    const double ninf = -HUGE_VAL;
+    if (*prob_ref != ninf && *prob_alt != ninf) {
+        const double hi = *prob_ref > *prob_alt ? *prob_ref : *prob_alt, lo = *prob_ref > *prob_alt ? *prob_alt : *prob_ref;
+        const double t = hi + std::log1p(std::exp(lo - hi));
+        *prob_ref -= t; *prob_alt -= t;
+    }
+    if (*prob_ref == ninf && *prob_alt == ninf) { *prob_ref = std::log(0.5); *prob_alt = *prob_ref; }
+}
+
+// A realigned evidence into its member: the normalised supports (pr, pa) of a scored evidence, or the status of one that cannot be scored
+VLR_BP_HD inline void apply_realigned(Member& m, const vlr_indelpileup_hit& h, double pr, double pa) {
+    m.read_position = VLR_BASEPILEUP_NO_READ_POSITION;
+    m.third_allele = 0;
+    m.strand = vlr_bp::STRAND_NONE;
+    m.prob_ref = 0.0; m.prob_alt = 0.0;
+    if (h.status & VLR_INDELPILEUP_HIT_LEADING_REFSKIP) { m.status = VLR_BASEPILEUP_HIT_LEADING_REFSKIP; return; }
+    if (h.status & VLR_INDELPILEUP_HIT_STRAND_INFO) { m.status = VLR_FRAGPILEUP_OBS_REALIGN_STRAND_INFO; return; }
+    m.status = 0;
+    m.prob_ref = pr; m.prob_alt = pa;
+    if (pr != pa) m.strand = (m.flag & 0x10u) ? vlr_bp::STRAND_REVERSE : vlr_bp::STRAND_FORWARD;
 }
 
 // QNAME order: bytes, a shorter name before any name it prefixes (BTreeMap<Vec<u8>>)

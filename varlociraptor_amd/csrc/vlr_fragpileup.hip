@@ -26,6 +26,16 @@
 //   frag_gather_kernel   one workgroup per locus writes its observations at the offset, in rank order, with VLR_FRAGPILEUP_READPOS_MAJOR
 //                        and the alt_locus class (vlr_fp::alt_locus_class)
 // No atomic decides a place or an order that reaches the output: the cursors only fill the sort's input.
+// A realigning session (vlr_fragpileup_open_realign) adds, per chunk, three more count arrays (evidences, x bytes, y bytes of a record)
+// to the same count, scan and fill launches: the fill kernel writes the evidence of every member it flags NEEDS_REALIGN (vlr_fp::
+// realign_evidence) at ev[ev_base + eoff[i] ...), the member's index beside it and the session-wide u64 offsets of its two pairs; then
+//   indelpileup_gather_kernel  (vlr_pairscore.h, the kernel of the indel session) copies the windows of the chunk's evidences into pair
+//                              arrays that accumulate over the session: the records are resident only during their chunk
+// and at vlr_fragpileup_result, in front of the fragment pass, once per range of evidences whose pair bytes fit the limit:
+//   vlr_ip::score_pairs        edit distance, band, pair HMM (vlr_pairscore.h), indelpileup_collect_kernel the raw scores into the evidences
+//   (host)                     vlr_fp::normalize_support over the raw scores
+//   frag_apply_kernel          one evidence per thread: vlr_fp::apply_realigned writes the supports into the member and clears the flag
+// An evidence's place is a prefix sum over the record order; the ranges only decide which launch scores a pair, not its bytes.
 //
 // LDS of frag_locus_kernel: 4 B index + 2 B rank per member + 2 KiB of scan cells = 26 KiB at VLR_FRAGPILEUP_MAX_MEMBERS = 4096, six
 // workgroups per CU by LDS.
@@ -38,7 +48,9 @@
 
 #include "vlr_bamsession.h"
 #include "vlr_fragpileup.h"
+#include "vlr_pairscore.h"
 
+static_assert(sizeof(vlr_indelpileup_hit) == 64, "hit layout");
 static_assert(sizeof(vlr_fragpileup_obs) == 56, "observation layout");
 static_assert(sizeof(vlr_fragpileup_locus) == 24, "locus record layout");
 static_assert(sizeof(vlr_fp::Member) == 72, "member layout");
@@ -50,35 +62,83 @@ using vlr_bam::C_BAD;
 using vlr_bam::C_FIRST_BAD;
 using vlr_bam::C_REJECTED;
 using vlr_bam::kScanThreads;
-enum { K_MEMBERS = 0, K_NAME = 1, K_XA = 2, K_N = 3 };   // the three counts of a record
+enum { K_MEMBERS = 0, K_NAME = 1, K_XA = 2, K_N = 3, K_EV = 3, K_X = 4, K_Y = 5, K_N_REALIGN = 6 };   // the counts of a record; the last three of a realigning session
 constexpr int kThreads = 256;
 constexpr int kLocusThreads = 256;
 constexpr uint32_t kMax = VLR_FRAGPILEUP_MAX_MEMBERS;
 constexpr uint32_t kSentinel = 0xffffffffu;
 constexpr uint16_t kNoRank = 0xffffu;
 
+// what the fill kernel of a realigning session needs beyond the members' arguments (on = false: every other session)
+struct EvFill {
+    bool on;
+    Realign ra;
+    const uint64_t *eoff, *xoff, *yoff;     // the chunk's scanned evidence / x byte / y byte offsets per record
+    uint64_t ev0, cap, n_ev;                // evidences in front of the chunk, the capacity, the chunk's evidences
+    uint64_t x0, y0, x_bytes, y_bytes;      // pair bytes in front of the chunk, the chunk's
+    vlr_indelpileup_hit* hits;              // [cap]
+    uint32_t* member;                       // [cap] the member of an evidence
+    uint64_t *gx, *gy;                      // [2 * cap + 1] session-wide offsets of the pairs
+    vlr_ip::Src* src;                       // [n_ev] chunk-local
+};
+
+// the windows of a realigned SNV / MNV evidence: the alt allele window is the contig with the locus bytes replaced (vlr_fp::alt_window)
+struct SnvWindows {
+    vlr_bp::Loci L;
+    const uint8_t* const* ctg;
+    Realign ra;
+    __device__ int64_t n_loci() const { return L.n; }
+    __device__ int32_t ref_id(uint32_t locus) const { return L.ref_id[locus]; }
+    __device__ const uint8_t* contig(int32_t ref_id) const { return ctg[ref_id]; }
+    __device__ int64_t contig_len(int32_t ref_id) const { return ra.ctg_len[ref_id]; }
+    __device__ uint32_t alt_len(uint32_t locus, int64_t contig_len) const { int64_t b, e; alt_window(L, (int64_t)locus, contig_len, ra.window, &b, &e); return (uint32_t)(e - b); }
+    __device__ uint8_t alt_byte(uint32_t locus, const uint8_t* contig, int64_t contig_len, uint32_t k) const {
+        int64_t b, e;
+        alt_window(L, (int64_t)locus, contig_len, ra.window, &b, &e);
+        return alt_window_byte(L, (int64_t)locus, contig, contig_len, b, k);
+    }
+};
+
+// one evidence per thread: the normalised supports (or the evidence's status) into its member
+__global__ __launch_bounds__(kThreads) void frag_apply_kernel(const vlr_indelpileup_hit* __restrict__ hits, const uint32_t* __restrict__ member, const double* __restrict__ norm,
+                                                              uint64_t n_ev, uint64_t member_cap, Member* __restrict__ members) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_ev) return;
+    const uint32_t m = member[e];
+    if ((uint64_t)m >= member_cap) return;
+    apply_realigned(members[m], hits[e], norm[2 * e], norm[2 * e + 1]);
+}
+
+// kRealign: the instance of a realigning session; the other instance is the kernel every session had before
+template <bool kRealign>
 __global__ __launch_bounds__(kThreads) void frag_count_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
                                                               vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
                                                               uint32_t* __restrict__ cnt, uint32_t* __restrict__ nbytes, uint32_t* __restrict__ nxa,
-                                                              unsigned long long* __restrict__ counters) {
+                                                              unsigned long long* __restrict__ counters, Realign ra, uint32_t* __restrict__ nev,
+                                                              uint32_t* __restrict__ nxb, uint32_t* __restrict__ nyb) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t o = starts[i], end = starts[i + 1];
-    const RecMembers r = record_members(t, L, base + o, end - o, rec0 + (uint64_t)i, realign != 0, window, coeff, nullptr, 0, 0, nullptr, 0, nullptr, 0);
+    const RecMembers r = record_members(t, L, base + o, end - o, rec0 + (uint64_t)i, realign != 0, window, coeff, nullptr, 0, 0, nullptr, 0, nullptr, 0,
+                                        kRealign ? &ra : nullptr);
     cnt[i] = r.n_members;
     nbytes[i] = r.name_bytes;
     nxa[i] = r.n_xa;
+    if constexpr (kRealign) { nev[i] = r.n_ev; nxb[i] = r.x_bytes; nyb[i] = r.y_bytes; }
     if (r.cls == vlr_bp::REC_REJECTED) atomicAdd(&counters[C_REJECTED], 1ull);
     if (r.cls == vlr_bp::REC_BAD) { atomicAdd(&counters[C_BAD], 1ull); atomicMin(&counters[C_FIRST_BAD], (unsigned long long)(rec0 + (uint64_t)i)); }
 }
 
+template <bool kRealign>
 __global__ __launch_bounds__(kThreads) void frag_fill_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
                                                              vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
                                                              const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ nbytes, const uint64_t* __restrict__ off,
                                                              const uint64_t* __restrict__ noff, const uint64_t* __restrict__ xoff, uint64_t member0, uint64_t member_cap,
                                                              uint64_t name0, uint64_t name_cap, uint64_t key0, uint64_t key_cap, Member* __restrict__ members,
-                                                             uint8_t* __restrict__ names, AltKey* __restrict__ keys, uint32_t* __restrict__ locus_cnt) {
+                                                             uint8_t* __restrict__ names, AltKey* __restrict__ keys, uint32_t* __restrict__ locus_cnt, EvFill ev) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // the end of the chunk's pairs, for the last evidence's windows (index 2 * (ev0 + n_ev) <= 2 * capacity: the arrays hold one more)
+    if (kRealign && i == 0 && ev.on) { ev.gx[2 * (ev.ev0 + ev.n_ev)] = ev.x0 + ev.x_bytes; ev.gy[2 * (ev.ev0 + ev.n_ev)] = ev.y0 + ev.y_bytes; }
     if (i >= n || cnt[i] == 0) return;
     const uint64_t first = member0 + off[i];
     if (first >= member_cap) return;
@@ -88,9 +148,30 @@ __global__ __launch_bounds__(kThreads) void frag_fill_kernel(const uint8_t* __re
     const uint64_t key_at = key0 + xoff[i];
     const uint64_t key_room = key_at < key_cap ? key_cap - key_at : 0;
     const uint64_t o = starts[i], end = starts[i + 1];
+    // (a realigning fill runs only when every member and every evidence of the chunk fits its buffer)
+    const uint64_t e_first = kRealign && ev.on ? ev.ev0 + ev.eoff[i] : 0;
+    const uint64_t e_room = kRealign && ev.on && e_first < ev.cap ? ev.cap - e_first : 0;
     const RecMembers r = record_members(t, L, base + o, end - o, rec0 + (uint64_t)i, realign != 0, window, coeff, members + first, room, name_at, name_dst, key_at,
-                                        key_room ? keys + key_at : nullptr, key_room);
+                                        key_room ? keys + key_at : nullptr, key_room, kRealign && ev.on ? &ev.ra : nullptr, e_room ? ev.hits + e_first : nullptr, e_room);
     const uint64_t written = std::min<uint64_t>(r.n_members, room);
+    if (kRealign && e_room) {   // the evidences of the record: their members, the offsets of their pairs, where their read windows come from
+        uint64_t x = ev.x0 + ev.xoff[i], y = ev.y0 + ev.yoff[i], e = 0;
+        for (uint64_t k = 0; k < written && e < r.n_ev && e < e_room && ev.eoff[i] + e < ev.n_ev; ++k) {
+            const Member& m = members[first + k];
+            if (!(m.bits & M_ENCLOSING) || !(m.status & VLR_BASEPILEUP_HIT_NEEDS_REALIGN)) continue;
+            const vlr_indelpileup_hit h = ev.hits[e_first + e];
+            uint64_t alt = 0;
+            if (!h.status) { int64_t ab, ae; alt_window(L, (int64_t)h.locus, ev.ra.ctg_len[L.ref_id[h.locus]], ev.ra.window, &ab, &ae); alt = (uint64_t)(ae - ab); }
+            const uint64_t pr = 2 * (e_first + e);
+            ev.member[e_first + e] = (uint32_t)(first + k);
+            ev.gx[pr] = x; x += h.ref_len;
+            ev.gx[pr + 1] = x; x += alt;
+            ev.gy[pr] = y; y += h.read_len;
+            ev.gy[pr + 1] = y; y += h.read_len;
+            ev.src[ev.eoff[i] + e] = vlr_ip::Src{o + r.seq_off, o + r.qual_off, r.l_seq, 0u};
+            ++e;
+        }
+    }
     for (uint64_t k = 0; k < written; ++k) {
         const uint32_t li = members[first + k].locus;
         if ((int64_t)li < L.n) atomicAdd(&locus_cnt[li], 1u);
@@ -301,6 +382,24 @@ struct vlr_fragpileup : vlr_bam::Session {
     std::vector<vlr_fragpileup_locus> locus_rec;
     int64_t n_too_deep = 0;
     double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // a realigning session (vlr_fragpileup_open_realign)
+    bool realigning = false;
+    int k_n = vlr_fp::K_N;               // count arrays per record
+    int rl_window = 64;
+    vlr_ip::ScoreParams score;
+    std::vector<int32_t> h_ref_id;       // of the loci
+    std::vector<int64_t> h_end;          // start + len of the loci
+    vlr_ip::ContigTable ctg;
+    uint64_t ev_cap = 0, x_cap = 0, y_cap = 0, pair_byte_limit = vlr_ip::kPairByteLimit;
+    vlr_indelpileup_hit* d_ev = nullptr; uint32_t* d_evm = nullptr; uint64_t *d_gx = nullptr, *d_gy = nullptr;
+    uint8_t *d_xb = nullptr, *d_yb = nullptr, *d_yq = nullptr;
+    vlr_ip::Src* d_src = nullptr; size_t src_cap = 0;
+    uint64_t n_ev = 0, x_total = 0, y_total = 0;   // evidences and pair bytes the input produced so far
+    bool ev_overflow = false;
+    int64_t n_ranges = 0;
+    std::vector<vlr_indelpileup_hit> ev;           // the scored evidences, record-major
+    double rt[4] = {0, 0, 0, 0};
+    vlr_fp::Realign ra() const { return vlr_fp::Realign{rl_window, (int64_t)ctg.h_len.size() - 1, ctg.d_len}; }
 };
 
 namespace vlr_fp {
@@ -310,28 +409,71 @@ using vlr_bam::guarded;
 using vlr_bam::now_s;
 using vlr_bam::zeros;
 
+// a realigning session: the contig table of a file; every locus must lie inside its contig
+int on_header(vlr_fragpileup* s, const std::vector<std::string>& names, const char* path) {
+    const int rc = s->ctg.on_header(s->h_ref_id, names, path);
+    if (rc != VLR_OK) return rc;
+    for (size_t k = 0; k < s->h_ref_id.size(); ++k) {
+        const int64_t end = s->h_end[k];
+        if (end > s->ctg.h_len[(size_t)s->h_ref_id[k]])
+            return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: locus %zu ends at %lld, behind the %lld bases of its contig in the reference", path, k, (long long)end,
+                         (long long)s->ctg.h_len[(size_t)s->h_ref_id[k]]);
+    }
+    return VLR_OK;
+}
+
 int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
     const uint8_t* d_base; const uint64_t* d_starts;
     int rc = vlr_dev_file_split_view(df, &d_base, &d_starts);
-    if (rc != VLR_OK || (rc = vlr_bam::reserve_records<uint32_t>(*s, n, K_N, st)) != VLR_OK) return rc;
+    if (rc != VLR_OK || (rc = vlr_bam::reserve_records<uint32_t>(*s, n, s->k_n, st)) != VLR_OK) return rc;
     const double t0 = now_s();
     const unsigned blocks = (unsigned)((n + kThreads - 1) / kThreads);
     const uint64_t rec0 = s->n_records;
     const size_t stride = s->rec_cap;
     uint32_t *d_cnt = (uint32_t*)s->d_cnt, *d_nbytes = d_cnt + K_NAME * stride, *d_nxa = d_cnt + K_XA * stride;
-    hipLaunchKernelGGL(frag_count_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt, d_nbytes,
-                       d_nxa, s->d_counters);
-    uint64_t total[K_N] = {0, 0, 0};
-    if ((rc = vlr_bam::scan_records<uint32_t>(*s, n, K_N, total, st)) != VLR_OK) return rc;
+    if (s->realigning)
+        hipLaunchKernelGGL(frag_count_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt,
+                           d_nbytes, d_nxa, s->d_counters, s->ra(), d_cnt + K_EV * stride, d_cnt + K_X * stride, d_cnt + K_Y * stride);
+    else
+        hipLaunchKernelGGL(frag_count_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt,
+                           d_nbytes, d_nxa, s->d_counters, Realign{0, 0, nullptr}, nullptr, nullptr, nullptr);
+    uint64_t total[K_N_REALIGN] = {0, 0, 0, 0, 0, 0};
+    if ((rc = vlr_bam::scan_records<uint32_t>(*s, n, s->k_n, total, st)) != VLR_OK) return rc;
     // once a buffer has overflowed nothing more is written: the session only counts on
     const bool fits = s->n_members <= s->member_cap && s->n_name_bytes <= s->name_cap && s->n_keys <= s->key_cap;
+    // the evidences of the chunk are written when all of them, and all its members, fit (counted, not written, otherwise)
+    if (s->realigning && (s->n_ev + total[K_EV] > s->ev_cap || s->x_total + total[K_X] > s->x_cap || s->y_total + total[K_Y] > s->y_cap)) s->ev_overflow = true;
+    EvFill ev{};
+    ev.on = s->realigning && total[K_EV] > 0 && !s->ev_overflow && fits && s->n_members + total[K_MEMBERS] <= s->member_cap;
+    if (ev.on) {
+        if ((rc = vlr_bam::grow(s->d_src, s->src_cap, (size_t)total[K_EV])) != VLR_OK) return rc;
+        ev.ra = s->ra();
+        ev.eoff = s->d_off + K_EV * stride; ev.xoff = s->d_off + K_X * stride; ev.yoff = s->d_off + K_Y * stride;
+        ev.ev0 = s->n_ev; ev.cap = s->ev_cap; ev.n_ev = total[K_EV];
+        ev.x0 = s->x_total; ev.y0 = s->y_total; ev.x_bytes = total[K_X]; ev.y_bytes = total[K_Y];
+        ev.hits = s->d_ev; ev.member = s->d_evm; ev.gx = s->d_gx; ev.gy = s->d_gy; ev.src = s->d_src;
+    }
     if (total[K_MEMBERS] && fits && s->n_members < s->member_cap) {
-        hipLaunchKernelGGL(frag_fill_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt, d_nbytes,
-                           s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys, s->key_cap,
-                           s->d_members, s->d_names, s->d_keys, s->d_lcnt);
+        if (s->realigning)
+            hipLaunchKernelGGL(frag_fill_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt, d_nbytes,
+                               s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys, s->key_cap,
+                               s->d_members, s->d_names, s->d_keys, s->d_lcnt, ev);
+        else
+            hipLaunchKernelGGL(frag_fill_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt, d_nbytes,
+                               s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys, s->key_cap,
+                               s->d_members, s->d_names, s->d_keys, s->d_lcnt, ev);
         VLR_HIP_OK(hipStreamSynchronize(st));
         VLR_HIP_OK(hipGetLastError());
+        if (ev.on) {   // the windows of the chunk's evidences, while its records are resident
+            double tg = now_s();
+            const unsigned waves_per_block = vlr_ip::kThreads / 64;
+            hipLaunchKernelGGL((vlr_ip::indelpileup_gather_kernel<SnvWindows, uint64_t>), dim3((unsigned)((ev.n_ev + waves_per_block - 1) / waves_per_block)), dim3(vlr_ip::kThreads),
+                               0, st, d_base, ev.n_ev, s->d_ev + ev.ev0, SnvWindows{s->dl.loci, s->ctg.d_ctg, ev.ra}, s->d_src, s->d_gx + 2 * ev.ev0, s->d_gy + 2 * ev.ev0, s->d_xb,
+                               s->d_yb, s->d_yq);
+            if ((rc = vlr_ip::sync_stage(st, s->rt[0], tg)) != VLR_OK) return rc;
+        }
     }
+    if (s->realigning) { s->n_ev += total[K_EV]; s->x_total += total[K_X]; s->y_total += total[K_Y]; }
     s->n_members += total[K_MEMBERS];
     s->n_name_bytes += total[K_NAME];
     s->n_keys += total[K_XA];
@@ -340,6 +482,76 @@ int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
     return VLR_OK;
 }
 
+
+// The realignment of the session's evidences: scored in ranges of evidences whose pair bytes fit pair_byte_limit, normalised on the
+// host, written into their members.
+int realign_pass(vlr_fragpileup* s) {
+    const size_t ne = (size_t)s->n_ev;
+    std::vector<uint64_t> gx(2 * ne + 1), gy(2 * ne + 1);
+    VLR_HIP_OK(hipMemcpy(gx.data(), s->d_gx, gx.size() * 8, hipMemcpyDeviceToHost));
+    VLR_HIP_OK(hipMemcpy(gy.data(), s->d_gy, gy.size() * 8, hipMemcpyDeviceToHost));
+    // (the offsets came from the device: nothing below trusts them beyond what the buffers hold)
+    gx[2 * ne] = s->x_total; gy[2 * ne] = s->y_total;
+    for (size_t p = 0; p < 2 * ne; ++p)
+        if (gx[p] > gx[p + 1] || gy[p] > gy[p + 1] || gx[p + 1] > s->x_cap || gy[p + 1] > s->y_cap) return bfail(VLR_ERR_HIP, "vlr_fragpileup_result: the pair offsets of evidence %zu are not ascending", p / 2);
+    uint32_t *d_xoff = nullptr, *d_yoff = nullptr; int32_t *d_band = nullptr, *d_dist = nullptr; double *d_lnp = nullptr, *d_norm = nullptr;
+    std::vector<uint32_t> xo, yo;
+    auto body = [&]() -> int {
+        int rc;
+        hipStream_t st = 0;
+        for (size_t e0 = 0; e0 < ne;) {
+            size_t e1 = e0 + 1;
+            while (e1 < ne && gx[2 * (e1 + 1)] - gx[2 * e0] <= s->pair_byte_limit && gy[2 * (e1 + 1)] - gy[2 * e0] <= s->pair_byte_limit) ++e1;
+            const size_t np = 2 * (e1 - e0);
+            if (gx[2 * e1] - gx[2 * e0] >= (1ull << 32) || gy[2 * e1] - gy[2 * e0] >= (1ull << 32)) return bfail(VLR_ERR_UNSUPPORTED, "evidence %zu: its windows take 4 GiB or more", e0);
+            if (!d_xoff) {   // sized once, by the first (largest possible) range: at most all pairs
+                if ((rc = guarded(d_xoff, 2 * ne + 1)) != VLR_OK || (rc = guarded(d_yoff, 2 * ne + 1)) != VLR_OK || (rc = guarded(d_band, 2 * ne)) != VLR_OK ||
+                    (rc = guarded(d_dist, 2 * ne)) != VLR_OK || (rc = guarded(d_lnp, 2 * ne)) != VLR_OK)
+                    return rc;
+            }
+            xo.resize(np + 1); yo.resize(np + 1);
+            for (size_t p = 0; p <= np; ++p) { xo[p] = (uint32_t)(gx[2 * e0 + p] - gx[2 * e0]); yo[p] = (uint32_t)(gy[2 * e0 + p] - gy[2 * e0]); }
+            double t0 = now_s();
+            VLR_HIP_OK(hipMemcpy(d_xoff, xo.data(), (np + 1) * 4, hipMemcpyHostToDevice));
+            VLR_HIP_OK(hipMemcpy(d_yoff, yo.data(), (np + 1) * 4, hipMemcpyHostToDevice));
+            VLR_HIP_OK(hipMemset(d_band, 0xff, np * 4));   // -1: no band
+            if ((rc = vlr_ip::score_pairs(s->score, np, d_xoff, s->d_xb + gx[2 * e0], d_yoff, s->d_yb + gy[2 * e0], s->d_yq + gy[2 * e0], d_band, d_dist, d_lnp, st, s->rt[1],
+                                          s->rt[2], t0)) != VLR_OK)
+                return rc;
+            hipLaunchKernelGGL(vlr_ip::indelpileup_collect_kernel, dim3((unsigned)((e1 - e0 + vlr_ip::kThreads - 1) / vlr_ip::kThreads)), dim3(vlr_ip::kThreads), 0, st, d_lnp, d_dist,
+                               (uint64_t)(e1 - e0), (uint64_t)e0, (uint64_t)ne, s->d_ev);
+            if ((rc = vlr_ip::sync_stage(st, s->rt[3], t0)) != VLR_OK) return rc;
+            ++s->n_ranges;
+            e0 = e1;
+        }
+        double t0 = now_s();
+        s->ev.resize(ne);
+        VLR_HIP_OK(hipMemcpy(s->ev.data(), s->d_ev, ne * sizeof(vlr_indelpileup_hit), hipMemcpyDeviceToHost));
+        std::vector<double> norm(2 * ne);
+        for (size_t e = 0; e < ne; ++e) {
+            norm[2 * e] = s->ev[e].ln_ref; norm[2 * e + 1] = s->ev[e].ln_alt;
+            normalize_support(&norm[2 * e], &norm[2 * e + 1]);
+        }
+        if ((rc = guarded(d_norm, 2 * ne)) != VLR_OK) return rc;
+        VLR_HIP_OK(hipMemcpy(d_norm, norm.data(), 2 * ne * 8, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(frag_apply_kernel, dim3((unsigned)((ne + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, s->d_ev, s->d_evm, d_norm, (uint64_t)ne,
+                           std::min<uint64_t>(s->n_members, s->member_cap), s->d_members);
+        if ((rc = vlr_ip::sync_stage(st, s->rt[3], t0)) != VLR_OK) return rc;
+        bool ok = true;
+        rc = guard_intact(d_xoff, 2 * ne + 1, &ok);
+        if (rc == VLR_OK) rc = guard_intact(d_yoff, 2 * ne + 1, &ok);
+        if (rc == VLR_OK) rc = guard_intact(d_band, 2 * ne, &ok);
+        if (rc == VLR_OK) rc = guard_intact(d_dist, 2 * ne, &ok);
+        if (rc == VLR_OK) rc = guard_intact(d_lnp, 2 * ne, &ok);
+        if (rc == VLR_OK) rc = guard_intact(d_norm, 2 * ne, &ok);
+        if (rc == VLR_OK && !ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
+        return rc;
+    };
+    const int rc = body();
+    void* p[] = {d_xoff, d_yoff, d_band, d_dist, d_lnp, d_norm};
+    for (void* q : p) if (q) (void)hipFree(q);
+    return rc;
+}
 
 int fragment_pass(vlr_fragpileup* s) {
     const size_t nm = (size_t)s->n_members, nl = (size_t)s->n_loci;
@@ -404,20 +616,22 @@ int fragment_pass(vlr_fragpileup* s) {
 
 }  // namespace vlr_fp
 
-extern "C" {
+namespace vlr_fp {
 
-int vlr_fragpileup_open(int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int32_t* len, const uint8_t* kind,
-                        const uint8_t* ref_bases, const uint8_t* alt_bases, int realign_indel_reads, int64_t window, int max_mapq, int max_read_len,
-                        int64_t member_capacity, int64_t name_capacity, int64_t key_capacity, int64_t window_bytes, vlr_fragpileup** out) {
-    using namespace vlr_fp;
+// what vlr_fragpileup_open_realign gives beyond vlr_fragpileup_open
+struct RealignOpen { const char* fasta; int window; vlr_ip::ScoreParams score; int64_t evidence_capacity, pair_byte_limit; };
+
+int open_impl(const char* api, int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int32_t* len, const uint8_t* kind, const uint8_t* ref_bases,
+              const uint8_t* alt_bases, int realign_indel_reads, int64_t window, int max_mapq, int max_read_len, int64_t member_capacity, int64_t name_capacity,
+              int64_t key_capacity, int64_t window_bytes, const RealignOpen* ro, vlr_fragpileup** out) {
     if (!out || n_loci < 0 || n_loci > 0x7fffffff || member_capacity < 0 || member_capacity > 0x7fffffff || name_capacity < 0 || key_capacity < 0 || key_capacity > 0x7fffffff ||
         window_bytes < 0 || window < 0 ||
         window > ((int64_t)1 << 40) || max_mapq < 0 || max_mapq > 255 || (n_loci > 0 && (!ref_id || !start || !len || !kind || !ref_bases || !alt_bases)))
-        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_open: bad argument");
-    if (max_read_len <= 0) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_open: max_read_len must be positive");
+        return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: bad argument", api);
+    if (max_read_len <= 0) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: max_read_len must be positive", api);
     *out = nullptr;
     std::vector<uint64_t> base_off;
-    int rc = vlr_bp::check_snv_mnv_loci("vlr_fragpileup_open", n_loci, ref_id, start, len, kind, base_off);
+    int rc = vlr_bp::check_snv_mnv_loci(api, n_loci, ref_id, start, len, kind, base_off);
     if (rc != VLR_OK || (rc = vlr_bam::use_device(device)) != VLR_OK) return rc;
     vlr_fragpileup* s = new vlr_fragpileup();
     s->realign = realign_indel_reads ? 1 : 0;
@@ -431,7 +645,34 @@ int vlr_fragpileup_open(int device, int64_t n_loci, const int32_t* ref_id, const
     s->locus_rec.assign((size_t)n_loci, vlr_fragpileup_locus{0, 0, 0, VLR_BASEPILEUP_NO_READ_POSITION, 0});
     const size_t nl = (size_t)n_loci;
     auto step = [&](int r) { if (rc == VLR_OK) rc = r; };
-    step(vlr_bam::open_session(*s, device, window_bytes, K_N));
+    if (ro != nullptr) {
+        s->realigning = true;
+        s->k_n = K_N_REALIGN;
+        s->rl_window = ro->window;
+        s->score = ro->score;
+        s->h_ref_id.assign(ref_id, ref_id + n_loci);
+        for (int64_t k = 0; k < n_loci; ++k) s->h_end.push_back(start[k] + (int64_t)len[k]);
+        s->ctg.fasta = ro->fasta;
+        s->ev_cap = (uint64_t)ro->evidence_capacity;
+        if (ro->pair_byte_limit > 0 && (uint64_t)ro->pair_byte_limit < vlr_ip::kPairByteLimit) s->pair_byte_limit = (uint64_t)ro->pair_byte_limit;
+        // an evidence's pairs: a ref window of at most 2 rw bases and an alt window of at most 2 rw + the locus; a read window of at most
+        // 2 * window <= 128 bases, twice
+        const uint64_t rw = (uint64_t)ro->window * 3 / 2;
+        s->x_cap = s->ev_cap * (4 * rw + VLR_BASEPILEUP_MAX_LEN);
+        s->y_cap = s->ev_cap * 2 * (uint64_t)vlr_ip::kMaxPatternLen;
+        step(vlr_bam::read_fai(s->ctg.fasta, s->ctg.fai));
+        step(guarded(s->d_ev, (size_t)s->ev_cap));
+        step(guarded(s->d_evm, (size_t)s->ev_cap));
+        step(guarded(s->d_gx, 2 * (size_t)s->ev_cap + 1));
+        step(guarded(s->d_gy, 2 * (size_t)s->ev_cap + 1));
+        step(guarded(s->d_xb, (size_t)s->x_cap));
+        step(guarded(s->d_yb, (size_t)s->y_cap));
+        step(guarded(s->d_yq, (size_t)s->y_cap));
+        // offsets nobody wrote read as empty windows
+        if (rc == VLR_OK && (hipMemset(s->d_gx, 0, (2 * (size_t)s->ev_cap + 1) * 8) != hipSuccess || hipMemset(s->d_gy, 0, (2 * (size_t)s->ev_cap + 1) * 8) != hipSuccess))
+            rc = bfail(VLR_ERR_HIP, "%s: hipMemset of the pair offsets failed", api);
+    }
+    step(vlr_bam::open_session(*s, device, window_bytes, s->k_n));
     step(s->dl.upload(n_loci, ref_id, start, len, kind, base_off, ref_bases, alt_bases));
     step(zeros(s->d_major_key, nl)); step(zeros(s->d_have_key, nl));
     step(zeros(s->d_lcnt, nl)); step(zeros(s->d_cursor, nl)); step(zeros(s->d_nobs, nl)); step(zeros(s->d_major, nl)); step(zeros(s->d_lstatus, nl));
@@ -444,9 +685,37 @@ int vlr_fragpileup_open(int device, int64_t n_loci, const int32_t* ref_id, const
     return VLR_OK;
 }
 
+}  // namespace vlr_fp
+
+extern "C" {
+
+int vlr_fragpileup_open(int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int32_t* len, const uint8_t* kind,
+                        const uint8_t* ref_bases, const uint8_t* alt_bases, int realign_indel_reads, int64_t window, int max_mapq, int max_read_len,
+                        int64_t member_capacity, int64_t name_capacity, int64_t key_capacity, int64_t window_bytes, vlr_fragpileup** out) {
+    return vlr_fp::open_impl("vlr_fragpileup_open", device, n_loci, ref_id, start, len, kind, ref_bases, alt_bases, realign_indel_reads, window, max_mapq, max_read_len,
+                             member_capacity, name_capacity, key_capacity, window_bytes, nullptr, out);
+}
+
+int vlr_fragpileup_open_realign(int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int32_t* len, const uint8_t* kind,
+                                const uint8_t* ref_bases, const uint8_t* alt_bases, int realign_indel_reads, int64_t window, int max_mapq,
+                                int max_read_len, int64_t member_capacity, int64_t name_capacity, int64_t key_capacity, int64_t window_bytes, const char* fasta_path,
+                                int realign_window, int mode, const double gap[4], const double* hop, int64_t evidence_capacity,
+                                int64_t pair_byte_limit, vlr_fragpileup** out) {
+    using namespace vlr_fp;
+    if (!fasta_path || !gap || evidence_capacity < 0 || evidence_capacity > 0x7fffffff || pair_byte_limit < 0)
+        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_open_realign: bad argument");
+    RealignOpen ro{fasta_path, realign_window, vlr_ip::ScoreParams(), evidence_capacity, pair_byte_limit};
+    const int rc = vlr_ip::check_score_params("vlr_fragpileup_open_realign", realign_window, mode, gap, hop, ro.score);
+    if (rc != VLR_OK) return rc;
+    return open_impl("vlr_fragpileup_open_realign", device, n_loci, ref_id, start, len, kind, ref_bases, alt_bases, realign_indel_reads, window, max_mapq, max_read_len,
+                     member_capacity, name_capacity, key_capacity, window_bytes, &ro, out);
+}
+
 int vlr_fragpileup_add_bam(vlr_fragpileup* s, const char* bam_path) {
     if (!s) return vlr_bam::bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_add_bam: null");
-    return vlr_bam::add_bam(*s, bam_path, "vlr_fragpileup_add_bam", {&s->t[0], &s->t[1], &s->t[2], &s->t[6], &s->t[5]}, nullptr,
+    std::function<int(const std::vector<std::string>&)> on_header;
+    if (s->realigning) on_header = [s, bam_path](const std::vector<std::string>& names) { return vlr_fp::on_header(s, names, bam_path); };
+    return vlr_bam::add_bam(*s, bam_path, "vlr_fragpileup_add_bam", {&s->t[0], &s->t[1], &s->t[2], &s->t[6], &s->t[5]}, on_header,
                             [s](vlr_dev_file* df, int64_t n, hipStream_t st) { return vlr_fp::run_chunk(s, df, n, st); });
 }
 
@@ -460,13 +729,26 @@ int vlr_fragpileup_result(vlr_fragpileup* s, vlr_fragpileup_counts* r) {
         if (rc == VLR_OK) rc = guard_intact(s->d_members, (size_t)s->member_cap, &ok);
         if (rc == VLR_OK) rc = guard_intact(s->d_names, (size_t)s->name_cap, &ok);
         if (rc == VLR_OK) rc = guard_intact(s->d_keys, (size_t)s->key_cap, &ok);
+        if (s->realigning) {
+            if (rc == VLR_OK) rc = guard_intact(s->d_ev, (size_t)s->ev_cap, &ok);
+            if (rc == VLR_OK) rc = guard_intact(s->d_evm, (size_t)s->ev_cap, &ok);
+            if (rc == VLR_OK) rc = guard_intact(s->d_gx, 2 * (size_t)s->ev_cap + 1, &ok);
+            if (rc == VLR_OK) rc = guard_intact(s->d_gy, 2 * (size_t)s->ev_cap + 1, &ok);
+            if (rc == VLR_OK) rc = guard_intact(s->d_xb, (size_t)s->x_cap, &ok);
+            if (rc == VLR_OK) rc = guard_intact(s->d_yb, (size_t)s->y_cap, &ok);
+            if (rc == VLR_OK) rc = guard_intact(s->d_yq, (size_t)s->y_cap, &ok);
+        }
         if (rc != VLR_OK) return rc;
         if (!ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
         if (vlr_bam::bad_record_seen(*s)) s->status |= VLR_FRAGPILEUP_BAD_RECORD;
         if (s->n_members > s->member_cap) s->status |= VLR_FRAGPILEUP_MEMBER_OVERFLOW;
         if (s->n_name_bytes > s->name_cap) s->status |= VLR_FRAGPILEUP_NAME_OVERFLOW;
         if (s->n_keys > s->key_cap) s->status |= VLR_FRAGPILEUP_KEY_OVERFLOW;
-        if (!(s->status & (VLR_FRAGPILEUP_MEMBER_OVERFLOW | VLR_FRAGPILEUP_NAME_OVERFLOW | VLR_FRAGPILEUP_KEY_OVERFLOW | VLR_FRAGPILEUP_GUARD_DAMAGED)) && s->n_members && s->n_loci) {
+        if (s->ev_overflow) s->status |= VLR_FRAGPILEUP_EVIDENCE_OVERFLOW;
+        if (!(s->status & (VLR_FRAGPILEUP_MEMBER_OVERFLOW | VLR_FRAGPILEUP_NAME_OVERFLOW | VLR_FRAGPILEUP_KEY_OVERFLOW | VLR_FRAGPILEUP_EVIDENCE_OVERFLOW | VLR_FRAGPILEUP_GUARD_DAMAGED)) &&
+            s->n_members && s->n_loci) {
+            if (s->realigning && s->n_ev && (rc = realign_pass(s)) != VLR_OK) return rc;
+            if (s->status & VLR_FRAGPILEUP_GUARD_DAMAGED) { s->collected = true; return vlr_fragpileup_result(s, r); }
             const double t0 = now_s();
             rc = fragment_pass(s);
             if (rc != VLR_OK) return rc;
@@ -474,7 +756,7 @@ int vlr_fragpileup_result(vlr_fragpileup* s, vlr_fragpileup_counts* r) {
         }
         s->collected = true;
     }
-    const bool over = (s->status & (VLR_FRAGPILEUP_MEMBER_OVERFLOW | VLR_FRAGPILEUP_NAME_OVERFLOW | VLR_FRAGPILEUP_KEY_OVERFLOW)) != 0;
+    const bool over = (s->status & (VLR_FRAGPILEUP_MEMBER_OVERFLOW | VLR_FRAGPILEUP_NAME_OVERFLOW | VLR_FRAGPILEUP_KEY_OVERFLOW | VLR_FRAGPILEUP_EVIDENCE_OVERFLOW)) != 0;
     r->n_obs = (int64_t)s->obs.size();
     r->n_members = over ? 0 : (int64_t)s->n_members;
     r->n_records = (int64_t)s->n_records;
@@ -499,12 +781,35 @@ int vlr_fragpileup_read(vlr_fragpileup* s, vlr_fragpileup_obs* obs, int64_t n_ob
     return VLR_OK;
 }
 
+int vlr_fragpileup_realign_result(vlr_fragpileup* s, vlr_fragpileup_realign_counts* r) {
+    using namespace vlr_fp;
+    if (!s || !r || !s->collected) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_realign_result: call vlr_fragpileup_result first");
+    if (!s->realigning) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_realign_result: the session was not opened with vlr_fragpileup_open_realign");
+    r->n_evidences = (int64_t)s->ev.size();
+    r->needed_evidences = (int64_t)s->n_ev;
+    r->x_bytes = s->ev_overflow ? 0 : (int64_t)s->x_total;
+    r->y_bytes = s->ev_overflow ? 0 : (int64_t)s->y_total;
+    r->n_ranges = s->n_ranges;
+    for (int k = 0; k < 4; ++k) r->seconds[k] = s->rt[k];
+    return VLR_OK;
+}
+
+int vlr_fragpileup_read_realigned(vlr_fragpileup* s, vlr_indelpileup_hit* hits, int64_t n) {
+    using namespace vlr_fp;
+    if (!s || !s->collected || !s->realigning) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_read_realigned: call vlr_fragpileup_result on a realigning session first");
+    if (n != (int64_t)s->ev.size() || (n > 0 && !hits)) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_read_realigned: size differs from vlr_fragpileup_realign_result");
+    if (n) memcpy(hits, s->ev.data(), (size_t)n * sizeof(vlr_indelpileup_hit));
+    return VLR_OK;
+}
+
 void vlr_fragpileup_close(vlr_fragpileup* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     vlr_bam::close_session(*s);
     s->dl.free();
-    void* p[] = {s->d_members, s->d_names, s->d_keys, s->d_major_key, s->d_have_key, s->d_lcnt, s->d_cursor, s->d_nobs, s->d_major, s->d_lstatus, s->d_loff, s->d_obsoff};
+    s->ctg.free();
+    void* p[] = {s->d_members, s->d_names, s->d_keys, s->d_major_key, s->d_have_key, s->d_lcnt, s->d_cursor, s->d_nobs, s->d_major, s->d_lstatus, s->d_loff, s->d_obsoff,
+                 s->d_ev, s->d_evm, s->d_gx, s->d_gy, s->d_xb, s->d_yb, s->d_yq, s->d_src};
     for (void* q : p) if (q) (void)hipFree(q);
     delete s;
 }

@@ -33,13 +33,9 @@
 
 #include "vlr_bamsession.h"
 #include "vlr_indelpileup.h"
+#include "vlr_pairscore.h"
 
 static_assert(sizeof(vlr_indelpileup_hit) == 64, "hit layout");
-
-extern "C" int vlr_launch_edit_kernel(const vlr_realign_batch_desc* b, int32_t* dist, int32_t* end, int32_t* n_hits, void* stream);
-extern "C" int vlr_launch_realign_kernel(const vlr_realign_batch_desc* b, double* ln_prob, void* stream);
-extern "C" int vlr_launch_pathhmm_kernel(const vlr_realign_batch_desc* b, double* ln_prob, void* stream);
-extern "C" int vlr_launch_homopoly_kernel(const vlr_realign_batch_desc* b, const double* hop, double* ln_prob, void* stream);
 
 namespace vlr_ip {
 
@@ -47,15 +43,7 @@ using vlr_bam::C_BAD;
 using vlr_bam::C_FIRST_BAD;
 using vlr_bam::C_REJECTED;
 enum { K_EV = 0, K_X = 1, K_Y = 2, K_N = 3 };   // the three counts of a record
-constexpr int kThreads = 256;
-constexpr int kEditBand = 4;                 // pairhmm.rs:20
-constexpr uint64_t kPairByteLimit = 1ull << 31;
-
-// where the windows of an evidence come from (chunk-local, one per evidence of the sub-range)
-struct Src {
-    uint64_t seq, qual;   // offsets of the record's packed SEQ and its QUAL from the chunk's base
-    uint32_t l_seq, pad;
-};
+// (kThreads, kEditBand, kPairByteLimit, Src, the gather / band / collect kernels and the scoring of a range of pairs: vlr_pairscore.h)
 
 __global__ __launch_bounds__(kThreads) void indelpileup_count_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0, Loci L,
                                                                      int window, uint64_t* __restrict__ cnt, int64_t stride, unsigned long long* __restrict__ counters) {
@@ -103,65 +91,19 @@ __global__ __launch_bounds__(kThreads) void indelpileup_fill_kernel(const uint8_
     }
 }
 
-// One wave per evidence: lane-contiguous copies of its four windows
-__global__ __launch_bounds__(kThreads) void indelpileup_gather_kernel(const uint8_t* __restrict__ base, uint64_t n_ev, const vlr_indelpileup_hit* __restrict__ hits, Loci L,
-                                                                      const uint8_t* const* __restrict__ ctg, const uint8_t* __restrict__ alt_bases,
-                                                                      const Src* __restrict__ src, const uint32_t* __restrict__ x_offset, const uint32_t* __restrict__ y_offset,
-                                                                      uint8_t* __restrict__ x_bases, uint8_t* __restrict__ y_bases, uint8_t* __restrict__ y_quals) {
-    const uint64_t e = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    if (e >= n_ev) return;
-    const vlr_indelpileup_hit h = hits[e];
-    if (h.status || (int64_t)h.locus >= L.n) return;
-    const int32_t ref_id = L.ref_id[h.locus];
-    const uint8_t* contig = ctg[ref_id];
-    const int64_t contig_len = L.ctg_len[ref_id];
-    const Src s = src[e];
-    const uint32_t x_ref = x_offset[2 * e], x_alt = x_offset[2 * e + 1], x_end = x_offset[2 * e + 2];
-    const uint32_t y_ref = y_offset[2 * e], y_alt = y_offset[2 * e + 1], y_end = y_offset[2 * e + 2];
-    for (uint32_t k = lane; k < h.ref_len && x_ref + k < x_alt; k += 64) x_bases[x_ref + k] = window_byte(WB_REF_BASE, contig, contig_len, h.ref_begin, k);
-    const uint8_t* alt = alt_bases + L.alt_off[h.locus];
-    const uint32_t alt_len = (uint32_t)(L.alt_off[h.locus + 1] - L.alt_off[h.locus]);
-    for (uint32_t k = lane; k < alt_len && x_alt + k < x_end; k += 64) x_bases[x_alt + k] = alt[k];
-    for (uint32_t k = lane; k < h.read_len && y_ref + k < y_alt && y_alt + k < y_end; k += 64) {
-        const uint8_t b = window_byte(WB_READ_BASE, base + s.seq, s.l_seq, h.read_begin, k);
-        const uint8_t q = window_byte(WB_READ_QUAL, base + s.qual, s.l_seq, h.read_begin, k);
-        y_bases[y_ref + k] = b; y_quals[y_ref + k] = q;
-        y_bases[y_alt + k] = b; y_quals[y_alt + k] = q;
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void indelpileup_band_kernel(const int32_t* __restrict__ dist, int64_t n_pairs, int32_t* __restrict__ band) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n_pairs) band[p] = dist[p] >= 0 ? dist[p] + kEditBand : -1;
-}
-
-__global__ __launch_bounds__(kThreads) void indelpileup_collect_kernel(const double* __restrict__ lnp, const int32_t* __restrict__ dist, uint64_t n_ev, uint64_t hit0,
-                                                                       uint64_t capacity, vlr_indelpileup_hit* __restrict__ hits) {
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n_ev || hit0 + e >= capacity) return;
-    vlr_indelpileup_hit* h = hits + hit0 + e;
-    h->ln_ref = lnp[2 * e]; h->ln_alt = lnp[2 * e + 1];
-    h->dist_ref = dist[2 * e]; h->dist_alt = dist[2 * e + 1];
-}
-
 }  // namespace vlr_ip
 
 struct vlr_indelpileup : vlr_bam::Session {
-    int window = 64, mode = VLR_INDELPILEUP_EXACT;
+    int window = 64;
     bool keep_pairs = false;
-    double gap[4] = {0, 0, 0, 0};
-    double hop[16];
+    vlr_ip::ScoreParams score;   // mode, gap, hop
     int64_t n_loci = 0;
     uint64_t capacity = 0;
     uint64_t pair_byte_limit = vlr_ip::kPairByteLimit;
-    std::string fasta;
-    vlr_bam::Fai fai;
     std::vector<int32_t> h_ref_id;   // of the loci
-    vlr_bam::Contigs contigs;        // uploaded contigs by name
+    vlr_ip::ContigTable ctg;         // the reference, the uploaded contigs and the table of the file being read
     // device state (the record arrays of the base: [K_N][rec_cap] u64 counts and their offsets; d_total[K_N])
     int32_t* d_ref_id = nullptr; int64_t *d_start = nullptr, *d_end = nullptr; uint64_t* d_alt_off = nullptr; uint8_t* d_altb = nullptr;
-    const uint8_t** d_ctg = nullptr; int64_t* d_ctg_len = nullptr; size_t ctg_cap = 0;
     vlr_indelpileup_hit* d_hits = nullptr;
     vlr_ip::Src* d_src = nullptr; uint32_t *d_xoff = nullptr, *d_yoff = nullptr; int32_t *d_band = nullptr, *d_dist = nullptr; double* d_lnp = nullptr; size_t ev_cap = 0;
     uint8_t *d_xb = nullptr, *d_yb = nullptr, *d_yq = nullptr; size_t x_cap = 0, y_cap = 0;
@@ -184,38 +126,12 @@ using vlr_bam::now_s;
 using vlr_bam::upload;
 
 
-// the contig table of a file: entry k = contig k of its header when a locus lies on it
+// the contig table of a file (vlr_pairscore.h), into the loci the kernels see
 int on_header(vlr_indelpileup* s, const std::vector<std::string>& names, const char* path) {
-    const size_t n = names.size();
-    std::vector<const uint8_t*> ctg(n + 1, nullptr);
-    std::vector<int64_t> len(n + 1, -1);
-    for (int32_t id : s->h_ref_id) {
-        if ((size_t)id >= n) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: a locus lies on reference id %d, the header has %zu contigs", path, (int)id, n);
-        if (len[(size_t)id] >= 0) continue;
-        std::pair<uint8_t*, uint64_t> c;
-        const int rc = vlr_bam::load_contig(s->fasta, s->fai, s->contigs, names[(size_t)id], path, true, c);
-        if (rc != VLR_OK) return rc;
-        ctg[(size_t)id] = c.first; len[(size_t)id] = (int64_t)c.second;
-    }
-    if (n + 1 > s->ctg_cap) {
-        size_t c1 = s->ctg_cap, c2 = s->ctg_cap;
-        int rc;
-        if ((rc = grow(s->d_ctg, c1, n + 1)) != VLR_OK || (rc = grow(s->d_ctg_len, c2, n + 1)) != VLR_OK) return rc;
-        s->ctg_cap = std::min(c1, c2);
-    }
-    VLR_HIP_OK(hipMemcpy((void*)s->d_ctg, ctg.data(), (n + 1) * sizeof(uint8_t*), hipMemcpyHostToDevice));
-    VLR_HIP_OK(hipMemcpy(s->d_ctg_len, len.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    s->loci.n_refs = (int64_t)n;
-    s->loci.ctg_len = s->d_ctg_len;
-    return VLR_OK;
-}
-
-int sync_stage(hipStream_t st, double& t, double& t0) {
-    VLR_HIP_OK(hipStreamSynchronize(st));
-    VLR_HIP_OK(hipGetLastError());
-    const double now = now_s();
-    t += now - t0;
-    t0 = now;
+    const int rc = s->ctg.on_header(s->h_ref_id, names, path);
+    if (rc != VLR_OK) return rc;
+    s->loci.n_refs = (int64_t)names.size();
+    s->loci.ctg_len = s->ctg.d_len;
     return VLR_OK;
 }
 
@@ -246,24 +162,10 @@ int run_range(vlr_indelpileup* s, const uint8_t* d_base, const uint64_t* d_start
     hipLaunchKernelGGL(indelpileup_fill_kernel, dim3(rec_blocks), dim3(kThreads), 0, st, d_base, d_starts, rec0, s->loci, s->window, (const uint64_t*)s->d_cnt, s->d_off, stride, g, hit0,
                        s->capacity, s->d_hits, s->d_src, s->d_xoff, s->d_yoff, s->d_band);
     const unsigned waves_per_block = kThreads / 64;
-    hipLaunchKernelGGL(indelpileup_gather_kernel, dim3((unsigned)((ne + waves_per_block - 1) / waves_per_block)), dim3(kThreads), 0, st, d_base, (uint64_t)ne,
-                       s->d_hits + hit0, s->loci, s->d_ctg, s->d_altb, s->d_src, s->d_xoff, s->d_yoff, s->d_xb, s->d_yb, s->d_yq);
+    hipLaunchKernelGGL((indelpileup_gather_kernel<IndelWindows, uint32_t>), dim3((unsigned)((ne + waves_per_block - 1) / waves_per_block)), dim3(kThreads), 0, st, d_base,
+                       (uint64_t)ne, s->d_hits + hit0, IndelWindows{s->loci, s->ctg.d_ctg, s->d_altb}, s->d_src, s->d_xoff, s->d_yoff, s->d_xb, s->d_yb, s->d_yq);
     if ((rc = sync_stage(st, s->t[4], t0)) != VLR_OK) return rc;
-    vlr_realign_batch_desc b;
-    b.n_pairs = (int64_t)np;
-    b.x_offset = s->d_xoff; b.x_bases = s->d_xb; b.y_offset = s->d_yoff; b.y_bases = s->d_yb; b.y_quals = s->d_yq;
-    b.max_edit_dist = s->d_band;
-    for (int k = 0; k < 4; ++k) b.gap[k] = s->gap[k];
-    const unsigned pair_blocks = (unsigned)((np + kThreads - 1) / kThreads);
-    hipError_t e = (hipError_t)vlr_launch_edit_kernel(&b, s->d_dist, nullptr, nullptr, (void*)st);
-    if (e != hipSuccess) return bfail(VLR_ERR_HIP, "edit-distance kernel launch: %s", hipGetErrorString(e));
-    if (s->mode != VLR_INDELPILEUP_FAST) hipLaunchKernelGGL(indelpileup_band_kernel, dim3(pair_blocks), dim3(kThreads), 0, st, s->d_dist, (int64_t)np, s->d_band);
-    if ((rc = sync_stage(st, s->t[5], t0)) != VLR_OK) return rc;
-    if (s->mode == VLR_INDELPILEUP_FAST) e = (hipError_t)vlr_launch_pathhmm_kernel(&b, s->d_lnp, (void*)st);
-    else if (s->mode == VLR_INDELPILEUP_HOMOPOLYMER) e = (hipError_t)vlr_launch_homopoly_kernel(&b, s->hop, s->d_lnp, (void*)st);
-    else e = (hipError_t)vlr_launch_realign_kernel(&b, s->d_lnp, (void*)st);
-    if (e != hipSuccess) return bfail(VLR_ERR_HIP, "realign kernel launch: %s", hipGetErrorString(e));
-    if ((rc = sync_stage(st, s->t[6], t0)) != VLR_OK) return rc;
+    if ((rc = score_pairs(s->score, np, s->d_xoff, s->d_xb, s->d_yoff, s->d_yb, s->d_yq, s->d_band, s->d_dist, s->d_lnp, st, s->t[5], s->t[6], t0)) != VLR_OK) return rc;
     hipLaunchKernelGGL(indelpileup_collect_kernel, dim3((unsigned)((ne + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, s->d_lnp, s->d_dist, (uint64_t)ne, hit0, s->capacity,
                        s->d_hits);
     if (s->keep_pairs) {
@@ -336,19 +238,9 @@ int vlr_indelpileup_open(int device, const char* fasta_path, int64_t n_loci, con
         (n_loci > 0 && (!ref_id || !start || !end || !kind || !alt_offset || !alt_bases)))
         return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: bad argument");
     *out = nullptr;
-    if (window < 1 || window > VLR_INDELPILEUP_MAX_WINDOW)
-        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: window %d outside 1 .. %d (a read window must fit the 128 bases of the kernels)", window,
-                     VLR_INDELPILEUP_MAX_WINDOW);
-    if (mode != VLR_INDELPILEUP_EXACT && mode != VLR_INDELPILEUP_FAST && mode != VLR_INDELPILEUP_HOMOPOLYMER)
-        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: unknown mode %d", mode);
-    for (int k = 0; k < 4; ++k)
-        if (gap[k] != gap[k] || gap[k] > 0.0) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: gap[%d] is not a log probability", k);
-    if (std::exp(gap[0]) + std::exp(gap[1]) > 1.0 + 1e-12) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: P(gap in x) + P(gap in y) exceeds one");
-    if (mode == VLR_INDELPILEUP_HOMOPOLYMER) {
-        if (!hop) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: null hop parameters");
-        for (int k = 0; k < 16; ++k)
-            if (!(hop[k] <= 0.0)) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: hop parameter %d is not a ln probability", k);
-    }
+    ScoreParams sp;
+    int rc = check_score_params("vlr_indelpileup_open", window, mode, gap, hop, sp);
+    if (rc != VLR_OK) return rc;
     int64_t max_len = 0;
     for (int64_t k = 0; k < n_loci; ++k) {
         if (kind[k] > VLR_INDELPILEUP_REPLACEMENT || ref_id[k] < 0 || start[k] < 0 || end[k] <= start[k] || alt_offset[k + 1] < alt_offset[k] || (k == 0 && alt_offset[0] != 0))
@@ -358,13 +250,10 @@ int vlr_indelpileup_open(int device, const char* fasta_path, int64_t n_loci, con
             return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_indelpileup_open: loci are not sorted by (ref_id, start) at %lld", (long long)k);
         max_len = std::max(max_len, end[k] - start[k]);
     }
-    int rc = vlr_bam::use_device(device);
-    if (rc != VLR_OK) return rc;
+    if ((rc = vlr_bam::use_device(device)) != VLR_OK) return rc;
     vlr_indelpileup* s = new vlr_indelpileup();
     s->device = device;
-    s->window = window; s->mode = mode; s->keep_pairs = keep_pairs != 0;
-    for (int k = 0; k < 4; ++k) s->gap[k] = gap[k];
-    for (int k = 0; k < 16; ++k) s->hop[k] = hop && mode == VLR_INDELPILEUP_HOMOPOLYMER ? hop[k] : -HUGE_VAL;
+    s->window = window; s->score = sp; s->keep_pairs = keep_pairs != 0;
     s->n_loci = n_loci;
     s->capacity = (uint64_t)hit_capacity;
     // tuning / test knob: the pair bytes a record sub-range may hold (the uint32 offsets need at most 2^31)
@@ -372,10 +261,10 @@ int vlr_indelpileup_open(int device, const char* fasta_path, int64_t n_loci, con
         const unsigned long long x = strtoull(v, nullptr, 10);
         if (x >= 1 && x <= kPairByteLimit) s->pair_byte_limit = x;
     }
-    s->fasta = fasta_path;
+    s->ctg.fasta = fasta_path;
     s->h_ref_id.assign(ref_id, ref_id + n_loci);
     const uint64_t zero = 0;
-    rc = vlr_bam::read_fai(s->fasta, s->fai);
+    rc = vlr_bam::read_fai(s->ctg.fasta, s->ctg.fai);
     auto step = [&](int r) { if (rc == VLR_OK) rc = r; };
     step(upload(s->d_ref_id, ref_id, (size_t)n_loci));
     step(upload(s->d_start, start, (size_t)n_loci));
@@ -473,10 +362,10 @@ void vlr_indelpileup_close(vlr_indelpileup* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     vlr_bam::close_session(*s);
-    void* p[] = {s->d_ref_id, s->d_start, s->d_end, s->d_alt_off, s->d_altb, (void*)s->d_ctg, s->d_ctg_len, s->d_hits,
+    void* p[] = {s->d_ref_id, s->d_start, s->d_end, s->d_alt_off, s->d_altb, s->d_hits,
                  s->d_src, s->d_xoff, s->d_yoff, s->d_band, s->d_dist, s->d_lnp, s->d_xb, s->d_yb, s->d_yq};
     for (void* q : p) if (q) (void)hipFree(q);
-    for (auto& c : s->contigs) if (c.second.first) (void)hipFree(c.second.first);
+    s->ctg.free();
     delete s;
 }
 

@@ -26,7 +26,7 @@ EXPORTS = [
     "vlr_plan_n_samples", "vlr_plan_set_max_depth", "vlr_plan_set_max_obs", "vlr_plan_fit_max_obs", "vlr_plan_reserve", "vlr_batch_run", "vlr_batch_run_host", "vlr_batch_run_device_in",
     "vlr_plan_last_kernel_ms", "vlr_plan_last_instance", "vlr_plan_work_counters", "vlr_plan_fused_counters", "vlr_host_alloc", "vlr_host_free",
     "vlr_node_create", "vlr_node_destroy", "vlr_node_n_devices", "vlr_node_device", "vlr_node_plan", "vlr_node_set_max_depth", "vlr_node_set_max_obs", "vlr_node_shard_range", "vlr_node_batch_run_host",
-    "vlr_realign_batch", "vlr_realign_batch_host", "vlr_realign_fast_batch", "vlr_realign_fast_batch_host", "vlr_realign_homopolymer_batch", "vlr_realign_homopolymer_batch_host", "vlr_edit_distance_batch", "vlr_edit_distance_batch_host", "vlr_fdr_threshold", "vlr_contamination_posterior", "vlr_bamstats_open", "vlr_bamstats_add_bam", "vlr_bamstats_result", "vlr_bamstats_read", "vlr_bamstats_close", "vlr_basepileup_open", "vlr_basepileup_add_bam", "vlr_basepileup_result", "vlr_basepileup_read", "vlr_basepileup_tables", "vlr_basepileup_close", "vlr_indelpileup_open", "vlr_indelpileup_add_bam", "vlr_indelpileup_result", "vlr_indelpileup_read", "vlr_indelpileup_read_pairs", "vlr_indelpileup_close", "vlr_fragpileup_open", "vlr_fragpileup_add_bam", "vlr_fragpileup_result", "vlr_fragpileup_read", "vlr_fragpileup_close", "vlr_selftest_math", "vlr_selftest_stream", "vlr_selftest_format_fixed", "vlr_selftest_afd_text",
+    "vlr_realign_batch", "vlr_realign_batch_host", "vlr_realign_fast_batch", "vlr_realign_fast_batch_host", "vlr_realign_homopolymer_batch", "vlr_realign_homopolymer_batch_host", "vlr_edit_distance_batch", "vlr_edit_distance_batch_host", "vlr_fdr_threshold", "vlr_contamination_posterior", "vlr_bamstats_open", "vlr_bamstats_add_bam", "vlr_bamstats_result", "vlr_bamstats_read", "vlr_bamstats_close", "vlr_basepileup_open", "vlr_basepileup_add_bam", "vlr_basepileup_result", "vlr_basepileup_read", "vlr_basepileup_tables", "vlr_basepileup_close", "vlr_indelpileup_open", "vlr_indelpileup_add_bam", "vlr_indelpileup_result", "vlr_indelpileup_read", "vlr_indelpileup_read_pairs", "vlr_indelpileup_close", "vlr_fragpileup_open", "vlr_fragpileup_add_bam", "vlr_fragpileup_result", "vlr_fragpileup_read", "vlr_fragpileup_close", "vlr_fragpileup_open_realign", "vlr_fragpileup_realign_result", "vlr_fragpileup_read_realigned", "vlr_selftest_math", "vlr_selftest_stream", "vlr_selftest_format_fixed", "vlr_selftest_afd_text",
     "vlr_obs_read", "vlr_obs_table_free", "vlr_obs_table_batch", "vlr_obs_table_sites", "vlr_obs_write", "vlr_calls_write", "vlr_ingest_last_timings", "vlr_ingest_total_timings",
     "vlr_obs_reader_open", "vlr_obs_reader_open_device", "vlr_obs_table_device_batch", "vlr_obs_reader_set_host_columns", "vlr_obs_reader_set_async_columns", "vlr_obs_table_fetch_columns", "vlr_obs_table_summaries", "vlr_bgzf_inflate", "vlr_ingest_device_timings", "vlr_ingest_device_trim", "vlr_obs_reader_open_device_shard", "vlr_obs_reader_shard_row_size", "vlr_obs_reader_shard_counts", "vlr_obs_reader_shard_assign", "vlr_node_obs_readers_open", "vlr_obs_reader_next", "vlr_obs_reader_close", "vlr_calls_writer_open", "vlr_calls_writer_append", "vlr_calls_writer_close", "vlr_calls_writer_set_part", "vlr_calls_concat_parts", "vlr_calls_filter_fdr",
     "vlr_posterior_odds_keep", "vlr_range_group_lse", "vlr_calls_filter_odds", "vlr_calls_mutational_burden", "vlr_callstats_last_kernel_ms",
@@ -37,7 +37,7 @@ EXPORTS = [
 SOURCES = tuple("csrc/" + f for f in (
     "vlr_kernels.hip", "vlr_kernels_lean.hip", "vlr_kernels_deep.hip", "vlr_kernels_wide.hip", "vlr_kernels_widedeep.hip", "vlr_realign.hip",
     "vlr_fdr.hip", "vlr_contam.hip", "vlr_callstats.hip", "vlr_bamstats.hip", "vlr_basepileup.hip", "vlr_indelpileup.hip", "vlr_fragpileup.hip", "vlr_inflate.hip", "vlr_decode.hip", "vlr_host.cpp", "vlr_ingest.cpp",
-    "vlr_plan.h", "vlr_gpuio.h", "vlr_callstats.h", "vlr_bamstream.h", "vlr_bamsession.h", "vlr_basepileup.h", "vlr_indelpileup.h", "vlr_fragpileup.h")) + ("../include/vlr.h", "../include/vlr_detmath.h")
+    "vlr_plan.h", "vlr_gpuio.h", "vlr_callstats.h", "vlr_bamstream.h", "vlr_bamsession.h", "vlr_basepileup.h", "vlr_indelpileup.h", "vlr_fragpileup.h", "vlr_pairscore.h")) + ("../include/vlr.h", "../include/vlr_detmath.h")
 
 
 class EngineError(RuntimeError):
@@ -190,6 +190,13 @@ def bind_fragpileup():
     L.vlr_fragpileup_result.argtypes = [C.c_void_p, C.POINTER(abi.FragPileupCounts)]
     L.vlr_fragpileup_read.restype = C.c_int
     L.vlr_fragpileup_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+    L.vlr_fragpileup_open_realign.restype = C.c_int
+    L.vlr_fragpileup_open_realign.argtypes = L.vlr_fragpileup_open.argtypes[:-1] + [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int64,
+                                                                                    C.POINTER(C.c_void_p)]
+    L.vlr_fragpileup_realign_result.restype = C.c_int
+    L.vlr_fragpileup_realign_result.argtypes = [C.c_void_p, C.POINTER(abi.FragPileupRealignCounts)]
+    L.vlr_fragpileup_read_realigned.restype = C.c_int
+    L.vlr_fragpileup_read_realigned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.vlr_fragpileup_close.restype = None
     L.vlr_fragpileup_close.argtypes = [C.c_void_p]
     return L

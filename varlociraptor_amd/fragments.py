@@ -24,7 +24,19 @@ MAPQ adjustment (a sequential ln_sum_exp in observation order).  A locus with mo
 observations carry more alt loci than that, comes back flagged and is finished with the restatement on the library's tables, as are
 MNVs longer than basecalls.MAX_LEN.
 
-NOT mirrored (callers must know): realignment of indel-bearing reads and `alt_variants` (with realign_indel_reads=True such
+Realignment of indel-bearing reads (snv.rs:72-86, mnv.rs:83, Realigner::allele_support, realignment/mod.rs:161-424): with a
+RealignSpec a record that encloses the locus and carries an I or D operation is realigned against the ref and the alt allele window
+(`realign_evidence`, `realigned_hit`): candidate region (mod.rs:58-153) on [start, start + len), ref allele window = its ref interval,
+alt allele window = readwindows.substitution_locus, edit distance / band / pair HMM of the spec's mode, realign.normalize_support;
+strand = the record's when the supports differ, else none; no read position, no third-allele evidence.  device="cpu" scores the windows
+with the CPU restatement of the pair HMMs under oracle/, a device number with the kernels (vlr_fragpileup_open_realign in one pass over
+the BAM; loci finished on the host through realign.best_hits / prob_related*).  NOT mirrored there: the read-inferred third allele
+(mod.rs:317-348: needs the Myers traceback of the `bio` crate, which the reference does not vendor), `alt_variants`
+(--atomic-candidate-variants stays required, so an MNV is realigned only for an indel operation), `homopolymer_indel_len`.  Refused,
+with the record's ordinal: a CIGAR that begins with N (read_pos fails) and a record that needs realignment and carries an SI:Z tag
+(strand information over an interval, mod.rs:381-387).
+
+NOT mirrored (callers must know): `alt_variants`; without a RealignSpec the realignment (with realign_indel_reads=True such
 observations come back flagged NEEDS_REALIGN and `observations` raises), `max_depth` subsampling (the `rand` crate's StdRng),
 `report_fragment_ids` (None), indel / SV / breakend candidates with their insert-size terms, haplotype blocks, methylation.
 `preprocess_variants` is the command `python -m varlociraptor_amd preprocess variants`; it says what it does not do as errors.
@@ -39,10 +51,13 @@ import numpy as np
 
 from . import abi, basecalls
 from .basecalls import Hit, Locus, Tables
+from .engine import EngineError   # (a reference without its .fai index, a window the kernels refuse: what the command reports)
 from .readwindows import BamRecord, read_bam, read_fasta
 
 NEEDS_REALIGN = basecalls.NEEDS_REALIGN
 INVALID_RO = abi.FRAGPILEUP_OBS_INVALID_RO
+REALIGN_STRAND_INFO = abi.FRAGPILEUP_OBS_REALIGN_STRAND_INFO
+MAX_INDEL_WINDOW = abi.INDELPILEUP_MAX_WINDOW   # cli.rs:877
 ORIENT_INVALID = 255
 RO_VALUES = {b"F1R2": abi.FRAG_F1R2, b"F2R1": abi.FRAG_F2R1, b"F1F2": abi.FRAG_F1F2, b"F2F1": abi.FRAG_F2F1, b"R1R2": abi.FRAG_R1R2,
              b"R2R1": abi.FRAG_R2R1, b"R1F2": abi.FRAG_R1F2, b"R2F1": abi.FRAG_R2F1, b"None": abi.FRAG_ORIENT_NONE}
@@ -58,7 +73,32 @@ class FragPileupError(ValueError):
 
 
 class NeedsRealign(FragPileupError):
-    """a read the reference would realign (realign_indel_reads=True): that realignment is not built"""
+    """a read the reference would realign (realign_indel_reads=True) and no RealignSpec to realign it with"""
+
+
+class LeadingRefSkip(FragPileupError):
+    """rust-htslib's read_pos fails on a CIGAR that begins with a reference skip"""
+
+
+class RealignStrandInfo(FragPileupError):
+    """a record that needs realignment carries an SI:Z tag: strand information over an interval (mod.rs:381-387) is not built"""
+
+
+@dataclass
+class RealignSpec:
+    """how indel-bearing reads are realigned: --indel-window, --pairhmm-mode, gap and homopolymer parameters (realign.GapParams /
+    HopParams; None = the defaults, as for an alignment-properties JSON without them)"""
+    window: int = 64
+    mode: str = "exact"
+    gap: Optional[object] = None
+    hop: Optional[object] = None
+
+    def __post_init__(self):
+        from .readwindows import MODES
+        if not 1 <= int(self.window) <= MAX_INDEL_WINDOW:
+            raise ValueError("indel window %d outside 1 .. %d" % (self.window, MAX_INDEL_WINDOW))
+        if self.mode not in MODES:
+            raise ValueError("mode must be one of %s" % ", ".join(MODES))
 
 
 @dataclass
@@ -226,10 +266,14 @@ def is_member(rec: BamRecord, loc: Locus, window: int) -> bool:
     return basecalls.is_valid_record(rec.flag) and rec.ref_id == loc.ref_id and rec.pos >= 0 and max(loc.start - window, 0) <= rec.pos < loc.end
 
 
-def _support(rec: BamRecord, loc: Locus, li: int, ordinal: int, t: Tables, realign_indel_reads: bool) -> Optional[Hit]:
-    """allele_support_per_read; what the reference raises comes back as the hit's status"""
+def _support(rec: BamRecord, loc: Locus, li: int, ordinal: int, t: Tables, realign_indel_reads: bool, realigned: Optional[Dict] = None) -> Optional[Hit]:
+    """allele_support_per_read; what the reference raises comes back as the hit's status.  `realigned`: {(ordinal, locus): Hit} of the
+    records that were realigned"""
     try:
-        return basecalls.allele_support(rec, loc, li, ordinal, t, realign_indel_reads)
+        h = basecalls.allele_support(rec, loc, li, ordinal, t, realign_indel_reads)
+        if h is not None and h.status & NEEDS_REALIGN and realigned is not None:
+            return realigned[(ordinal, li)]
+        return h
     except basecalls.ReadPosOutOfBounds:
         st = abi.BASEPILEUP_HIT_READ_POS_OUT_OF_BOUNDS
     except basecalls.InvalidStrandInfo:
@@ -240,7 +284,7 @@ def _support(rec: BamRecord, loc: Locus, li: int, ordinal: int, t: Tables, reali
 
 
 def fragment_observation(left: Tuple[int, BamRecord], right: Optional[Tuple[int, BamRecord]], loc: Locus, li: int, max_mapq: int, t: Tables,
-                         realign_indel_reads: bool = False) -> Optional[FragObs]:
+                         realign_indel_reads: bool = False, realigned: Optional[Dict] = None) -> Optional[FragObs]:
     """mod.rs:352-384 and evidence_to_observation for one candidate"""
     lo, lr = left
     if right is not None:
@@ -250,8 +294,8 @@ def fragment_observation(left: Tuple[int, BamRecord], right: Optional[Tuple[int,
             return None
     elif not basecalls.enclosing(lr, loc):
         return None
-    hl = _support(lr, loc, li, lo, t, realign_indel_reads)
-    hr = _support(right[1], loc, li, right[0], t, realign_indel_reads) if right is not None else None
+    hl = _support(lr, loc, li, lo, t, realign_indel_reads, realigned)
+    hr = _support(right[1], loc, li, right[0], t, realign_indel_reads, realigned) if right is not None else None
     if hl is None and hr is None:
         return None
     h = basecalls.merge(hl, hr) if hl is not None and hr is not None else (hl if hl is not None else hr)
@@ -278,7 +322,7 @@ def fragment_observation(left: Tuple[int, BamRecord], right: Optional[Tuple[int,
 
 
 def locus_observations(members: Sequence[Tuple[int, BamRecord]], loc: Locus, li: int, max_mapq: int, t: Tables = basecalls.TABLES,
-                       realign_indel_reads: bool = False) -> List[FragObs]:
+                       realign_indel_reads: bool = False, realigned: Optional[Dict] = None) -> List[FragObs]:
     """the observations of one locus from its members (ordinal, record) in file order, in the byte order of the names"""
     cand: Dict[bytes, List] = {}
     for o, rec in members:
@@ -293,7 +337,7 @@ def locus_observations(members: Sequence[Tuple[int, BamRecord]], loc: Locus, li:
         c[1] = (o, rec)
     out = []
     for name in sorted(cand):
-        ob = fragment_observation(cand[name][0], cand[name][1], loc, li, max_mapq, t, realign_indel_reads)
+        ob = fragment_observation(cand[name][0], cand[name][1], loc, li, max_mapq, t, realign_indel_reads, realigned)
         if ob is not None:
             out.append(ob)
     return out
@@ -311,11 +355,136 @@ class Restated:
     max_read_len: int = 0
     n_rejected: int = 0
     bad_records: List[int] = field(default_factory=list)
+    evidences: List["RealignEvidence"] = field(default_factory=list)   # with a RealignSpec: the realigned evidences, record-major
+
+
+# ---------------------------------------------------------------------------------------------- realignment of indel-bearing reads
+@dataclass
+class RealignEvidence:
+    """one (record, locus) pair that is realigned: what csrc/vlr_fragpileup.h `realign_evidence` computes, and its scores"""
+    locus: int
+    ev: "object"                     # readwindows.Evidence: status 0 / NO_OVERLAP / LEADING_REFSKIP / abi.INDELPILEUP_HIT_STRAND_INFO
+    alt_allele: bytes                # the alt allele window (empty with a status)
+    ln_ref: float = -math.inf        # raw scores and edit distances, as in a vlr_indelpileup_hit
+    ln_alt: float = -math.inf
+    dist_ref: int = -1
+    dist_alt: int = -1
+
+    def key(self):
+        return (self.locus,) + self.ev.key()
+
+
+def realign_evidence(rec: BamRecord, loc: Locus, li: int, ordinal: int, ref_seq: bytes, window: int) -> RealignEvidence:
+    """The windows of a record that encloses `loc` and carries an I or D operation (`ref_seq`: its contig, upper case)."""
+    from . import readwindows as rw
+    from . import realign
+    flag = rec.flag & (0x1 | 0x10 | 0x40)
+
+    def refused(status):
+        return RealignEvidence(li, rw.Evidence(ordinal, status, (0, 0), (0, 0), b"", b"", b"", flag, rec.mapq), b"")
+    try:
+        reg = rw.candidate_region(rec, loc.start, loc.end, len(ref_seq), window)
+    except ValueError:
+        return refused(rw.LEADING_REFSKIP)
+    if basecalls.aux_tag_strand_info(rec) is not None:
+        return refused(abi.INDELPILEUP_HIT_STRAND_INFO)
+    ro, re_ = reg.read_interval
+    if not reg.overlap or re_ - ro < 1:
+        return refused(rw.NO_OVERLAP)
+    rb, re2 = reg.ref_interval
+    rb = min(rb, re2)
+    alt = rw.substitution_locus(ref_seq, loc.start, loc.ref, loc.alt, window).alt_allele
+    return RealignEvidence(li, rw.Evidence(ordinal, 0, (ro, re_), (rb, re2), rec.seq[ro:re_].upper(), bytes(rec.qual[ro:re_]),
+                                           realign.ref_allele(ref_seq, rb, re2).upper(), flag, rec.mapq), alt)
+
+
+def evidence_pair_batch(evs: Sequence[RealignEvidence]):
+    """pair 2e = (ref allele window, read window), pair 2e + 1 = (alt allele window, read window), bands unset"""
+    from .realign import PairBatch
+    pb = PairBatch()
+    for e in evs:
+        pb.add(e.ev.ref_allele, e.ev.read_window, e.ev.quals, -1)
+        pb.add(e.alt_allele, e.ev.read_window, e.ev.quals, -1)
+    return pb
+
+
+def score_pairs(pb, spec: RealignSpec, device="cpu"):
+    """(edit distances, ln P) of every pair of a realign.PairBatch in the spec's mode; sets the bands as the reference does (distance + 4,
+    -1 without a hit, none in fast mode).  device="cpu": oracle/'s restatement of the pair HMMs; a device number: the kernels."""
+    from . import realign
+    gap = spec.gap or realign.GapParams()
+    n = len(pb)
+    if n == 0:
+        return np.zeros(0, np.int32), np.zeros(0)
+    if device != "cpu":
+        dist, _, _ = realign.best_hits(pb, int(device))
+        if spec.mode == "fast":
+            return dist, realign.prob_best_path(pb, gap, int(device))
+        pb.band = [int(x) + realign.EDIT_BAND if x >= 0 else -1 for x in dist]
+        if spec.mode == "homopolymer":
+            return dist, realign.prob_related_homopolymer(pb, gap, spec.hop or realign.HopParams(), int(device))
+        return dist, realign.prob_related(pb, gap, int(device))
+    from oracle import oracle      # (the repository's CPU restatement of the pair HMMs; built on first use)
+    oracle.build()
+    g = [gap.prob_insertion_artifact, gap.prob_deletion_artifact, gap.prob_insertion_extend_artifact, gap.prob_deletion_extend_artifact]
+    dist, lnp = np.full(n, -1, np.int32), np.full(n, -math.inf)
+    for k in range(n):
+        x, y, q = pb.x[k], pb.y[k], pb.q[k]
+        if not x or not y:
+            continue
+        dist[k] = oracle.edit_distance(x, y)[0]
+        if spec.mode == "fast":
+            lnp[k] = oracle.pathhmm_best(x, y, q, g)
+            continue
+        pb.band[k] = int(dist[k]) + realign.EDIT_BAND if dist[k] >= 0 else -1
+        if spec.mode == "homopolymer":
+            lnp[k] = oracle.homopoly_prob_related(x, y, q, g, (spec.hop or realign.HopParams()).as_list(), pb.band[k])
+        else:
+            lnp[k] = oracle.pairhmm_prob_related(x, y, q, g, pb.band[k])
+    return dist, lnp
+
+
+def realigned_hit(e: RealignEvidence, rec: BamRecord) -> Hit:
+    """the member support of a realigned evidence (csrc/vlr_fragpileup.h `apply_realigned`)"""
+    from . import readwindows as rw
+    from . import realign
+    o = e.ev.record
+    if e.ev.status & rw.LEADING_REFSKIP:
+        return Hit(e.locus, o, 0.0, 0.0, abi.STRAND_NONE, None, 0, rec.mapq, e.ev.flag, abi.BASEPILEUP_HIT_LEADING_REFSKIP, (o,))
+    if e.ev.status & abi.INDELPILEUP_HIT_STRAND_INFO:
+        return Hit(e.locus, o, 0.0, 0.0, abi.STRAND_NONE, None, 0, rec.mapq, e.ev.flag, REALIGN_STRAND_INFO, (o,))
+    pr, pa = realign.normalize_support(e.ln_ref, e.ln_alt)     # (no overlap: ln 0 twice -> ln 0.5 twice, mod.rs:186-199)
+    strand = abi.STRAND_NONE if pr == pa else (abi.STRAND_REVERSE if rec.flag & 0x10 else abi.STRAND_FORWARD)
+    return Hit(e.locus, o, pr, pa, strand, None, 0, rec.mapq, e.ev.flag, 0, (o,))
+
+
+def realign_members(good: Sequence[Tuple[int, BamRecord]], loci: Sequence[Locus], which: Sequence[int], props: Props, spec: RealignSpec, ref_seqs: Dict[int, bytes],
+                    device="cpu"):
+    """(evidences record-major, loci ascending within a record; {(ordinal, locus): Hit}) of the members of the loci `which` (ascending)
+    that need realignment"""
+    evs: List[RealignEvidence] = []
+    recs: List[BamRecord] = []
+    for o, rec in good:
+        if not basecalls.contains_indel_op(rec):
+            continue
+        for li in which:
+            loc = loci[li]
+            if is_member(rec, loc, props.window) and basecalls.enclosing(rec, loc):
+                evs.append(realign_evidence(rec, loc, li, o, ref_seqs[loc.ref_id], spec.window))
+                recs.append(rec)
+    dist, lnp = score_pairs(evidence_pair_batch(evs), spec, device)
+    hits = {}
+    for k, (e, rec) in enumerate(zip(evs, recs)):
+        e.ln_ref, e.ln_alt, e.dist_ref, e.dist_alt = float(lnp[2 * k]), float(lnp[2 * k + 1]), int(dist[2 * k]), int(dist[2 * k + 1])
+        hits[(e.ev.record, e.locus)] = realigned_hit(e, rec)
+    return evs, hits
 
 
 def restate(records: Sequence[BamRecord], loci: Sequence[Locus], props: Props, t: Tables = basecalls.TABLES, realign_indel_reads: bool = False,
-            first_ordinal: int = 0, only: Optional[Sequence[int]] = None) -> Restated:
-    """The observations of every locus (`only`: of these loci) from `records` in file order."""
+            first_ordinal: int = 0, only: Optional[Sequence[int]] = None, realign: Optional[RealignSpec] = None, ref_seqs: Optional[Dict[int, bytes]] = None,
+            device="cpu") -> Restated:
+    """The observations of every locus (`only`: of these loci) from `records` in file order.  `realign`: indel-bearing reads are
+    realigned (realign_indel_reads is implied) against `ref_seqs` {ref_id: contig, upper case}, scored on `device`."""
     out = Restated([[] for _ in loci], [0] * len(loci), len(records), props.max_read_len)
     good = []
     for k, rec in enumerate(records):
@@ -325,11 +494,18 @@ def restate(records: Sequence[BamRecord], loci: Sequence[Locus], props: Props, t
             out.bad_records.append(first_ordinal + k)
         elif rec.ref_id >= 0 and rec.pos >= 0:
             good.append((first_ordinal + k, rec))
-    for li in (range(len(loci)) if only is None else only):
+    which = list(range(len(loci)) if only is None else only)
+    realigned = None
+    if realign is not None:
+        if ref_seqs is None:
+            raise ValueError("realignment needs the contigs of the loci (ref_seqs)")
+        realign_indel_reads = True
+        out.evidences, realigned = realign_members(good, loci, sorted(which), props, realign, ref_seqs, device)
+    for li in which:
         loc = loci[li]
         members = [(o, r) for o, r in good if is_member(r, loc, props.window)]
         out.n_members[li] = len(members)
-        out.per_locus[li] = locus_observations(members, loc, li, props.max_mapq, t, realign_indel_reads)
+        out.per_locus[li] = locus_observations(members, loc, li, props.max_mapq, t, realign_indel_reads, realigned)
     return out
 
 
@@ -339,10 +515,15 @@ def _bases(loci, attr):
 
 
 def device_observations(bams, loci: Sequence[Locus], props: Props, device: int = 0, realign_indel_reads: bool = False, member_capacity: Optional[int] = None,
-                        name_capacity: Optional[int] = None, window_bytes: int = 0, retry: bool = True, key_capacity: Optional[int] = None):
+                        name_capacity: Optional[int] = None, window_bytes: int = 0, retry: bool = True, key_capacity: Optional[int] = None,
+                        realign: Optional[RealignSpec] = None, fasta: Optional[str] = None, evidence_capacity: Optional[int] = None, pair_byte_limit: int = 0,
+                        evidences: bool = False):
     """(observations as abi.FRAGPILEUP_OBS_DTYPE, locus records as abi.FRAGPILEUP_LOCUS_DTYPE, abi.FragPileupCounts) from the kernels.
     `bams`: a path or several (one record stream: a pair may straddle two files); `loci` sorted by (ref_id, start), MNVs of at most
-    basecalls.MAX_LEN bases.  An overflow of a capacity is retried once with the needed ones unless retry=False."""
+    basecalls.MAX_LEN bases.  An overflow of a capacity is retried once with the needed ones unless retry=False.
+    `realign` (with `fasta`): indel-bearing reads are realigned in the same pass (vlr_fragpileup_open_realign; realign_indel_reads is
+    implied); evidences=True adds (the realigned evidences as abi.INDELPILEUP_HIT_DTYPE, record-major; abi.FragPileupRealignCounts) to
+    the result."""
     import ctypes as C
     from . import engine
     L = engine.bind_fragpileup()
@@ -357,11 +538,23 @@ def device_observations(bams, loci: Sequence[Locus], props: Props, device: int =
     mcap = int(member_capacity) if member_capacity is not None else max(1 << 16, 256 * n)
     ncap = int(name_capacity) if name_capacity is not None else max(1 << 20, 4096 * n)
     kcap = int(key_capacity) if key_capacity is not None else max(1 << 16, 256 * n)
+    ecap = int(evidence_capacity) if evidence_capacity is not None else 1 << 14
+    if realign is not None:
+        from . import realign as rl
+        from .readwindows import MODES
+        if fasta is None:
+            raise ValueError("realignment needs the reference (fasta)")
+        gap = (realign.gap or rl.GapParams()).as_array()
+        hop = (realign.hop or rl.HopParams()).as_array() if realign.mode == "homopolymer" else None
     while True:
         h = C.c_void_p()
-        engine._check(L.vlr_fragpileup_open(int(device), n, ref_id.ctypes.data, start.ctypes.data, length.ctypes.data, kind.ctypes.data, refb.ctypes.data,
-                                            altb.ctypes.data, int(bool(realign_indel_reads)), int(props.window), int(props.max_mapq), int(props.max_read_len),
-                                            mcap, ncap, kcap, int(window_bytes), C.byref(h)))
+        head = (int(device), n, ref_id.ctypes.data, start.ctypes.data, length.ctypes.data, kind.ctypes.data, refb.ctypes.data, altb.ctypes.data)
+        caps = (int(props.window), int(props.max_mapq), int(props.max_read_len), mcap, ncap, kcap, int(window_bytes))
+        if realign is None:
+            engine._check(L.vlr_fragpileup_open(*head, int(bool(realign_indel_reads)), *caps, C.byref(h)))
+        else:
+            engine._check(L.vlr_fragpileup_open_realign(*head, 1, *caps, fasta.encode(), int(realign.window), MODES[realign.mode], gap, hop, ecap, int(pair_byte_limit),
+                                                        C.byref(h)))
         try:
             for b in bams:
                 engine._check(L.vlr_fragpileup_add_bam(h, b.encode()))
@@ -369,14 +562,24 @@ def device_observations(bams, loci: Sequence[Locus], props: Props, device: int =
             engine._check(L.vlr_fragpileup_result(h, C.byref(res)))
             if res.status & abi.FRAGPILEUP_GUARD_DAMAGED:
                 raise FragPileupError("the guard words behind a buffer of the fragment session changed")
-            if res.status & abi.FRAGPILEUP_ANY_OVERFLOW and retry:
+            rres = abi.FragPileupRealignCounts()
+            if realign is not None:
+                engine._check(L.vlr_fragpileup_realign_result(h, C.byref(rres)))
+            over = abi.FRAGPILEUP_ANY_OVERFLOW | abi.FRAGPILEUP_EVIDENCE_OVERFLOW
+            if res.status & over and retry:
                 mcap, ncap, kcap = max(mcap, int(res.needed_members)), max(ncap, int(res.needed_name_bytes)), max(kcap, int(res.needed_keys))
+                ecap = max(ecap, int(rres.needed_evidences))
                 continue
             obs = np.zeros(int(res.n_obs), abi.FRAGPILEUP_OBS_DTYPE)
             loc = np.zeros(n, abi.FRAGPILEUP_LOCUS_DTYPE)
-            if not res.status & abi.FRAGPILEUP_ANY_OVERFLOW:
+            if not res.status & over:
                 engine._check(L.vlr_fragpileup_read(h, obs.ctypes.data, len(obs), loc.ctypes.data, n))
-            return obs, loc, res
+            if not evidences:
+                return obs, loc, res
+            ev = np.zeros(int(rres.n_evidences), abi.INDELPILEUP_HIT_DTYPE)
+            if realign is not None and len(ev):
+                engine._check(L.vlr_fragpileup_read_realigned(h, ev.ctypes.data, len(ev)))
+            return obs, loc, res, ev, rres
         finally:
             L.vlr_fragpileup_close(h)
 
@@ -399,12 +602,15 @@ def raise_for_status(o: FragObs):
     if o.status & abi.BASEPILEUP_HIT_INVALID_STRAND_INFO:
         raise basecalls.InvalidStrandInfo("invalid strand information in the SI tag of record %d" % o.left)
     if o.status & abi.BASEPILEUP_HIT_LEADING_REFSKIP:
-        raise ValueError("leading reference skip in record %d" % o.left)
+        raise LeadingRefSkip("leading reference skip in record %d%s" % (o.left, "" if o.right is None else " or its mate, record %d" % o.right))
+    if o.status & REALIGN_STRAND_INFO:
+        raise RealignStrandInfo("record %d%s carries an insertion or deletion and an SI:Z tag: REALIGN_STRAND_INFO (strand information over the realigned "
+                                "interval is not built)" % (o.left, "" if o.right is None else " or its mate, record %d," % o.right))
     if o.status & INVALID_RO:
         raise InvalidReadOrientationInfo("invalid read orientation in the RO tag of record %d or its mate" % o.left)
     if o.status & NEEDS_REALIGN:
         raise NeedsRealign("record %d (or its mate) carries an insertion or deletion and would be realigned by the reference: NEEDS_REALIGN "
-                              "(realignment against SNV / MNV candidates is not built)" % o.left)
+                              "(give a RealignSpec / --realign-indel-reads to realign it)" % o.left)
 
 
 # ---------------------------------------------------------------------------------------------- pileups
@@ -487,9 +693,10 @@ def table_of(obs: Sequence[FragObs], props: Props, t: Tables, omit_mapq_adjustme
 
 
 def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, bytes]], props, device=0, omit_mapq_adjustment: bool = False,
-                 realign_indel_reads: bool = False, window_bytes: int = 0) -> List[ObsTable]:
+                 realign_indel_reads: bool = False, window_bytes: int = 0, realign: Optional[RealignSpec] = None) -> List[ObsTable]:
     """Per candidate (contig, 0-based position, REF, ALT), in the order given, its processed pileup.  device="cpu": the restatement; a
-    device number: the kernels, finished as the module header says."""
+    device number: the kernels, finished as the module header says.  `realign`: indel-bearing reads are realigned (module header);
+    realign_indel_reads=True without it raises NeedsRealign for such a read."""
     from . import alignprops
     props = props_of(props)
     bams = [bam] if isinstance(bam, str) else list(bam)
@@ -501,6 +708,7 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
         if c not in tid or c not in seqs:
             raise ValueError("contig %s is not in the BAM header and the reference" % c)
         loci.append(basecalls.locus(seqs[c], tid[c], int(pos), ref, alt))
+    ref_seqs = {tid[c]: seqs[c].upper() for c in set(c for c, _, _, _ in candidates)} if realign is not None else None
     order = sorted(range(len(loci)), key=lambda k: (loci[k].ref_id, loci[k].start))
     recs: Optional[List[BamRecord]] = None
 
@@ -512,7 +720,7 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
     out: List[Optional[ObsTable]] = [None] * len(loci)
     if device == "cpu":
         t = basecalls.TABLES
-        rs = restate(records(), [loci[k] for k in order], props, t, realign_indel_reads)
+        rs = restate(records(), [loci[k] for k in order], props, t, realign_indel_reads, realign=realign, ref_seqs=ref_seqs)
         if rs.bad_records:
             raise FragPileupError("%s: record %d is malformed" % (bams[0], rs.bad_records[0]))
         for j, k in enumerate(order):
@@ -520,7 +728,7 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
         return out
     t = basecalls.library_tables()
     short = [k for k in order if len(loci[k].ref) <= basecalls.MAX_LEN]
-    arr, lrec, res = device_observations(bams, [loci[k] for k in short], props, int(device), realign_indel_reads, window_bytes=window_bytes)
+    arr, lrec, res = device_observations(bams, [loci[k] for k in short], props, int(device), realign_indel_reads, window_bytes=window_bytes, realign=realign, fasta=fasta)
     if res.status & abi.FRAGPILEUP_BAD_RECORD:
         raise FragPileupError("%s: record %d is malformed" % (bams[0], int(res.first_bad_record)))
     deep = abi.FRAGPILEUP_LOCUS_TOO_MANY_MEMBERS | abi.FRAGPILEUP_LOCUS_TOO_MANY_ALT_LOCI
@@ -533,7 +741,7 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
         mj = int(lrec[j]["major_read_position"])
         out[k] = table_of(obs, props, t, omit_mapq_adjustment, None if mj == abi.BASEPILEUP_NO_READ_POSITION else mj)
     if host:
-        rs = restate(records(), [loci[k] for k in host], props, t, realign_indel_reads)
+        rs = restate(records(), [loci[k] for k in host], props, t, realign_indel_reads, realign=realign, ref_seqs=ref_seqs, device=int(device))
         for j, k in enumerate(host):
             out[k] = table_of(rs.per_locus[j], props, t, omit_mapq_adjustment)
     return out
@@ -593,6 +801,16 @@ class PreprocessError(ValueError):
     """something `preprocess variants` does not do, or an input it cannot use; the message names the record or the flag"""
 
 
+def gap_hop_of(p):
+    """(realign.GapParams, realign.HopParams) of alignment properties (the dict of a JSON or alignprops.AlignmentProperties): the
+    defaults where the JSON has none"""
+    if isinstance(p, dict):
+        import json
+        from . import alignprops
+        p = alignprops.load(json.dumps(p))
+    return p.gap_params, p.hop_params
+
+
 def read_candidates(path: str) -> List[Tuple[str, int, str, str, str]]:
     """(CHROM, 1-based POS, ID, REF, ALT) per ALT allele of a candidate VCF (text) or BCF, in file order"""
     out = []
@@ -616,9 +834,10 @@ def read_candidates(path: str) -> List[Tuple[str, int, str, str, str]]:
 
 def preprocess_variants(reference: str, candidates: str, bam: str, output: str, alignment_properties: Optional[str] = None, device=0,
                         atomic_candidate_variants: bool = False, omit_mapq_adjustment: bool = False, max_depth: int = 200,
-                        score_indel_reads_from_alignment: bool = False, warn=None) -> int:
+                        score_indel_reads_from_alignment: bool = False, warn=None, realign: Optional[RealignSpec] = None) -> int:
     """`preprocess variants` for SNV / MNV candidates of one sample: the observation BCF `output` (format v15) that `call variants`
-    reads.  Returns the number of records written."""
+    reads.  Returns the number of records written.  `realign` (--realign-indel-reads): indel-bearing reads over a candidate are
+    realigned as the reference does by default; its gap / hop parameters default to those of the alignment properties."""
     import json
     from . import ingest
     if not atomic_candidate_variants:
@@ -631,16 +850,21 @@ def preprocess_variants(reference: str, candidates: str, bam: str, output: str, 
         if sym or len(ref) != len(alt) or not ref:
             raise PreprocessError("candidate %s:%d %s>%s is not an SNV or MNV: indel, structural and breakend candidates are not built" % (chrom, pos, ref, alt))
         cands.append((chrom, pos - 1, ref.encode(), alt.encode()))
+    if realign is not None and score_indel_reads_from_alignment:
+        raise PreprocessError("--realign-indel-reads and --score-indel-reads-from-alignment exclude each other")
     if alignment_properties is not None:
-        props = props_of(json.load(open(alignment_properties)))
+        pj = json.load(open(alignment_properties))
     else:
         from . import alignprops
-        props = props_of(alignprops.estimate(reference, [bam], None, device)[0])
+        pj = alignprops.estimate(reference, [bam], None, device)[0]
+    props = props_of(pj)
+    if realign is not None and realign.gap is None and realign.hop is None:
+        realign = RealignSpec(realign.window, realign.mode, *gap_hop_of(pj))
     try:
         tabs = observations(bam, reference, cands, props, device=device, omit_mapq_adjustment=omit_mapq_adjustment,
-                            realign_indel_reads=not score_indel_reads_from_alignment)
+                            realign_indel_reads=not score_indel_reads_from_alignment, realign=realign)
     except NeedsRealign as e:
-        raise PreprocessError(str(e) + "; --score-indel-reads-from-alignment scores such reads as they are aligned") from e
+        raise PreprocessError(str(e) + "; --score-indel-reads-from-alignment scores such reads as they are aligned, --realign-indel-reads realigns them") from e
     deep = sum(1 for t in tabs if len(t) > max_depth)
     if deep and warn is not None:
         warn("%d of %d loci have more than --max-depth %d observations; they are processed whole (the reference's subsampling is not built)" % (deep, len(tabs), max_depth))

@@ -242,6 +242,21 @@ def indel_locus(ref_seq: bytes, pos: int, ref: bytes, alt: bytes, window: int = 
                       realign.replacement_allele(ref_seq, max(0, pos - ref_window), min(pos + len(ref) + ref_window, n), pos, len(ref), alt))
 
 
+def substitution_locus(ref_seq: bytes, pos: int, ref: bytes, alt: bytes, window: int = 64) -> IndelLocus:
+    """Locus and alt allele window of the SNV / MNV candidate `ref` > `alt` (equal lengths) at 0-based `pos`, for the realignment of
+    indel-bearing reads (snv.rs:157-178, mnv.rs:224-233: Snv / MnvEmissionParams): the contig over [max(0, pos - rw), min(pos + len + rw,
+    n)), rw = int(window * 1.5), with the locus bytes replaced — realign.replacement_allele with len(alt) == len(ref)."""
+    from . import realign
+    ref, alt = bytes(ref).upper(), bytes(alt).upper()
+    if len(ref) != len(alt) or not ref:
+        raise ValueError("REF and ALT of different lengths are not an SNV or MNV (indel_locus handles them)")
+    if ref_seq[pos:pos + len(ref)].upper() != ref:
+        raise ValueError("REF allele does not match the reference sequence at position %d" % (pos + 1))
+    rw_, n = int(window * 1.5), len(ref_seq)
+    return IndelLocus("substitution", pos, pos + len(ref), 0,
+                      realign.replacement_allele(ref_seq, max(0, pos - rw_), min(pos + len(ref) + rw_, n), pos, len(ref), alt))
+
+
 def evidence_windows(records: List[BamRecord], ref_seq: bytes, locus: IndelLocus, window: int = 64) -> list:
     """(record, read window, qualities, ref allele window) of every record that is valid evidence for the locus (mapped, primary,
     overlapping it with its soft clips, with a candidate region)."""
