@@ -1,5 +1,6 @@
 """Device front door (csrc/vlr_inflate.hip, csrc/vlr_decode.hip behind vlr_obs_reader_open_device / vlr_bgzf_inflate, include/vlr.h):
-the BGZF inflate kernel against zlib on every DEFLATE block type, and the device reader against the host reader (csrc/vlr_ingest.cpp,
+the BGZF inflate kernel against zlib on every DEFLATE block type (as zlib's compressor writes them; the forms it never emits — long
+codes, every overlap, far matches, rare dynamic headers, refusals by reason — are in tests/test_gpu_inflate_streams.py), and the device reader against the host reader (csrc/vlr_ingest.cpp,
 itself held against the Python restatement and the reference's files in tests/test_ingest.py) — column by column, flag by flag,
 string by string; the device-resident batch evaluated by vlr_batch_run against the host batch through vlr_batch_run_host."""
 import os

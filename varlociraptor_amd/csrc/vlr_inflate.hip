@@ -57,6 +57,7 @@ constexpr bool kInflateBatchDefault = true;   // speculative batches (VLR_INFLAT
 // position is in HBM when a far match asks for it: kRing >= kFlush + 1286.
 constexpr uint32_t kRing = VLR_INFL_RING, kRingMask = kRing - 1, kFlush = 1024;   // flushed to HBM in 1 KiB pieces, each before the ring wraps onto it
 static_assert(kRing >= kFlush + 1286, "far matches read flushed bytes only");
+constexpr uint32_t kBadDistance = 1u, kBadSymbol = 2u, kBadOutput = 4u, kBadInput = 8u;   // the symbol loops' `bad`
 
 struct InflLds {
     uint8_t out[kRing];              // ring over the last kRing bytes of the inflated member, position shifted by (HBM destination & 15)
@@ -374,6 +375,9 @@ __global__ __launch_bounds__(64) void vlr_inflate_kernel(const uint8_t* __restri
         // (One loop exit — every early exit of a multi-exit loop costs the structurised control flow a flag test per iteration — and one
         // rare branch: the position is compared with `next_stop`, the nearer of the next flush point and the member's end; a corrupt
         // stream that runs past the end is caught there, before anything beyond the member's bytes could go to HBM.)
+        // `bad` has one bit per reason, and the reason reported is the one that can only have come first: a bad distance does not end
+        // the loop (what follows it may be garbage: a bad symbol, an overrun), a bad symbol and an overrun do.  (The INFL_ values
+        // themselves were OR-ed here once: a distance symbol without a code in the batch loop gave 6 | 5 = 7, an output overrun.)
         uint32_t bad = 0;
         bool done = false;
         uint32_t next_stop = flushed + kFlush + 512 < lim + 1 ? flushed + kFlush + 512 : lim + 1;
@@ -439,12 +443,12 @@ __global__ __launch_bounds__(64) void vlr_inflate_kernel(const uint8_t* __restri
                             }
                             n += dl;
                             const int dx = (int)((d >> 4) & 15u);
-                            if (dx == 15) { bad |= (uint32_t)INFL_BAD_DISTANCE; t = make_token(3, 1, 0, 1); }
+                            if (dx == 15) { bad |= kBadDistance; t = make_token(3, 1, 0, 1); }
                             else {
                                 const uint32_t dist = (d >> 8) + ((uint32_t)(v64 >> n) & ((1u << dx) - 1u));
                                 n += dx;
                                 t = make_token(1, (uint32_t)n, len, dist ? dist : 1u);
-                                if (dist == 0) bad |= (uint32_t)INFL_BAD_DISTANCE;
+                                if (dist == 0) bad |= kBadDistance;
                             }
                         } else t = make_token(kind, (uint32_t)n, kind == 0 ? (e >> 8) & 255u : 0u, 1u);
                     }
@@ -455,18 +459,18 @@ __global__ __launch_bounds__(64) void vlr_inflate_kernel(const uint8_t* __restri
                     } else if (kind == 1) {
                         const uint32_t len = (t >> 8) & 511u, dist = (t >> 17) + 1u;
                         const bool inside = dist <= pos - sh;
-                        bad |= inside ? 0u : (uint32_t)INFL_BAD_DISTANCE;
+                        bad |= inside ? 0u : kBadDistance;
                         copy_match(L, gbase, pos, dist, len, inside, lane);
                         pos += len;
                     } else {
                         done = true;   // 2: end of block
-                        bad |= kind == 3 ? (uint32_t)INFL_BAD_SYMBOL : 0u;
+                        bad |= kind == 3 ? kBadSymbol : 0u;
                     }
                     off += adv;
                     if (__builtin_expect(pos >= next_stop, 0)) {
-                        if (pos > lim) { bad |= (uint32_t)INFL_OUTPUT_OVERRUN << 8; done = true; }
+                        if (pos > lim) { bad |= kBadOutput; done = true; }
                         else if (bad) done = true;
-                        else if ((const uint8_t*)b.g + ((bp + off) >> 3) > in_end + 8) { bad |= (uint32_t)INFL_INPUT_OVERRUN << 8; done = true; }   // (a corrupt stream must not read far beyond its member: kInflateInputSlack)
+                        else if ((const uint8_t*)b.g + ((bp + off) >> 3) > in_end + 8) { bad |= kBadInput; done = true; }   // (a corrupt stream must not read far beyond its member: kInflateInputSlack)
                         else if (pos - flushed >= kFlush + 512) { const uint32_t to = pos & ~(kFlush - 1); flush_ring(L, gbase, flushed, to, lane); flushed = to; }
                         next_stop = flushed + kFlush + 512 < lim + 1 ? flushed + kFlush + 512 : lim + 1;
                     }
@@ -510,7 +514,7 @@ __global__ __launch_bounds__(64) void vlr_inflate_kernel(const uint8_t* __restri
                 const uint32_t dist = (d >> 8) + peek(b, dx);
                 drop(b, dx);
                 const bool inside = (dx != 15) & (dist <= pos - sh) & (dist != 0);
-                bad |= inside ? 0u : (uint32_t)INFL_BAD_DISTANCE;
+                bad |= inside ? 0u : kBadDistance;
                 refill(b, lane);
                 const uint32_t ev = L.lit[peek(b, kLitBits)];   // the next symbol's entry: in flight while the bytes are copied
                 copy_match(L, gbase, pos, dist, len, inside, lane);
@@ -518,19 +522,19 @@ __global__ __launch_bounds__(64) void vlr_inflate_kernel(const uint8_t* __restri
                 e = uni(ev);
             } else {
                 done = true;   // 2: end of block
-                bad |= kind == 3 ? (uint32_t)INFL_BAD_SYMBOL : 0u;
+                bad |= kind == 3 ? kBadSymbol : 0u;
             }
             if (__builtin_expect(pos >= next_stop, 0)) {
-                if (pos > lim) { bad |= (uint32_t)INFL_OUTPUT_OVERRUN << 8; done = true; }
+                if (pos > lim) { bad |= kBadOutput; done = true; }
                 else if (bad) done = true;
-                else if (bits_used_end(b) > in_end + 8) { bad |= (uint32_t)INFL_INPUT_OVERRUN << 8; done = true; }
+                else if (bits_used_end(b) > in_end + 8) { bad |= kBadInput; done = true; }
                 else if (pos - flushed >= kFlush + 512) { const uint32_t to = pos & ~(kFlush - 1); flush_ring(L, gbase, flushed, to, lane); flushed = to; }
                 next_stop = flushed + kFlush + 512 < lim + 1 ? flushed + kFlush + 512 : lim + 1;
             }
         } while (!done);
         }
-        if (pos > lim) bad |= (uint32_t)INFL_OUTPUT_OVERRUN << 8;
-        if (bad) err = (bad >> 8) ? (int)(bad >> 8) : (int)(bad & 0xffu);
+        if (pos > lim) bad |= kBadOutput;
+        if (bad) err = (bad & kBadDistance) ? INFL_BAD_DISTANCE : (bad & kBadSymbol) ? INFL_BAD_SYMBOL : (bad & kBadOutput) ? INFL_OUTPUT_OVERRUN : INFL_INPUT_OVERRUN;
         if (err == INFL_OK && bits_used_end(b) > in_end) err = INFL_INPUT_OVERRUN;
     }
     if (err == INFL_OK && pos != lim) err = INFL_SIZE_MISMATCH;
