@@ -70,8 +70,7 @@ def test_built_libraries_carry_the_id_of_the_current_sources():
     want = engine.source_id()
     paths = [engine.LIB_PATH] + [os.path.join(engine.MATRIX_DIR, "libvlr_%s.so" % n) for n in engine.MATRIX_LIBS]
     for path in paths:
-        L = ctypes.CDLL(path)
-        L.vlr_build_id.restype = ctypes.c_char_p
+        L = engine.bind(ctypes.CDLL(path))
         assert L.vlr_build_id().decode() == want, path
 
 

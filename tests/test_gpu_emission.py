@@ -21,8 +21,6 @@ def _device_text(count, vaf, lnprob, text_capacity=None):
     text = np.zeros(text_capacity, np.uint8)
     span = np.zeros((n, 2), np.uint32)
     unf = C.c_uint32(0)
-    L.vlr_selftest_afd_text.restype = C.c_int
-    L.vlr_selftest_afd_text.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32)]
     count = np.ascontiguousarray(count, np.int32)
     vaf = np.ascontiguousarray(vaf, np.float64)
     lnprob = np.ascontiguousarray(lnprob, np.float64)

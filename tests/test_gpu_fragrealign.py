@@ -25,7 +25,7 @@ K_THREADS = 256   # vlr_ip::kThreads
 
 
 def test_the_entry_point_is_exported():
-    assert engine.bind_fragpileup().vlr_fragpileup_open_realign is not None and engine.lib().vlr_abi_version() == 14
+    assert engine.lib().vlr_fragpileup_open_realign is not None and engine.lib().vlr_abi_version() == 14
 
 
 class Case:

@@ -1,6 +1,5 @@
 """Device build of the shared decision arithmetic: bit-identical to the host build of include/vlr_detmath.h (that is the
 premise of sharing it between kernel and oracle), and the kernel's own mantissa logarithm against libm."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -14,8 +13,6 @@ pytestmark = pytest.mark.gpu
 def _dev(which, a, b=None):
     from varlociraptor_amd import engine
     L = engine.lib()
-    L.vlr_selftest_math.restype = C.c_int
-    L.vlr_selftest_math.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     out = np.empty(len(a))
     rc = L.vlr_selftest_math(0, which, a.ctypes.data, b.ctypes.data if b is not None else None, out.ctypes.data, len(a))
     assert rc == 0, L.vlr_last_error()

@@ -89,12 +89,9 @@ def test_kernel_limits_and_nan():
 
 
 def _raw_bad_group():
-    import ctypes as C
     from varlociraptor_amd import engine
     L = engine.lib()
     v = np.array([0.5]); p = np.array([-1.0]); g = np.array([5], np.int32); lo = np.array([0.0]); hi = np.array([1.0]); out = np.zeros(2)
-    L.vlr_range_group_lse.restype = C.c_int
-    L.vlr_range_group_lse.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     rc = L.vlr_range_group_lse(0, 1, v.ctypes.data, p.ctypes.data, g.ctypes.data, 1, lo.ctypes.data, hi.ctypes.data, 2, out.ctypes.data)
     assert rc != 0
     raise engine.EngineError(rc, L.vlr_last_error().decode())

@@ -152,6 +152,156 @@ def declared_functions():
     return sorted(set(re.findall(r"\b(vlr_[a-z_0-9]+)\s*\(", text)))
 
 
+def declared_prototypes():
+    """name -> (return type, [parameter, ...]) as the header's text, comments stripped, of every function include/vlr.h declares"""
+    text = open(os.path.join(ROOT, "include", "vlr.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    out = {}
+    for ret, name, params in re.findall(r"(?m)^([A-Za-z_][\w \t\*]*?)\b(vlr_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text):
+        params = " ".join(params.split())
+        out[name] = (ret.strip(), [] if params == "void" else [p.strip() for p in params.split(",")])
+    return out
+
+
+def c_class(decl):
+    """pointer / i32 / i64 / float / double / void of a C parameter or return type, from its text alone"""
+    if "*" in decl or "[" in decl:
+        return "pointer"
+    words = set(re.findall(r"\w+", decl))
+    if words & {"int64_t", "uint64_t", "size_t"} or "long long" in decl:
+        return "i64"
+    for w in ("double", "float", "void"):
+        if w in words:
+            return w
+    assert words & {"int", "int32_t", "uint32_t", "unsigned"}, decl
+    return "i32"
+
+
+def ctypes_class(t):
+    if t is None:
+        return "void"
+    if issubclass(t, C._Pointer) or t in (C.c_void_p, C.c_char_p):
+        return "pointer"
+    if t in (C.c_double, C.c_float):
+        return "double" if t is C.c_double else "float"
+    assert issubclass(t, C._SimpleCData) and t._type_ in "iIlLqQ", t
+    return {4: "i32", 8: "i64"}[C.sizeof(t)]
+
+
+def test_signatures_match_the_header():
+    """abi.SIGNATURES, which engine.lib() binds the library with, against the prototypes of include/vlr.h: the same names, and for each
+    the same number of parameters, the same class of every parameter and the same class of return value.  The header is the reference."""
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_functions() and len(protos) >= 100   # the prototype parser missed none
+    assert set(abi.SIGNATURES) == set(protos)
+    assert not set(abi.INTERNAL_SIGNATURES) & set(protos)
+    for name, (ret, params) in protos.items():
+        restype, argtypes = abi.SIGNATURES[name]
+        assert len(argtypes) == len(params), name
+        for k, (t, p) in enumerate(zip(argtypes, params)):
+            assert ctypes_class(t) == c_class(p), "%s: parameter %d (%s)" % (name, k, p)
+        assert ctypes_class(restype) == c_class(ret), "%s returns %s" % (name, ret)
+    # the classifier itself, on the kinds of declaration the header has
+    assert [c_class(d) for d in ("const double gap[4]", "vlr_plan** out", "size_t bytes", "unsigned long long n", "uint32_t mode", "float x", "double alpha",
+                                 "void", "const char*")] == ["pointer", "pointer", "i64", "i64", "i32", "float", "double", "void", "pointer"]
+    assert [ctypes_class(t) for t in (C.c_size_t, C.c_ulonglong, C.c_uint32, C.c_int, C.POINTER(C.c_int), None)] == ["i64", "i64", "i32", "i32", "pointer", "void"]
+
+
+def test_signatures_are_bound_in_one_place():
+    """no module, test or tool sets the restype / argtypes of a vlr_* function: abi.py states them, engine.bind() applies them"""
+    import ast
+    import glob
+
+    def targets(t):
+        return [x for e in t.elts for x in targets(e)] if isinstance(t, (ast.Tuple, ast.List)) else [t]
+
+    found = []
+    for d in ("varlociraptor_amd", "tests", "tools"):
+        for path in sorted(glob.glob(os.path.join(ROOT, d, "*.py"))):
+            if d == "varlociraptor_amd" and os.path.basename(path) in ("abi.py", "engine.py"):
+                continue
+            for node in ast.walk(ast.parse(open(path).read())):
+                ts = node.targets if isinstance(node, ast.Assign) else [node.target] if isinstance(node, (ast.AugAssign, ast.AnnAssign)) else []
+                for t in (x for t in ts for x in targets(t)):
+                    if (isinstance(t, ast.Attribute) and t.attr in ("argtypes", "restype") and isinstance(t.value, ast.Attribute)
+                            and t.value.attr.startswith("vlr_")):
+                        found.append("%s:%d %s.%s" % (os.path.relpath(path, ROOT), node.lineno, t.value.attr, t.attr))
+    assert not found, found
+
+
+class _OverflowingPileups:
+    """Stands in for the library: every pileup session reports an overflow whose needed capacities are the ones it was opened with."""
+
+    def __init__(self, cap_args, status, needed):
+        self.cap_args, self.status, self.needed = cap_args, status, needed
+        self.opens = self.closes = 0
+
+    def __getattr__(self, name):
+        def open_(*args):
+            self.opens += 1
+            assert self.opens <= 8, "the wrapper keeps opening sessions"   # ends a runaway thread
+            self.caps = [args[k] for k in self.cap_args]
+            return 0
+
+        def result(h, out):
+            out._obj.status = self.status
+            for field, cap in zip(self.needed, self.caps):
+                setattr(out._obj, field, cap)
+            return 0
+
+        def close(h):
+            self.closes += 1
+
+        if name.endswith(("_open", "_open_realign")):
+            return open_
+        if name.endswith("pileup_result"):
+            return result
+        if name.endswith("_close"):
+            return close
+        return lambda *args: 0   # add_bam, read, realign_result
+
+
+def _pileup_wrappers():
+    from varlociraptor_amd import basecalls, fragments, readwindows
+    snv = basecalls.Locus(abi.BASEPILEUP_SNV, 0, 10, b"A", b"C")
+    deletion = readwindows.IndelLocus("deletion", 10, 12, -1, b"ACGT")
+    return {
+        "basecalls": (lambda: basecalls.device_hits("x.bam", [snv], hit_capacity=100)[:2],
+                      (9,), abi.BASEPILEUP_OVERFLOW, ("needed_capacity",)),
+        "readwindows": (lambda: readwindows.device_hits("x.bam", "x.fa", [0], [deletion], hit_capacity=100)[:2],
+                        (14,), abi.INDELPILEUP_OVERFLOW, ("needed_capacity",)),
+        "fragments": (lambda: fragments.device_observations("x.bam", [snv], fragments.Props(500, 60, 150), member_capacity=100, name_capacity=200, key_capacity=300)[::2],
+                      (12, 13, 14), abi.FRAGPILEUP_MEMBER_OVERFLOW, ("needed_members", "needed_name_bytes", "needed_keys")),
+    }
+
+
+@pytest.mark.parametrize("which", ["basecalls", "readwindows", "fragments"])
+def test_pileup_wrappers_retry_once(which, monkeypatch):
+    """An overflow is retried once, as the docstrings say, however often the engine reports one: two sessions, both closed, then what
+    retry=False returns (the counts with the overflow bit, empty arrays)."""
+    import threading
+    call, cap_args, status, needed = _pileup_wrappers()[which]
+    fake = _OverflowingPileups(cap_args, status, needed)
+    monkeypatch.setattr(engine, "_LIB", fake)
+    got = []
+
+    def run():
+        try:
+            got.append(call())
+        except BaseException as e:  # noqa: BLE001 (reported below, in the test's thread)
+            got.append(e)
+    t = threading.Thread(target=run, daemon=True)
+    t.start()
+    t.join(5.0)
+    assert not t.is_alive(), "the wrapper did not return"
+    assert not isinstance(got[0], BaseException), got[0]
+    arr, counts = got[0]
+    assert (fake.opens, fake.closes) == (2, 2)
+    assert counts.status & status and len(arr) == 0
+    assert [getattr(counts, f) for f in needed] == fake.caps
+
+
 def test_library_exports_all_declared_symbols():
     engine.build()
     L = engine.lib()

@@ -281,8 +281,6 @@ def test_writer_fixed_point_formatting_equals_printf():
     import ctypes as C
     from varlociraptor_amd import engine
     L = engine.lib()
-    L.vlr_selftest_format_fixed.restype = C.c_int
-    L.vlr_selftest_format_fixed.argtypes = [C.c_double, C.c_int, C.c_char_p, C.c_int]
     buf = C.create_string_buffer(80)
 
     def fmt(v, d):

@@ -1,8 +1,9 @@
 """ctypes mirror of include/vlr.h (the C ABI of the engine).
 
-Only struct layouts and constants live here; nothing is computed.  Both the product binding
-(`varlociraptor_amd.engine`) and the test-only oracle binding (`oracle/oracle.py`) use these
-definitions, because the oracle consumes exactly the same boundary structs as the engine.
+Only struct layouts, constants and the signature of every entry point (SIGNATURES, at the end) live
+here; nothing is computed.  Both the product binding (`varlociraptor_amd.engine`, which applies the
+signatures to the library once, at load) and the test-only oracle binding (`oracle/oracle.py`) use
+these definitions, because the oracle consumes exactly the same boundary structs as the engine.
 """
 import ctypes as C
 
@@ -233,3 +234,157 @@ class FragPileupRealignCounts(C.Structure):
     """vlr_fragpileup_realign_counts"""
     _fields_ = [("n_evidences", C.c_int64), ("needed_evidences", C.c_int64), ("x_bytes", C.c_int64), ("y_bytes", C.c_int64), ("n_ranges", C.c_int64),
                 ("seconds", C.c_double * 4)]
+
+
+class RealignDesc(C.Structure):
+    """vlr_realign_batch_desc"""
+    _fields_ = [("n_pairs", C.c_int64), ("x_offset", C.c_void_p), ("x_bases", C.c_void_p), ("y_offset", C.c_void_p),
+                ("y_bases", C.c_void_p), ("y_quals", C.c_void_p), ("max_edit_dist", C.c_void_p), ("gap", C.c_double * 4)]
+
+
+class ObsSites(C.Structure):
+    """vlr_obs_sites"""
+    _fields_ = [
+        ("n_loci", C.c_int64), ("n_contigs", C.c_int32), ("_pad", C.c_int32),
+        ("contig_names", C.POINTER(C.c_char_p)), ("contig", C.c_void_p), ("pos", C.c_void_p), ("strings", C.c_void_p),
+        ("id_offset", C.c_void_p), ("ref_offset", C.c_void_p), ("alt_offset", C.c_void_p),
+        ("group_representative", C.c_void_p), ("heterozygosity_ln", C.c_void_p), ("somatic_effective_mutation_rate_ln", C.c_void_p),
+        ("third_allele_evidence", C.c_void_p), ("imprecise", C.c_void_p), ("group_key", C.c_void_p),
+    ]
+
+
+# name -> (restype, argtypes) of every function include/vlr.h declares, in the header's order.  engine.lib() applies the table to
+# the library once; tests/test_host_logic.py compares it with the header's prototypes (count, and pointer / 32-bit / 64-bit /
+# float / double of every parameter and of the return value).  Opaque handles and plain arrays are c_void_p.
+_FRAGPILEUP_OPEN_HEAD = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                         C.c_int64, C.c_int64, C.c_int64, C.c_int64]   # what vlr_fragpileup_open and vlr_fragpileup_open_realign share
+SIGNATURES = {
+    # ---- entry points: build, plans, batches
+    "vlr_abi_version": (C.c_int, []),
+    "vlr_build_id": (C.c_char_p, []),
+    "vlr_last_error": (C.c_char_p, []),
+    "vlr_plan_create": (C.c_int, [C.POINTER(ScenarioDesc), C.c_int, C.POINTER(C.c_void_p)]),
+    "vlr_plan_destroy": (None, [C.c_void_p]),
+    "vlr_plan_n_out": (C.c_int, [C.c_void_p]),
+    "vlr_plan_n_samples": (C.c_int, [C.c_void_p]),
+    "vlr_plan_set_max_depth": (C.c_int, [C.c_void_p, C.c_int]),
+    "vlr_plan_set_max_obs": (C.c_int, [C.c_void_p, C.c_int]),
+    "vlr_plan_fit_max_obs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "vlr_batch_run": (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Results), C.c_void_p]),
+    "vlr_batch_run_host": (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Results)]),
+    "vlr_batch_run_device_in": (C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(Results)]),
+    # ---- one node, several devices
+    "vlr_node_create": (C.c_int, [C.POINTER(ScenarioDesc), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
+    "vlr_node_destroy": (None, [C.c_void_p]),
+    "vlr_node_n_devices": (C.c_int, [C.c_void_p]),
+    "vlr_node_device": (C.c_int, [C.c_void_p, C.c_int]),
+    "vlr_node_plan": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "vlr_node_set_max_depth": (C.c_int, [C.c_void_p, C.c_int]),
+    "vlr_node_set_max_obs": (C.c_int, [C.c_void_p, C.c_int]),
+    "vlr_node_shard_range": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vlr_node_batch_run_host": (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Results)]),
+    # ---- page-locked host memory, buffer reservation, counters of a plan
+    "vlr_host_alloc": (C.c_void_p, [C.c_size_t]),
+    "vlr_host_free": (None, [C.c_void_p]),
+    "vlr_plan_reserve": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
+    "vlr_plan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "vlr_plan_last_instance": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vlr_plan_work_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
+    "vlr_plan_fused_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
+    # ---- read-vs-allele pair HMM, edit-distance pre-filter
+    "vlr_realign_batch": (C.c_int, [C.c_int, C.POINTER(RealignDesc), C.c_void_p, C.c_void_p]),
+    "vlr_realign_batch_host": (C.c_int, [C.c_int, C.POINTER(RealignDesc), C.c_void_p]),
+    "vlr_realign_fast_batch": (C.c_int, [C.c_int, C.POINTER(RealignDesc), C.c_void_p, C.c_void_p]),
+    "vlr_realign_fast_batch_host": (C.c_int, [C.c_int, C.POINTER(RealignDesc), C.c_void_p]),
+    "vlr_realign_homopolymer_batch": (C.c_int, [C.c_int, C.POINTER(RealignDesc), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "vlr_realign_homopolymer_batch_host": (C.c_int, [C.c_int, C.POINTER(RealignDesc), C.POINTER(C.c_double), C.c_void_p]),
+    "vlr_edit_distance_batch": (C.c_int, [C.c_int, C.POINTER(RealignDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vlr_edit_distance_batch_host": (C.c_int, [C.c_int, C.POINTER(RealignDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ---- Bayesian FDR control, contamination estimation
+    "vlr_fdr_threshold": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "vlr_contamination_posterior": (C.c_int, [C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 2 + [C.POINTER(C.c_double)]),
+    # ---- alignment properties
+    "vlr_bamstats_open": (C.c_int, [C.c_int, C.c_char_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "vlr_bamstats_add_bam": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "vlr_bamstats_result": (C.c_int, [C.c_void_p, C.POINTER(BamStatsResult)]),
+    "vlr_bamstats_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "vlr_bamstats_close": (None, [C.c_void_p]),
+    # ---- SNV / MNV allele supports from BAM records
+    "vlr_basepileup_open": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                      C.POINTER(C.c_void_p)]),
+    "vlr_basepileup_add_bam": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "vlr_basepileup_result": (C.c_int, [C.c_void_p, C.POINTER(BasePileupCounts)]),
+    "vlr_basepileup_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "vlr_basepileup_tables": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "vlr_basepileup_close": (None, [C.c_void_p]),
+    # ---- indel allele supports from BAM records
+    "vlr_indelpileup_open": (C.c_int, [C.c_int, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "vlr_indelpileup_add_bam": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "vlr_indelpileup_result": (C.c_int, [C.c_void_p, C.POINTER(IndelPileupCounts)]),
+    "vlr_indelpileup_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "vlr_indelpileup_read_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "vlr_indelpileup_close": (None, [C.c_void_p]),
+    # ---- fragment observations of SNV / MNV candidates from BAM records
+    "vlr_fragpileup_open": (C.c_int, _FRAGPILEUP_OPEN_HEAD + [C.POINTER(C.c_void_p)]),
+    "vlr_fragpileup_add_bam": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "vlr_fragpileup_result": (C.c_int, [C.c_void_p, C.POINTER(FragPileupCounts)]),
+    "vlr_fragpileup_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "vlr_fragpileup_close": (None, [C.c_void_p]),
+    "vlr_fragpileup_open_realign": (C.c_int, _FRAGPILEUP_OPEN_HEAD + [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int64,
+                                                                      C.POINTER(C.c_void_p)]),
+    "vlr_fragpileup_realign_result": (C.c_int, [C.c_void_p, C.POINTER(FragPileupRealignCounts)]),
+    "vlr_fragpileup_read_realigned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    # ---- consumers of a calls file: filter-calls control-fdr / posterior-odds, estimate mutational-burden
+    "vlr_calls_filter_fdr": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_double, C.c_uint32, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vlr_posterior_odds_keep": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vlr_range_group_lse": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vlr_callstats_last_kernel_ms": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "vlr_calls_filter_odds": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vlr_calls_mutational_burden": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_int, C.c_void_p, C.POINTER(C.c_int64)]),
+    # ---- diagnostics
+    "vlr_selftest_math": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "vlr_selftest_stream": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int]),
+    # ---- native ingest / emission
+    "vlr_obs_read": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "vlr_obs_table_free": (None, [C.c_void_p]),
+    "vlr_obs_table_batch": (C.c_int, [C.c_void_p, C.POINTER(Batch)]),
+    "vlr_obs_table_sites": (C.c_int, [C.c_void_p, C.POINTER(ObsSites)]),
+    "vlr_obs_write": (C.c_int, [C.c_char_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "vlr_calls_write": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p, C.POINTER(Results), C.POINTER(C.c_char_p), C.c_int]),
+    "vlr_obs_reader_open": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "vlr_obs_reader_next": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "vlr_obs_reader_close": (None, [C.c_void_p]),
+    "vlr_calls_writer_open": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "vlr_calls_writer_append": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Results), C.POINTER(C.c_char_p), C.c_int]),
+    "vlr_calls_writer_close": (C.c_int, [C.c_void_p]),
+    "vlr_calls_writer_set_part": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "vlr_calls_concat_parts": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_int]),
+    "vlr_selftest_format_fixed": (C.c_int, [C.c_double, C.c_int, C.c_char_p, C.c_int]),
+    "vlr_selftest_afd_text": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "vlr_ingest_last_timings": (None, [C.POINTER(C.c_double)]),
+    "vlr_ingest_total_timings": (None, [C.POINTER(C.c_double), C.c_int]),
+    # ---- device front door
+    "vlr_obs_reader_open_device": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "vlr_obs_reader_open_device_shard": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "vlr_obs_reader_shard_row_size": (C.c_int, []),
+    "vlr_obs_reader_shard_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vlr_obs_reader_shard_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vlr_node_obs_readers_open": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "vlr_obs_table_device_batch": (C.c_int, [C.c_void_p, C.POINTER(Batch)]),
+    "vlr_obs_reader_set_host_columns": (C.c_int, [C.c_void_p, C.c_int]),
+    "vlr_obs_table_summaries": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "vlr_obs_table_fetch_columns": (C.c_int, [C.c_void_p]),
+    "vlr_obs_reader_set_async_columns": (C.c_int, [C.c_void_p, C.c_int]),
+    "vlr_bgzf_inflate": (C.c_int, [C.c_int, C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "vlr_ingest_device_timings": (None, [C.POINTER(C.c_double), C.c_int]),
+    "vlr_ingest_device_trim": (None, []),
+}
+
+# exported by the library without a declaration in the header: developer aids that a test and a tool read
+INTERNAL_SIGNATURES = {
+    "vlr_launch_realign_pairs_per_wave": (C.c_int, []),                              # realign.last_pairs_per_wave
+    "vlr_plan_profile_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),  # tools/profile_phases.py
+}

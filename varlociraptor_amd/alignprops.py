@@ -794,16 +794,6 @@ def count_bams_device(fasta: str, bams: Sequence[str], num_records: int, device:
     import ctypes as C
     from . import abi, engine
     L = engine.lib()
-    L.vlr_bamstats_open.restype = C.c_int
-    L.vlr_bamstats_open.argtypes = [C.c_int, C.c_char_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
-    L.vlr_bamstats_add_bam.restype = C.c_int
-    L.vlr_bamstats_add_bam.argtypes = [C.c_void_p, C.c_char_p]
-    L.vlr_bamstats_result.restype = C.c_int
-    L.vlr_bamstats_result.argtypes = [C.c_void_p, C.POINTER(abi.BamStatsResult)]
-    L.vlr_bamstats_read.restype = C.c_int
-    L.vlr_bamstats_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
-    L.vlr_bamstats_close.restype = None
-    L.vlr_bamstats_close.argtypes = [C.c_void_p]
     h = C.c_void_p()
     rc = L.vlr_bamstats_open(device, fasta.encode(), C.c_int64(num_records), C.c_int64(window_bytes), C.byref(h))
     if rc != 0:

@@ -92,8 +92,6 @@ def library_tables() -> Tables:
     import ctypes as C
     from . import engine
     L = engine.lib()
-    L.vlr_basepileup_tables.restype = C.c_int
-    L.vlr_basepileup_tables.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     call, mis = (C.c_double * 256)(), (C.c_double * 256)()
     engine._check(L.vlr_basepileup_tables(call, mis))
     return Tables(list(call), list(mis))
@@ -449,7 +447,7 @@ def device_hits(bam: str, loci: Sequence[Locus], device: int = 0, realign_indel_
     retry=False (then the counts carry BASEPILEUP_OVERFLOW and the array is empty)."""
     import ctypes as C
     from . import engine
-    L = engine.bind_basepileup()
+    L = engine.lib()
     n = len(loci)
     ref_id = np.array([l.ref_id for l in loci], np.int32)
     start = np.array([l.start for l in loci], np.int64)
@@ -470,6 +468,7 @@ def device_hits(bam: str, loci: Sequence[Locus], device: int = 0, realign_indel_
                 raise BasePileupError("the guard words behind the hit buffer changed")
             if res.status & abi.BASEPILEUP_OVERFLOW and retry:
                 cap = int(res.needed_capacity)
+                retry = False
                 continue
             hits = np.zeros(int(res.n_hits), abi.BASEPILEUP_HIT_DTYPE)
             engine._check(L.vlr_basepileup_read(h, hits.ctypes.data, int(res.n_hits)))

@@ -179,11 +179,7 @@ def range_group_lse(vaf, ln_prob, group, lo, hi, n_groups: int, device="cpu") ->
         import ctypes as C
         from . import engine
         L = engine.lib()
-        L.vlr_range_group_lse.restype = C.c_int
-        L.vlr_range_group_lse.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        rc = L.vlr_range_group_lse(_device_index(device), len(vaf), vaf.ctypes.data, lp.ctypes.data, grp.ctypes.data, R, lo.ctypes.data, hi.ctypes.data, G, out.ctypes.data)
-        if rc != 0:
-            raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+        engine.check(L.vlr_range_group_lse(_device_index(device), len(vaf), vaf.ctypes.data, lp.ctypes.data, grp.ctypes.data, R, lo.ctypes.data, hi.ctypes.data, G, out.ctypes.data))
         return out
     # The reference's order of a cell's terms: its map is keyed by VAF and a key's entries keep their push order, so a range query
     # walks the entries by (VAF, push order); into_group_map keeps that order within a group.  Sort once by (group, VAF), stable.
@@ -230,8 +226,6 @@ def last_kernel_ms() -> Tuple[float, float]:
     import ctypes as C
     from . import engine
     L = engine.lib()
-    L.vlr_callstats_last_kernel_ms.restype = C.c_int
-    L.vlr_callstats_last_kernel_ms.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     a, b = C.c_double(), C.c_double()
     L.vlr_callstats_last_kernel_ms(C.byref(a), C.byref(b))
     return float(a.value), float(b.value)
@@ -242,9 +236,6 @@ def cells_native(path: str, events: Sequence[str], samples: Sequence[str], by_sa
     import ctypes as C
     from . import engine
     L = engine.lib()
-    L.vlr_calls_mutational_burden.restype = C.c_int
-    L.vlr_calls_mutational_burden.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                              C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
     lo = np.ascontiguousarray(lo, np.float64)
     hi = np.ascontiguousarray(hi, np.float64)
     G = (len(samples) if by_sample else 1) * N_SIG
@@ -252,10 +243,8 @@ def cells_native(path: str, events: Sequence[str], samples: Sequence[str], by_sa
     ev = (C.c_char_p * len(events))(*[e.encode() for e in events])
     sm = (C.c_char_p * len(samples))(*[s.encode() for s in samples])
     n = C.c_int64()
-    rc = L.vlr_calls_mutational_burden(path.encode(), len(events), ev, len(samples), sm, int(bool(by_sample)), len(lo), lo.ctypes.data, hi.ctypes.data,
-                                       int(device), int(threads), out.ctypes.data, C.byref(n))
-    if rc != 0:
-        raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+    engine.check(L.vlr_calls_mutational_burden(path.encode(), len(events), ev, len(samples), sm, int(bool(by_sample)), len(lo), lo.ctypes.data, hi.ctypes.data,
+                                               int(device), int(threads), out.ctypes.data, C.byref(n)))
     return out, int(n.value)
 
 

@@ -249,8 +249,6 @@ def posterior_grid_device(list_offset, list_vaf, list_lnprob, map_vaf, ln_prob_d
     import ctypes as C
     from . import engine
     L = engine.lib()
-    L.vlr_contamination_posterior.restype = C.c_int
-    L.vlr_contamination_posterior.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 2 + [C.POINTER(C.c_double)]
     off = np.ascontiguousarray(list_offset, np.int64)
     lv, lp = np.ascontiguousarray(list_vaf, np.float64), np.ascontiguousarray(list_lnprob, np.float64)
     mv, pd = np.ascontiguousarray(map_vaf, np.float64), np.ascontiguousarray(ln_prob_denovo, np.float64)
@@ -260,10 +258,8 @@ def posterior_grid_device(list_offset, list_vaf, list_lnprob, map_vaf, ln_prob_d
         raise ValueError("inconsistent contamination inputs")
     out = np.zeros(len(MAX_SOMATIC_VAFS) * N_C, np.float64)
     marg = C.c_double()
-    rc = L.vlr_contamination_posterior(int(device), n, off.ctypes.data, lv.ctypes.data, lp.ctypes.data, mv.ctypes.data, pd.ctypes.data,
-                                       float(max_vaf), pr.ctypes.data, out.ctypes.data, C.byref(marg))
-    if rc != 0:
-        raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+    engine.check(L.vlr_contamination_posterior(int(device), n, off.ctypes.data, lv.ctypes.data, lp.ctypes.data, mv.ctypes.data, pd.ctypes.data,
+                                               float(max_vaf), pr.ctypes.data, out.ctypes.data, C.byref(marg)))
     return out, float(marg.value)
 
 

@@ -21,16 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VLR_LIB", os.path.join(_HERE, "libvlr.so"))  # VLR_LIB: tuning variants only
 _LIB = None
 
-EXPORTS = [
-    "vlr_abi_version", "vlr_build_id", "vlr_last_error", "vlr_plan_create", "vlr_plan_destroy", "vlr_plan_n_out",
-    "vlr_plan_n_samples", "vlr_plan_set_max_depth", "vlr_plan_set_max_obs", "vlr_plan_fit_max_obs", "vlr_plan_reserve", "vlr_batch_run", "vlr_batch_run_host", "vlr_batch_run_device_in",
-    "vlr_plan_last_kernel_ms", "vlr_plan_last_instance", "vlr_plan_work_counters", "vlr_plan_fused_counters", "vlr_host_alloc", "vlr_host_free",
-    "vlr_node_create", "vlr_node_destroy", "vlr_node_n_devices", "vlr_node_device", "vlr_node_plan", "vlr_node_set_max_depth", "vlr_node_set_max_obs", "vlr_node_shard_range", "vlr_node_batch_run_host",
-    "vlr_realign_batch", "vlr_realign_batch_host", "vlr_realign_fast_batch", "vlr_realign_fast_batch_host", "vlr_realign_homopolymer_batch", "vlr_realign_homopolymer_batch_host", "vlr_edit_distance_batch", "vlr_edit_distance_batch_host", "vlr_fdr_threshold", "vlr_contamination_posterior", "vlr_bamstats_open", "vlr_bamstats_add_bam", "vlr_bamstats_result", "vlr_bamstats_read", "vlr_bamstats_close", "vlr_basepileup_open", "vlr_basepileup_add_bam", "vlr_basepileup_result", "vlr_basepileup_read", "vlr_basepileup_tables", "vlr_basepileup_close", "vlr_indelpileup_open", "vlr_indelpileup_add_bam", "vlr_indelpileup_result", "vlr_indelpileup_read", "vlr_indelpileup_read_pairs", "vlr_indelpileup_close", "vlr_fragpileup_open", "vlr_fragpileup_add_bam", "vlr_fragpileup_result", "vlr_fragpileup_read", "vlr_fragpileup_close", "vlr_fragpileup_open_realign", "vlr_fragpileup_realign_result", "vlr_fragpileup_read_realigned", "vlr_selftest_math", "vlr_selftest_stream", "vlr_selftest_format_fixed", "vlr_selftest_afd_text",
-    "vlr_obs_read", "vlr_obs_table_free", "vlr_obs_table_batch", "vlr_obs_table_sites", "vlr_obs_write", "vlr_calls_write", "vlr_ingest_last_timings", "vlr_ingest_total_timings",
-    "vlr_obs_reader_open", "vlr_obs_reader_open_device", "vlr_obs_table_device_batch", "vlr_obs_reader_set_host_columns", "vlr_obs_reader_set_async_columns", "vlr_obs_table_fetch_columns", "vlr_obs_table_summaries", "vlr_bgzf_inflate", "vlr_ingest_device_timings", "vlr_ingest_device_trim", "vlr_obs_reader_open_device_shard", "vlr_obs_reader_shard_row_size", "vlr_obs_reader_shard_counts", "vlr_obs_reader_shard_assign", "vlr_node_obs_readers_open", "vlr_obs_reader_next", "vlr_obs_reader_close", "vlr_calls_writer_open", "vlr_calls_writer_append", "vlr_calls_writer_close", "vlr_calls_writer_set_part", "vlr_calls_concat_parts", "vlr_calls_filter_fdr",
-    "vlr_posterior_odds_keep", "vlr_range_group_lse", "vlr_calls_filter_odds", "vlr_calls_mutational_burden", "vlr_callstats_last_kernel_ms",
-]
+EXPORTS = sorted(abi.SIGNATURES)  # every function include/vlr.h declares
 
 
 # What libvlr.so is built from, relative to this package, in the order of csrc/Makefile's SRC and headers (source_id hashes them in it)
@@ -90,6 +81,15 @@ def build_matrix(force: bool = False) -> str:
     return MATRIX_DIR
 
 
+def bind(L):
+    """Set the C signature of every entry point on a loaded library (abi.SIGNATURES, abi.INTERNAL_SIGNATURES): the one place that does."""
+    for table in (abi.SIGNATURES, abi.INTERNAL_SIGNATURES):
+        for name, (restype, argtypes) in table.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+    return L
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -105,106 +105,19 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        L.vlr_abi_version.restype = C.c_int
-        L.vlr_last_error.restype = C.c_char_p
-        L.vlr_build_id.restype = C.c_char_p
-        L.vlr_plan_create.restype = C.c_int
-        L.vlr_plan_create.argtypes = [C.POINTER(abi.ScenarioDesc), C.c_int, C.POINTER(C.c_void_p)]
-        L.vlr_plan_destroy.restype = None
-        L.vlr_plan_destroy.argtypes = [C.c_void_p]
-        L.vlr_plan_n_out.restype = C.c_int
-        L.vlr_plan_n_out.argtypes = [C.c_void_p]
-        L.vlr_plan_n_samples.restype = C.c_int
-        L.vlr_plan_n_samples.argtypes = [C.c_void_p]
-        L.vlr_plan_set_max_depth.restype = C.c_int
-        L.vlr_plan_set_max_depth.argtypes = [C.c_void_p, C.c_int]
-        L.vlr_plan_set_max_obs.restype = C.c_int
-        L.vlr_plan_set_max_obs.argtypes = [C.c_void_p, C.c_int]
-        L.vlr_batch_run.restype = C.c_int
-        L.vlr_batch_run.argtypes = [C.c_void_p, C.POINTER(abi.Batch), C.POINTER(abi.Results), C.c_void_p]
-        L.vlr_batch_run_host.restype = C.c_int
-        L.vlr_batch_run_host.argtypes = [C.c_void_p, C.POINTER(abi.Batch), C.POINTER(abi.Results)]
-        L.vlr_plan_last_kernel_ms.restype = C.c_int
-        L.vlr_plan_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        L.vlr_plan_last_instance.restype = C.c_int
-        L.vlr_plan_last_instance.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.vlr_host_alloc.restype = C.c_void_p
-        L.vlr_host_alloc.argtypes = [C.c_size_t]
-        L.vlr_host_free.restype = None
-        L.vlr_host_free.argtypes = [C.c_void_p]
-        L.vlr_plan_work_counters.restype = C.c_int
-        L.vlr_plan_work_counters.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
-        L.vlr_plan_fused_counters.restype = C.c_int
-        L.vlr_plan_fused_counters.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
+        bind(L)
         if L.vlr_abi_version() != abi.ABI_VERSION:
             raise EngineError(abi.ERR_INVALID_ARGUMENT, "ABI version mismatch")
         _LIB = L
     return _LIB
 
 
-def bind_basepileup():
-    """the library with the argument types of vlr_basepileup_* set (varlociraptor_amd/basecalls.py: device_hits)"""
-    L = lib()
-    L.vlr_basepileup_open.restype = C.c_int
-    L.vlr_basepileup_open.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
-                                      C.POINTER(C.c_void_p)]
-    L.vlr_basepileup_add_bam.restype = C.c_int
-    L.vlr_basepileup_add_bam.argtypes = [C.c_void_p, C.c_char_p]
-    L.vlr_basepileup_result.restype = C.c_int
-    L.vlr_basepileup_result.argtypes = [C.c_void_p, C.POINTER(abi.BasePileupCounts)]
-    L.vlr_basepileup_read.restype = C.c_int
-    L.vlr_basepileup_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.vlr_basepileup_close.restype = None
-    L.vlr_basepileup_close.argtypes = [C.c_void_p]
-    return L
-
-
-def bind_indelpileup():
-    """the library with the argument types of vlr_indelpileup_* set (varlociraptor_amd/readwindows.py: device_hits)"""
-    L = lib()
-    L.vlr_indelpileup_open.restype = C.c_int
-    L.vlr_indelpileup_open.argtypes = [C.c_int, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
-    L.vlr_indelpileup_add_bam.restype = C.c_int
-    L.vlr_indelpileup_add_bam.argtypes = [C.c_void_p, C.c_char_p]
-    L.vlr_indelpileup_result.restype = C.c_int
-    L.vlr_indelpileup_result.argtypes = [C.c_void_p, C.POINTER(abi.IndelPileupCounts)]
-    L.vlr_indelpileup_read.restype = C.c_int
-    L.vlr_indelpileup_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.vlr_indelpileup_read_pairs.restype = C.c_int
-    L.vlr_indelpileup_read_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
-    L.vlr_indelpileup_close.restype = None
-    L.vlr_indelpileup_close.argtypes = [C.c_void_p]
-    return L
-
-
-def bind_fragpileup():
-    """the library with the argument types of vlr_fragpileup_* set (varlociraptor_amd/fragments.py: device_observations)"""
-    L = lib()
-    L.vlr_fragpileup_open.restype = C.c_int
-    L.vlr_fragpileup_open.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
-                                      C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
-    L.vlr_fragpileup_add_bam.restype = C.c_int
-    L.vlr_fragpileup_add_bam.argtypes = [C.c_void_p, C.c_char_p]
-    L.vlr_fragpileup_result.restype = C.c_int
-    L.vlr_fragpileup_result.argtypes = [C.c_void_p, C.POINTER(abi.FragPileupCounts)]
-    L.vlr_fragpileup_read.restype = C.c_int
-    L.vlr_fragpileup_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
-    L.vlr_fragpileup_open_realign.restype = C.c_int
-    L.vlr_fragpileup_open_realign.argtypes = L.vlr_fragpileup_open.argtypes[:-1] + [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int64,
-                                                                                    C.POINTER(C.c_void_p)]
-    L.vlr_fragpileup_realign_result.restype = C.c_int
-    L.vlr_fragpileup_realign_result.argtypes = [C.c_void_p, C.POINTER(abi.FragPileupRealignCounts)]
-    L.vlr_fragpileup_read_realigned.restype = C.c_int
-    L.vlr_fragpileup_read_realigned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.vlr_fragpileup_close.restype = None
-    L.vlr_fragpileup_close.argtypes = [C.c_void_p]
-    return L
-
-
-def _check(rc):
+def check(rc):
     if rc != 0:
-        raise EngineError(rc, lib().vlr_last_error().decode())
+        raise EngineError(rc, (lib().vlr_last_error() or b"").decode())
+
+
+_check = check
 
 
 class _HostBlock:
@@ -265,10 +178,7 @@ class Plan:
         """vlr_plan_fit_max_obs: LDS budget from the batch's pileup offsets (host array of n_loci * n_samples + 1 uint32) — the
         deepest locus, or the budget that lets sixteen workgroups share a CU when at most 0.5 % of the loci exceed it."""
         off = np.ascontiguousarray(obs_offset, np.uint32)
-        L = lib()
-        L.vlr_plan_fit_max_obs.restype = C.c_int
-        L.vlr_plan_fit_max_obs.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-        rc = L.vlr_plan_fit_max_obs(self._h, off.ctypes.data, (len(off) - 1) // self.n_samples)
+        rc = lib().vlr_plan_fit_max_obs(self._h, off.ctypes.data, (len(off) - 1) // self.n_samples)
         if rc < 0:
             _check(rc)
         return int(rc)
@@ -295,23 +205,17 @@ class Plan:
     def call_table_device(self, table, afd_capacity: int = 0, results: Optional[CallResults] = None) -> CallResults:
         """vlr_batch_run_device_in: evaluate the device-resident batch of a table read by a device reader (ingest.ObsReader(device=k));
         results in host buffers."""
-        L = lib()
-        L.vlr_batch_run_device_in.restype = C.c_int
-        L.vlr_batch_run_device_in.argtypes = [C.c_void_p, C.POINTER(abi.Batch), C.c_void_p, C.POINTER(abi.Results)]
         db = table.device_batch()
         res = results if results is not None else CallResults(int(db.n_loci), self.n_out, self.n_samples, afd_capacity)
         rs = res.as_struct()
-        _check(L.vlr_batch_run_device_in(self._h, C.byref(db), C.c_void_p(table._struct.obs_offset), C.byref(rs)))
+        _check(lib().vlr_batch_run_device_in(self._h, C.byref(db), C.c_void_p(table._struct.obs_offset), C.byref(rs)))
         return res
 
     # ---- device pointers (torch tensors) in/out, stream-ordered
     def reserve(self, n_loci: int, with_afd=False):
         """Size the plan's device buffers once so that call_device never allocates (vlr_plan_reserve).  `with_afd`: False, or
         the AFD capacity (entries per locus and sample) the result buffers will have."""
-        L = lib()
-        L.vlr_plan_reserve.restype = C.c_int
-        L.vlr_plan_reserve.argtypes = [C.c_void_p, C.c_int64, C.c_int]
-        _check(L.vlr_plan_reserve(self._h, int(n_loci), int(with_afd)))
+        _check(lib().vlr_plan_reserve(self._h, int(n_loci), int(with_afd)))
 
     def call_device(self, dbatch: "DeviceBatch", out: "DeviceResults", stream=None):
         bs, rs = dbatch.as_struct(), out.as_struct()
@@ -343,11 +247,8 @@ class Plan:
 
 def shard_range(n_loci: int, n_shards: int, shard: int):
     """vlr_node_shard_range: the contiguous block of loci shard `shard` of `n_shards` evaluates (no device needed)."""
-    L = lib()
-    L.vlr_node_shard_range.restype = C.c_int
-    L.vlr_node_shard_range.argtypes = [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     l0, l1 = C.c_int64(), C.c_int64()
-    _check(L.vlr_node_shard_range(int(n_loci), int(n_shards), int(shard), C.byref(l0), C.byref(l1)))
+    _check(lib().vlr_node_shard_range(int(n_loci), int(n_shards), int(shard), C.byref(l0), C.byref(l1)))
     return int(l0.value), int(l1.value)
 
 
@@ -357,22 +258,6 @@ class Node:
 
     def __init__(self, scenario, devices=None, max_depth: Optional[int] = None):
         L = lib()
-        L.vlr_node_create.restype = C.c_int
-        L.vlr_node_create.argtypes = [C.POINTER(abi.ScenarioDesc), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]
-        L.vlr_node_destroy.restype = None
-        L.vlr_node_destroy.argtypes = [C.c_void_p]
-        L.vlr_node_n_devices.restype = C.c_int
-        L.vlr_node_n_devices.argtypes = [C.c_void_p]
-        L.vlr_node_device.restype = C.c_int
-        L.vlr_node_device.argtypes = [C.c_void_p, C.c_int]
-        L.vlr_node_plan.restype = C.c_void_p
-        L.vlr_node_plan.argtypes = [C.c_void_p, C.c_int]
-        L.vlr_node_set_max_depth.restype = C.c_int
-        L.vlr_node_set_max_depth.argtypes = [C.c_void_p, C.c_int]
-        L.vlr_node_set_max_obs.restype = C.c_int
-        L.vlr_node_set_max_obs.argtypes = [C.c_void_p, C.c_int]
-        L.vlr_node_batch_run_host.restype = C.c_int
-        L.vlr_node_batch_run_host.argtypes = [C.c_void_p, C.POINTER(abi.Batch), C.POINTER(abi.Results)]
         self.scenario = scenario
         self._h = C.c_void_p()
         desc = scenario.desc()

@@ -134,13 +134,9 @@ def fdr_threshold_device(prob_dist: Sequence[float], alpha_ln: float, smart: boo
     import ctypes as C
     from . import engine
     L = engine.lib()
-    L.vlr_fdr_threshold.restype = C.c_int
-    L.vlr_fdr_threshold.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     a = np.ascontiguousarray(prob_dist, dtype=np.float64)
     thr, st = C.c_double(), C.c_int()
-    rc = L.vlr_fdr_threshold(device, a.ctypes.data, len(a), int(smart), float(alpha_ln), C.byref(thr), C.byref(st))
-    if rc != 0:
-        raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+    engine.check(L.vlr_fdr_threshold(device, a.ctypes.data, len(a), int(smart), float(alpha_ln), C.byref(thr), C.byref(st)))
     return {0: None, 1: thr.value, 2: 0.0, 3: None}[st.value]
 
 
@@ -249,9 +245,6 @@ def filter_calls_native(in_path: str, out_path: str, events: Sequence[str], alph
     import ctypes as C
     from . import engine
     L = engine.lib()
-    L.vlr_calls_filter_fdr.restype = C.c_int
-    L.vlr_calls_filter_fdr.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_double, C.c_uint32, C.c_char_p, C.c_int64, C.c_int64,
-                                       C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     ev = (C.c_char_p * len(events))(*[e.encode() for e in events])
     mode = (1 if local else 0) | (2 if smart else 0) | (4 if smart_retain_artifacts else 0)
     kind, lo, hi = None, -1, -1
@@ -260,8 +253,6 @@ def filter_calls_native(in_path: str, out_path: str, events: Sequence[str], alph
         if rng is not None:
             lo, hi = int(rng[0]), int(min(rng[1], 1 << 62))
     kept, total = C.c_int64(), C.c_int64()
-    rc = L.vlr_calls_filter_fdr(in_path.encode(), out_path.encode(), len(events), ev, float(alpha), mode, kind.encode() if kind else None, lo, hi,
-                                int(device), int(threads), C.byref(kept), C.byref(total))
-    if rc != 0:
-        raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+    engine.check(L.vlr_calls_filter_fdr(in_path.encode(), out_path.encode(), len(events), ev, float(alpha), mode, kind.encode() if kind else None, lo, hi,
+                                        int(device), int(threads), C.byref(kept), C.byref(total)))
     return int(kept.value), int(total.value)

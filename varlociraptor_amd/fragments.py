@@ -526,7 +526,7 @@ def device_observations(bams, loci: Sequence[Locus], props: Props, device: int =
     the result."""
     import ctypes as C
     from . import engine
-    L = engine.bind_fragpileup()
+    L = engine.lib()
     if isinstance(bams, str):
         bams = [bams]
     n = len(loci)
@@ -569,6 +569,7 @@ def device_observations(bams, loci: Sequence[Locus], props: Props, device: int =
             if res.status & over and retry:
                 mcap, ncap, kcap = max(mcap, int(res.needed_members)), max(ncap, int(res.needed_name_bytes)), max(kcap, int(res.needed_keys))
                 ecap = max(ecap, int(rres.needed_evidences))
+                retry = False
                 continue
             obs = np.zeros(int(res.n_obs), abi.FRAGPILEUP_OBS_DTYPE)
             loc = np.zeros(n, abi.FRAGPILEUP_LOCUS_DTYPE)

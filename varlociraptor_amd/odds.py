@@ -77,15 +77,10 @@ def keep_bits(ln_target, ln_other, valid, min_level: int, device="cpu") -> np.nd
             k = np.exp(lo - lt)
             lev = np.where(k <= 1.0, 0, np.where(k <= 3.0, 1, np.where(k <= 20.0, 2, np.where(k <= 150.0, 3, 4))))
         return (((va & 3) == 3) & (lev < int(min_level))).astype(np.uint8)
-    import ctypes as C
     from . import engine
     L = engine.lib()
-    L.vlr_posterior_odds_keep.restype = C.c_int
-    L.vlr_posterior_odds_keep.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     keep = np.zeros(len(lt), np.uint8)
-    rc = L.vlr_posterior_odds_keep(_device_index(device), len(lt), lt.ctypes.data, lo.ctypes.data, va.ctypes.data, int(min_level), keep.ctypes.data)
-    if rc != 0:
-        raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+    engine.check(L.vlr_posterior_odds_keep(_device_index(device), len(lt), lt.ctypes.data, lo.ctypes.data, va.ctypes.data, int(min_level), keep.ctypes.data))
     return keep
 
 
@@ -117,12 +112,8 @@ def filter_calls_native(in_path: str, out_path: str, events: Sequence[str], min_
     import ctypes as C
     from . import engine
     L = engine.lib()
-    L.vlr_calls_filter_odds.restype = C.c_int
-    L.vlr_calls_filter_odds.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     ev = (C.c_char_p * len(events))(*[e.encode() for e in events])
     kept, total = C.c_int64(), C.c_int64()
-    rc = L.vlr_calls_filter_odds(in_path.encode(), out_path.encode(), len(events), ev, int(min_level), int(device), int(threads), C.byref(kept), C.byref(total))
-    if rc != 0:
-        raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+    engine.check(L.vlr_calls_filter_odds(in_path.encode(), out_path.encode(), len(events), ev, int(min_level), int(device), int(threads), C.byref(kept), C.byref(total)))
     return int(kept.value), int(total.value)
 

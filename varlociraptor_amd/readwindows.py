@@ -388,7 +388,7 @@ def device_hits(bams, fasta: str, ref_id, loci: List[IndelLocus], mode: str = "e
     import ctypes as C
     import numpy as np
     from . import abi, engine, realign
-    L = engine.bind_indelpileup()
+    L = engine.lib()
     if mode not in MODES:
         raise ValueError("mode must be one of %s" % ", ".join(MODES))
     n = len(loci)

@@ -60,9 +60,7 @@ class HopParams:
         return (C.c_double * 16)(*self.as_list())
 
 
-class RealignDesc(C.Structure):
-    _fields_ = [("n_pairs", C.c_int64), ("x_offset", C.c_void_p), ("x_bases", C.c_void_p), ("y_offset", C.c_void_p),
-                ("y_bases", C.c_void_p), ("y_quals", C.c_void_p), ("max_edit_dist", C.c_void_p), ("gap", C.c_double * 4)]
+RealignDesc = abi.RealignDesc  # the structure lives with the rest of the ABI; this name stays importable
 
 
 class PairBatch:
@@ -94,12 +92,7 @@ class PairBatch:
 
 
 def _bind():
-    L = engine.lib()
-    L.vlr_realign_batch_host.restype = C.c_int
-    L.vlr_realign_batch_host.argtypes = [C.c_int, C.POINTER(RealignDesc), C.c_void_p]
-    L.vlr_realign_batch.restype = C.c_int
-    L.vlr_realign_batch.argtypes = [C.c_int, C.POINTER(RealignDesc), C.c_void_p, C.c_void_p]
-    return L
+    return engine.lib()
 
 
 def prob_related(batch: PairBatch, gap: Optional[GapParams] = None, device: int = 0) -> np.ndarray:
@@ -109,48 +102,36 @@ def prob_related(batch: PairBatch, gap: Optional[GapParams] = None, device: int 
     xo, xb, yo, yb, qb, band = batch.arrays()
     out = np.empty(len(batch), np.float64)
     d = RealignDesc(len(batch), xo.ctypes.data, xb.ctypes.data, yo.ctypes.data, yb.ctypes.data, qb.ctypes.data, band.ctypes.data, gap.as_array())
-    rc = L.vlr_realign_batch_host(device, C.byref(d), out.ctypes.data)
-    if rc != 0:
-        raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+    engine.check(L.vlr_realign_batch_host(device, C.byref(d), out.ctypes.data))
     return out
 
 
 def last_pairs_per_wave() -> int:
     """Which kernel the last prob_related / DevicePairs.run of this process launched: 1 = one pair per wave (VLR_REALIGN_SINGLE), 2 = two, 0 = none yet."""
-    f = engine.lib().vlr_launch_realign_pairs_per_wave
-    f.restype = C.c_int
-    return int(f())
+    return int(engine.lib().vlr_launch_realign_pairs_per_wave())
 
 
 def prob_best_path(batch: PairBatch, gap: Optional[GapParams] = None, device: int = 0) -> np.ndarray:
     """`fast` mode (PathHMMRealigner, realignment/mod.rs:547-678): ln of the best path probability over the minimal-edit-distance
     alignments of every pair (vlr_realign_fast_batch_host)."""
     L = _bind()
-    L.vlr_realign_fast_batch_host.restype = C.c_int
-    L.vlr_realign_fast_batch_host.argtypes = [C.c_int, C.POINTER(RealignDesc), C.c_void_p]
     gap = gap or GapParams()
     xo, xb, yo, yb, qb, band = batch.arrays()
     out = np.empty(len(batch), np.float64)
     d = RealignDesc(len(batch), xo.ctypes.data, xb.ctypes.data, yo.ctypes.data, yb.ctypes.data, qb.ctypes.data, None, gap.as_array())
-    rc = L.vlr_realign_fast_batch_host(device, C.byref(d), out.ctypes.data)
-    if rc != 0:
-        raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+    engine.check(L.vlr_realign_fast_batch_host(device, C.byref(d), out.ctypes.data))
     return out
 
 
 def prob_related_homopolymer(batch: PairBatch, gap: Optional[GapParams] = None, hop: Optional[HopParams] = None, device: int = 0) -> np.ndarray:
     """`homopolymer` mode (HomopolyPairHMMRealigner, realignment/mod.rs:680-730): vlr_realign_homopolymer_batch_host."""
     L = _bind()
-    L.vlr_realign_homopolymer_batch_host.restype = C.c_int
-    L.vlr_realign_homopolymer_batch_host.argtypes = [C.c_int, C.POINTER(RealignDesc), C.POINTER(C.c_double), C.c_void_p]
     gap = gap or GapParams()
     hop = hop or HopParams()
     xo, xb, yo, yb, qb, band = batch.arrays()
     out = np.empty(len(batch), np.float64)
     d = RealignDesc(len(batch), xo.ctypes.data, xb.ctypes.data, yo.ctypes.data, yb.ctypes.data, qb.ctypes.data, band.ctypes.data, gap.as_array())
-    rc = L.vlr_realign_homopolymer_batch_host(device, C.byref(d), hop.as_array(), out.ctypes.data)
-    if rc != 0:
-        raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+    engine.check(L.vlr_realign_homopolymer_batch_host(device, C.byref(d), hop.as_array(), out.ctypes.data))
     return out
 
 
@@ -171,49 +152,35 @@ class DevicePairs:
         gap = gap or GapParams()
         p = [t.data_ptr() for t in self.t]
         d = RealignDesc(self.n, p[0], p[1], p[2], p[3], p[4], p[5], gap.as_array())
-        rc = L.vlr_realign_batch(device, C.byref(d), self.out.data_ptr(), stream)
-        if rc != 0:
-            raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+        engine.check(L.vlr_realign_batch(device, C.byref(d), self.out.data_ptr(), stream))
         return self.out
 
     def run_homopolymer(self, gap: Optional[GapParams] = None, hop: Optional[HopParams] = None, device: int = 0, stream: int = 0):
         L = _bind()
-        L.vlr_realign_homopolymer_batch.restype = C.c_int
-        L.vlr_realign_homopolymer_batch.argtypes = [C.c_int, C.POINTER(RealignDesc), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
         gap = gap or GapParams()
         hop = hop or HopParams()
         p = [t.data_ptr() for t in self.t]
         d = RealignDesc(self.n, p[0], p[1], p[2], p[3], p[4], p[5], gap.as_array())
-        rc = L.vlr_realign_homopolymer_batch(device, C.byref(d), hop.as_array(), self.out.data_ptr(), stream)
-        if rc != 0:
-            raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+        engine.check(L.vlr_realign_homopolymer_batch(device, C.byref(d), hop.as_array(), self.out.data_ptr(), stream))
         return self.out
 
     def run_fast(self, gap: Optional[GapParams] = None, device: int = 0, stream: int = 0):
         """`fast` mode on the resident pairs (vlr_realign_fast_batch; the band is not read)."""
         L = _bind()
-        L.vlr_realign_fast_batch.restype = C.c_int
-        L.vlr_realign_fast_batch.argtypes = [C.c_int, C.POINTER(RealignDesc), C.c_void_p, C.c_void_p]
         gap = gap or GapParams()
         p = [t.data_ptr() for t in self.t]
         d = RealignDesc(self.n, p[0], p[1], p[2], p[3], p[4], None, gap.as_array())
-        rc = L.vlr_realign_fast_batch(device, C.byref(d), self.out.data_ptr(), stream)
-        if rc != 0:
-            raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+        engine.check(L.vlr_realign_fast_batch(device, C.byref(d), self.out.data_ptr(), stream))
         return self.out
 
     def band_from_hits(self, device: int = 0, stream: int = 0):
         """Edit-distance pre-filter on the resident pairs; sets the band of the pair HMM to distance + EDIT_BAND in place."""
         import torch
         L = _bind()
-        L.vlr_edit_distance_batch.restype = C.c_int
-        L.vlr_edit_distance_batch.argtypes = [C.c_int, C.POINTER(RealignDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         p = [t.data_ptr() for t in self.t]
         d = RealignDesc(self.n, p[0], p[1], p[2], p[3], p[4], None, GapParams().as_array())
         dist = torch.empty(self.n, dtype=torch.int32, device=self.t[5].device)
-        rc = L.vlr_edit_distance_batch(device, C.byref(d), dist.data_ptr(), None, None, stream)
-        if rc != 0:
-            raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+        engine.check(L.vlr_edit_distance_batch(device, C.byref(d), dist.data_ptr(), None, None, stream))
         self.t[5].copy_(torch.where(dist >= 0, dist + EDIT_BAND, torch.full_like(dist, -1)))
         return dist
 
@@ -314,8 +281,6 @@ def best_hits(batch: "PairBatch", device: int = 0) -> Tuple[np.ndarray, np.ndarr
     """(dist, end, n_hits) of every pair on the GPU (vlr_edit_distance_batch_host, csrc/vlr_realign.hip): what `best_hit` computes
     for one pair on the host, plus the number of end positions reaching the smallest distance."""
     L = _bind()
-    L.vlr_edit_distance_batch_host.restype = C.c_int
-    L.vlr_edit_distance_batch_host.argtypes = [C.c_int, C.POINTER(RealignDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     n = len(batch)
     dist = np.full(n, -1, np.int32)
     end = np.full(n, -1, np.int32)
@@ -324,9 +289,7 @@ def best_hits(batch: "PairBatch", device: int = 0) -> Tuple[np.ndarray, np.ndarr
         return dist, end, hits
     xo, xb, yo, yb, qb, band = batch.arrays()
     desc = RealignDesc(n, xo.ctypes.data, xb.ctypes.data, yo.ctypes.data, yb.ctypes.data, qb.ctypes.data, None, GapParams().as_array())
-    rc = L.vlr_edit_distance_batch_host(device, C.byref(desc), dist.ctypes.data, end.ctypes.data, hits.ctypes.data)
-    if rc != 0:
-        raise engine.EngineError(rc, (L.vlr_last_error() or b"").decode())
+    engine.check(L.vlr_edit_distance_batch_host(device, C.byref(desc), dist.ctypes.data, end.ctypes.data, hits.ctypes.data))
     return dist, end, hits
 
 
