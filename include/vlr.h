@@ -47,7 +47,8 @@ extern "C" {
                              * 12: vlr_indelpileup_* (indel allele supports from BAM records);
                              * 13: vlr_fragpileup_* (fragment observations of SNV / MNV candidates from BAM records);
                              * 14: vlr_fragpileup_open_realign / _realign_result / _read_realigned (indel-bearing reads over SNV / MNV
-                             *     candidates realigned inside the fragment session) */
+                             *     candidates realigned inside the fragment session); still 14, purely additive: vlr_fragpileup_open_indel /
+                             *     _read_indel (fragments of deletion / insertion candidates in the fragment session) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -815,6 +816,43 @@ int  vlr_fragpileup_open_realign(int device, int64_t n_loci, const int32_t* ref_
                                  int64_t pair_byte_limit, vlr_fragpileup** out);
 int  vlr_fragpileup_realign_result(vlr_fragpileup* s, vlr_fragpileup_realign_counts* out);
 int  vlr_fragpileup_read_realigned(vlr_fragpileup* s, vlr_indelpileup_hit* hits, int64_t n);
+/* Deletion and insertion candidates in the fragment session (deletion.rs:41-85, 158-197, insertion.rs:57-61, 139-157, insert_size.rs:
+ *   17-45; the rule is stated once, at the head of csrc/vlr_fragpileup.h).  vlr_fragpileup_open_indel takes the arguments of
+ *   vlr_fragpileup_open_realign with the loci given as for vlr_indelpileup_open — [start, end) of a deletion (the anchor base and the
+ *   deleted bases but the last) or [start, start + 1) of an insertion, kind VLR_INDELPILEUP_DELETION / _INSERTION, the alt allele
+ *   window of locus k = alt_bases[alt_offset[k] .. alt_offset[k + 1]) — and has_insert_size (do the alignment properties carry an
+ *   insert size?).  A locus longer than VLR_FRAGPILEUP_MAX_INDEL_LEN, an alt window longer than that plus twice the ref window, or
+ *   any other kind is refused at open (VLR_ERR_INVALID_ARGUMENT, the locus named).  The caller gives only deletions whose three fetch
+ *   loci (start, centerpoint, end - 1) merge into one fetch, so that membership is the window test of every session on [start, end).
+ *   Every member of a locus is realigned (the evidences, their places, the gather, the scoring and the write into the members are those
+ *   of vlr_fragpileup_open_realign, with the locus's own alt window); the session also keeps, in arrays only it allocates, a 32-byte side
+ *   record per member (pos, end_pos, the four clip lengths) and per locus the maxima of its members' longest D, longest I and largest
+ *   soft clip / l_seq (integer maxima, a total order: order-independent).  The fragment pass forms one observation per fragment
+ *   with the validity rule of the kind and writes beside it a vlr_fragpileup_indel_obs.  The insert-size support, prob_sample_alt
+ *   and the running maxima of the alignment properties need libm and stay with the caller (varlociraptor_amd/fragments.py).
+ *   vlr_fragpileup_read, vlr_fragpileup_realign_result and vlr_fragpileup_read_realigned work on such a session as on a realigning one.
+ *   NOT mirrored: the read-inferred third allele, alt_variants, homopolymer_indel_len and the prob_observable_at_homopolymer_*
+ *   fields, max_depth subsampling, report_fragment_ids, replacements, SVs, breakends, deletions with more than one fetch.
+ * vlr_fragpileup_read_indel (after vlr_fragpileup_result): n_obs side records parallel to the observations of vlr_fragpileup_read and
+ *   n_loci records of maxima. */
+#define VLR_FRAGPILEUP_MAX_INDEL_LEN 4096
+#define VLR_FRAGPILEUP_INDEL_NONPOSITIVE_ISIZE (1u << 0)   /* insert size <= 0: the assertion of insert_size.rs:38-42 */
+typedef struct {
+    int64_t  insert_size;          /* of a deletion pair in a session with an insert size; 0 = none                                    */
+    uint32_t len_left, len_right;  /* l_seq of the two records (len_right = 0 for a single read)                                       */
+    uint32_t flags;                /* VLR_FRAGPILEUP_INDEL_*                                                                           */
+    uint32_t pad;
+} vlr_fragpileup_indel_obs;
+typedef struct {
+    uint32_t max_del, max_ins;     /* longest D / I operation of the locus's members (0 = none)                                        */
+    uint32_t max_clip, max_clip_l_seq;  /* the largest soft clip / l_seq of the members, as the pair; l_seq = 0: no soft clip          */
+} vlr_fragpileup_indel_locus;
+int  vlr_fragpileup_open_indel(int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int64_t* end, const uint8_t* kind,
+                               const uint64_t* alt_offset, const uint8_t* alt_bases, int64_t window, int max_mapq, int max_read_len,
+                               int64_t member_capacity, int64_t name_capacity, int64_t key_capacity, int64_t window_bytes, const char* fasta_path,
+                               int realign_window, int mode, const double gap[4], const double* hop, int64_t evidence_capacity,
+                               int64_t pair_byte_limit, int has_insert_size, vlr_fragpileup** out);
+int  vlr_fragpileup_read_indel(vlr_fragpileup* s, vlr_fragpileup_indel_obs* extra_obs, int64_t n_obs, vlr_fragpileup_indel_locus* extra_loci, int64_t n_loci);
 
 /* The whole of `varlociraptor filter-calls control-fdr` (/root/reference/src/filtration/fdr.rs:36-158, record typing
  * src/utils/collect_variants.rs:44-304, probability sums and the filtering pass src/utils/mod.rs:169-374): read the calls BCF

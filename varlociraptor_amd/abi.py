@@ -236,6 +236,14 @@ class FragPileupRealignCounts(C.Structure):
                 ("seconds", C.c_double * 4)]
 
 
+# vlr_fragpileup_open_indel / _read_indel (deletion and insertion candidates in the fragment session; additive, ABI stays 14)
+FRAGPILEUP_MAX_INDEL_LEN = 4096
+FRAGPILEUP_INDEL_NONPOSITIVE_ISIZE = 1
+FRAGPILEUP_INDEL_OBS_DTYPE = np.dtype([("insert_size", "<i8"), ("len_left", "<u4"), ("len_right", "<u4"), ("flags", "<u4"), ("pad", "<u4")])
+FRAGPILEUP_INDEL_LOCUS_DTYPE = np.dtype([("max_del", "<u4"), ("max_ins", "<u4"), ("max_clip", "<u4"), ("max_clip_l_seq", "<u4")])
+assert FRAGPILEUP_INDEL_OBS_DTYPE.itemsize == 24 and FRAGPILEUP_INDEL_LOCUS_DTYPE.itemsize == 16
+
+
 class RealignDesc(C.Structure):
     """vlr_realign_batch_desc"""
     _fields_ = [("n_pairs", C.c_int64), ("x_offset", C.c_void_p), ("x_bases", C.c_void_p), ("y_offset", C.c_void_p),
@@ -335,6 +343,9 @@ SIGNATURES = {
                                                                       C.POINTER(C.c_void_p)]),
     "vlr_fragpileup_realign_result": (C.c_int, [C.c_void_p, C.POINTER(FragPileupRealignCounts)]),
     "vlr_fragpileup_read_realigned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "vlr_fragpileup_open_indel": (C.c_int, [C.c_int, C.c_int64] + [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_char_p, C.c_int,
+                                            C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    "vlr_fragpileup_read_indel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     # ---- consumers of a calls file: filter-calls control-fdr / posterior-odds, estimate mutational-burden
     "vlr_calls_filter_fdr": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_double, C.c_uint32, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -179,6 +179,9 @@ def main(argv=None):
                     "--realign-indel-reads such a read is an error)")
     pv.add_argument("--realign-indel-reads", action="store_true",
                     help="realign a read with an insertion or deletion against the ref and the alt allele, as the reference does by default")
+    pv.add_argument("--indel-candidates", action="store_true",
+                    help="build deletion and insertion candidates too, one observation per fragment with the insert-size support of a deletion "
+                    "(without it such a candidate is an error)")
     pv.add_argument("--indel-window", type=int, default=64, help="bases of a read realigned on either side of the candidate (at most 64, cli.rs:877)")
     pv.add_argument("--pairhmm-mode", choices=["exact", "fast", "homopolymer"], default="exact")
     pv.add_argument("--device", default="0", help="HIP device index, or 'cpu' for the Python restatement")
@@ -195,7 +198,8 @@ def main(argv=None):
             n = fragments.preprocess_variants(a.reference, a.candidates, a.bam, a.output, a.alignment_properties, "cpu" if a.device == "cpu" else int(a.device),
                                               a.atomic_candidate_variants, a.omit_mapq_adjustment, a.max_depth, a.score_indel_reads_from_alignment,
                                               warn=lambda m: print(f"[WARN] {m}", file=sys.stderr),
-                                              realign=fragments.RealignSpec(a.indel_window, a.pairhmm_mode) if a.realign_indel_reads else None)
+                                              realign=fragments.RealignSpec(a.indel_window, a.pairhmm_mode) if a.realign_indel_reads else None,
+                                              indel_candidates=fragments.RealignSpec(a.indel_window, a.pairhmm_mode) if a.indel_candidates else None)
         except (fragments.PreprocessError, fragments.FragPileupError, fragments.InvalidReadOrientationInfo, fragments.EngineError) as e:
             print(f"error: {e}", file=sys.stderr)
             sys.exit(1)

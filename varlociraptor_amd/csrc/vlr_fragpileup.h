@@ -29,6 +29,31 @@
 //                            CIGAR that begins with N (read_pos fails) and a record with an SI:Z tag (strand information over an
 //                            interval, mod.rs:381-387).  A region without overlap or with an empty read window gives ln 0.5 / ln 0.5
 //                            (mod.rs:186-199).
+//   indel candidates         (an indel session, vlr_fragpileup_open_indel) deletion.rs:41-85, 158-197, insertion.rs:57-61, 139-157,
+//                            Realigner::allele_support (mod.rs:161-424), insert_size.rs:17-45.  A locus is [start, end) of a deletion
+//                            (REF longer than one base, ALT its first base: end - start deleted bases behind the anchor) or
+//                            [start, start + 1) of an insertion, its alt allele window computed by the caller as for
+//                            vlr_indelpileup_open (deletion.rs:120-141, insertion.rs:73-99).  A deletion is fetched at `start`,
+//                            centerpoint = start + round(len / 2) (f64::round: half away from zero, `centerpoint`) and end - 1; only
+//                            deletions whose three fetch loci merge into one fetch are given to a session (the caller refuses the
+//                            others), so membership is the window test above on [start, end).  EVERY member of an indel locus is
+//                            realigned (`realign_evidence` with the locus's own alt window; no overlap or an empty read window gives
+//                            ln 0.5 / ln 0.5, strand none, VLR_INDELPILEUP_HIT_NO_OVERLAP); a CIGAR that begins with N and an SI:Z tag
+//                            are refused as above.  A member carries M_OVERLAPS when SingleLocus::overlap(r, true, 0, 0) != None
+//                            (vlr_ip::overlaps: with soft clips, on [start, end)) and a Side record beside it (pos, end_pos, the four
+//                            clip lengths).  A fragment is valid (`make_obs_indel`): a single read when it overlaps; an insertion pair,
+//                            or a deletion pair of a session without an insert size, when either read overlaps; a deletion pair with
+//                            an insert size when left.pos < centerpoint && right.end_pos > centerpoint AND either read overlaps.  Its
+//                            support is AlleleSupport::merge(left, right) (read position none, third allele 0); an observation exists
+//                            only for a merged strand other than none (read_observation.rs:638-646) — the insert-size term, which
+//                            the host adds (it needs libm), has strand none and never decides that.  `insert_size` (insert_size.rs:
+//                            17-45): per read (pos - leading soft - leading hard, saturating at 0; end_pos + trailing soft + trailing
+//                            hard), inner distance + both spans; a value <= 0 is the reference's assertion and comes back flagged.
+//                            `cigar_maxima`: the longest D, the longest I and the largest soft clip of a record, which the reference
+//                            folds into the alignment properties while it reads (mod.rs:310, alignment_properties.rs:94-144).
+//                            NOT mirrored: the read-inferred third allele, alt_variants, homopolymer_indel_len and the two
+//                            prob_observable_at_homopolymer_* fields (the Myers traceback of the bio crate), max_depth subsampling,
+//                            report_fragment_ids, replacements, SVs, breakends, deletions with more than one fetch.
 // varlociraptor_amd/fragments.py is the same in Python.
 //
 // Bounds: `features` runs only on a record vlr_bp::decode accepted, so the fixed head, the name (l_read_name bytes behind the head) and
@@ -47,7 +72,7 @@ using vlr_bp::Rec;
 
 enum { ORIENT_INVALID = 255 };
 // bits of Member::bits
-enum { M_SOFTCLIPPED = 1, M_HAS_XA = 2, M_ENCLOSING = 4, M_HAS_SUPPORT = 8 };
+enum { M_SOFTCLIPPED = 1, M_HAS_XA = 2, M_ENCLOSING = 4, M_HAS_SUPPORT = 8, M_OVERLAPS = 16 };   // (M_OVERLAPS: an indel session)
 
 // one alt locus of a record: the key the mode is taken over
 struct AltKey { uint64_t contig_hash, bucket; };
@@ -66,6 +91,67 @@ struct Member {
     uint8_t name_len, mapq, orientation, strand, bits, status;
     uint32_t xa_n;
 };
+
+// what an indel session keeps beside a member (parallel to the members; the 72 bytes of a Member stay): the alignment and its clips
+struct Side {
+    int64_t pos, end_pos;
+    uint32_t lead_soft, lead_hard, trail_soft, trail_hard;   // rust-htslib's leading_softclips / leading_hardclips / trailing_*
+};
+
+// what the member pass of an indel session knows beyond the loci: how long a locus can be (first_candidate) and where the Side records
+// of the record's members go (parallel to `out` of record_members; nullptr in the count pass)
+struct Indel {
+    int64_t max_locus_len;
+    Side* side;
+};
+
+// Deletion::centerpoint (deletion.rs:45): start + (len as f64 / 2.0).round(), half away from zero
+VLR_BP_HD inline int64_t centerpoint(int64_t start, int64_t len) { return start + (len + 1) / 2; }
+
+// the clips of insert_size.rs:21-28: a soft clip counts at an end when it is the outermost operation or lies behind one hard clip
+VLR_BP_HD inline Side side_of(const Rec& r) {
+    Side s = {r.pos, r.end_pos, 0u, 0u, 0u, 0u};
+    const uint8_t* c = r.p + r.cig_off;
+    const uint32_t n = r.n_cigar;
+    if (n == 0) return s;
+    uint32_t v = ld32(c);
+    if ((v & 15u) == 5u) { s.lead_hard = v >> 4; v = n > 1 ? ld32(c + 4) : 0u; }
+    if ((v & 15u) == 4u) s.lead_soft = v >> 4;
+    v = ld32(c + 4u * (n - 1));
+    if ((v & 15u) == 5u) { s.trail_hard = v >> 4; v = n > 1 ? ld32(c + 4u * (n - 2)) : 0u; }
+    if ((v & 15u) == 4u) s.trail_soft = v >> 4;
+    return s;
+}
+
+// estimate_insert_size (insert_size.rs:17-45) as written: inner mate distance + both spans; <= 0 is the reference's assertion
+VLR_BP_HD inline int64_t insert_size(const Side& l, const Side& r) {
+    const int64_t lc = (int64_t)l.lead_soft + (int64_t)l.lead_hard, rc = (int64_t)r.lead_soft + (int64_t)r.lead_hard;
+    const int64_t ls = l.pos > lc ? l.pos - lc : 0, rs = r.pos > rc ? r.pos - rc : 0;
+    const int64_t le = l.end_pos + (int64_t)l.trail_soft + (int64_t)l.trail_hard, re = r.end_pos + (int64_t)r.trail_soft + (int64_t)r.trail_hard;
+    return (rs - le) + (le - ls) + (re - rs);
+}
+
+// update_max_cigar_ops_len (alignment_properties.rs:94-144) of one record: its longest D, its longest I, its largest S
+VLR_BP_HD inline void cigar_maxima(const Rec& r, uint32_t* max_del, uint32_t* max_ins, uint32_t* max_clip) {
+    *max_del = 0; *max_ins = 0; *max_clip = 0;
+    for (uint32_t i = 0; i < r.n_cigar; ++i) {
+        const uint32_t v = ld32(r.p + r.cig_off + 4u * i), op = v & 15u, l = v >> 4;
+        if (op == 2u && l > *max_del) *max_del = l;
+        if (op == 1u && l > *max_ins) *max_ins = l;
+        if (op == 4u && l > *max_clip) *max_clip = l;
+    }
+}
+
+// the order of the soft-clip fractions clip / l_seq, packed (clip << 32 | l_seq): by the fraction (exact in integers: a CIGAR length
+// is below 2^28 and l_seq below 2^32, so the products fit 64 bits), then by the clip — a total order, so the maximum of a set does not
+// depend on the order it is taken in.  l_seq == 0 (no fraction) is the least element.
+VLR_BP_HD inline bool clip_frac_greater(uint64_t a, uint64_t b) {
+    const uint64_t ac = a >> 32, al = a & 0xffffffffull, bc = b >> 32, bl = b & 0xffffffffull;
+    if (al == 0) return false;
+    if (bl == 0) return true;
+    const uint64_t x = ac * bl, y = bc * al;
+    return x != y ? x > y : ac > bc;
+}
 
 struct Feat {
     int32_t mtid;
@@ -198,8 +284,9 @@ VLR_BP_HD inline void features(const Rec& r, uint64_t size, Feat& f) {
 }
 
 // the loci of which a record starting at (ref_id, pos) is a member: [first, ...) while member_of says so
-VLR_BP_HD inline int64_t first_candidate(const vlr_bp::Loci& L, int32_t ref_id, int64_t pos) {
-    return vlr_bp::lower_bound(L, ref_id, pos - (int64_t)VLR_BASEPILEUP_MAX_LEN + 1);
+// (max_len: the longest locus of the session — VLR_BASEPILEUP_MAX_LEN for SNVs / MNVs, an indel session's own)
+VLR_BP_HD inline int64_t first_candidate(const vlr_bp::Loci& L, int32_t ref_id, int64_t pos, int64_t max_len = VLR_BASEPILEUP_MAX_LEN) {
+    return vlr_bp::lower_bound(L, ref_id, pos - max_len + 1);
 }
 VLR_BP_HD inline bool in_reach(const vlr_bp::Loci& L, int64_t li, int32_t ref_id, int64_t pos, int64_t window) {
     return li < L.n && L.ref_id[li] == ref_id && L.start[li] - window <= pos;
@@ -214,6 +301,7 @@ struct RecMembers {
     vlr_bp::RecClass cls;
     uint32_t n_ev, x_bytes, y_bytes;   // a realigning pass: the record's evidences and the bytes of their pairs (allele windows; read windows, twice)
     uint32_t seq_off, qual_off, l_seq; // of an accepted record: where its packed SEQ and its QUAL start
+    uint32_t max_del, max_ins, max_clip;   // an indel session: cigar_maxima of a record that is a member of any locus
 };
 
 // what a realigning pass knows beyond the loci: --indel-window and the contigs of the BAM header (-1: not loaded, no locus lies on it)
@@ -236,9 +324,10 @@ VLR_BP_HD inline uint8_t alt_window_byte(const vlr_bp::Loci& L, int64_t li, cons
 }
 
 // The evidence of a record that needs realignment at locus li: the windows of its candidate region, or a status.  *x_bytes / *y_bytes:
-// the bytes of its two pairs.
+// the bytes of its two pairs.  own_alt_window: an indel session, whose loci bring their alt allele windows
+// (alt_bases[base_off[li] .. base_off[li + 1])).
 VLR_BP_HD inline vlr_indelpileup_hit realign_evidence(const Realign& ra, const vlr_bp::Loci& L, int64_t li, const Rec& r, uint64_t ordinal, uint32_t* x_bytes,
-                                                      uint32_t* y_bytes) {
+                                                      uint32_t* y_bytes, bool own_alt_window = false) {
     vlr_indelpileup_hit h;
     h.ln_ref = 0.0; h.ln_alt = 0.0;
     h.record = ordinal;
@@ -259,8 +348,9 @@ VLR_BP_HD inline vlr_indelpileup_hit realign_evidence(const Realign& ra, const v
     else if (r.has_si) h.status = VLR_INDELPILEUP_HIT_STRAND_INFO;
     else if (!g.overlap || g.read_end - g.read_begin < 1) h.status = VLR_INDELPILEUP_HIT_NO_OVERLAP;
     else {
-        int64_t ab, ae;
-        alt_window(L, li, contig_len, ra.window, &ab, &ae);
+        int64_t ab = 0, ae = 0;
+        if (own_alt_window) ae = (int64_t)(L.base_off[li + 1] - L.base_off[li]);
+        else alt_window(L, li, contig_len, ra.window, &ab, &ae);
         h.ref_begin = g.ref_begin;
         h.ref_len = (uint32_t)(g.ref_end - g.ref_begin);
         h.read_begin = (uint32_t)g.read_begin;
@@ -277,20 +367,52 @@ VLR_BP_HD inline vlr_indelpileup_hit realign_evidence(const Realign& ra, const v
 VLR_BP_HD inline RecMembers record_members(const vlr_bp::Tables& t, const vlr_bp::Loci& L, const uint8_t* p, uint64_t size, uint64_t ordinal,
                                            bool realign_indel_reads, int64_t window, uint64_t coeff, Member* out, uint64_t room, uint64_t name_off, uint8_t* name_dst,
                                            uint64_t xa_off, AltKey* xa_dst, uint64_t xa_room, const Realign* ra = nullptr, vlr_indelpileup_hit* ev_out = nullptr,
-                                           uint64_t ev_room = 0) {
-    RecMembers res = {0u, 0u, 0u, vlr_bp::REC_OK, 0u, 0u, 0u, 0u, 0u, 0u};
+                                           uint64_t ev_room = 0, const Indel* ia = nullptr) {
+    RecMembers res = {0u, 0u, 0u, vlr_bp::REC_OK, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     Rec r;
     res.cls = vlr_bp::decode(p, size, r);
     if (res.cls != vlr_bp::REC_OK || r.ref_id < 0 || r.pos < 0) return res;
     res.seq_off = r.seq_off; res.qual_off = r.qual_off; res.l_seq = r.l_seq;
     Feat f;
     bool have_f = false;
-    for (int64_t li = first_candidate(L, r.ref_id, r.pos); in_reach(L, li, r.ref_id, r.pos, window); ++li) {
+    const int64_t max_len = ia != nullptr ? ia->max_locus_len : (int64_t)VLR_BASEPILEUP_MAX_LEN;
+    for (int64_t li = first_candidate(L, r.ref_id, r.pos, max_len); in_reach(L, li, r.ref_id, r.pos, window); ++li) {
         if (!member_of(L, li, r.pos, window)) continue;
         if (!have_f) {
             features(r, size, f);
             have_f = true;
             if (f.has_xa) res.n_xa = xa_keys(p + f.xa_off, f.xa_len, coeff, xa_dst, xa_room);
+            if (ia != nullptr) cigar_maxima(r, &res.max_del, &res.max_ins, &res.max_clip);
+        }
+        if (ia != nullptr && ra != nullptr) {   // an indel locus: every member is realigned; no base-by-base score, no enclosing rule
+            uint32_t xb, yb;
+            const vlr_indelpileup_hit h = realign_evidence(*ra, L, li, r, ordinal, &xb, &yb, true);
+            if (ev_out != nullptr && (uint64_t)res.n_ev < ev_room) ev_out[res.n_ev] = h;
+            ++res.n_ev; res.x_bytes += xb; res.y_bytes += yb;
+            if (out != nullptr && (uint64_t)res.n_members < room) {
+                Member m;
+                m.prob_ref = 0.0; m.prob_alt = 0.0;
+                m.ordinal = ordinal;
+                m.name_off = name_off;
+                m.xa_off = xa_off;
+                m.xa_n = res.n_xa;
+                m.locus = (uint32_t)li;
+                m.read_position = VLR_BASEPILEUP_NO_READ_POSITION;
+                m.third_allele = 0;
+                m.l_seq = r.l_seq;
+                m.flag = (uint16_t)r.flag;
+                m.name_len = (uint8_t)f.name_len;
+                m.mapq = (uint8_t)r.mapq;
+                m.orientation = f.orientation;
+                m.strand = vlr_bp::STRAND_NONE;
+                m.bits = (uint8_t)((f.softclipped ? M_SOFTCLIPPED : 0) | (f.has_xa ? M_HAS_XA : 0) | M_HAS_SUPPORT |
+                                   (vlr_ip::overlaps(r, L.start[li], L.start[li] + (int64_t)L.len[li]) ? M_OVERLAPS : 0));
+                m.status = VLR_BASEPILEUP_HIT_NEEDS_REALIGN;   // (until apply_realigned writes the evidence into it)
+                out[res.n_members] = m;
+                if (ia->side != nullptr) ia->side[res.n_members] = side_of(r);
+            }
+            ++res.n_members;
+            continue;
         }
         // SingleLocus::overlap(read, false, 0, 0) == Enclosing
         const bool enclosing = r.pos <= L.start[li] && r.end_pos >= L.start[li] + (int64_t)L.len[li];
@@ -388,6 +510,40 @@ VLR_BP_HD inline bool skipped_as_partial(const Member& left, const Member& rec) 
 
 VLR_BP_HD inline bool is_alt_support(double pr, double pa) { return pa > pr; }
 
+// the end of make_obs below, for make_obs_indel (make_obs keeps its own text, so that the kernels of the other sessions compile to the
+// code they had): the status / strand rule (read_observation.rs:638-646) and the features of the fragment
+VLR_BP_HD inline bool finish_obs(const Member& l, const Member* r, double pr, double pa, uint32_t pos, uint32_t strand, uint32_t third, uint32_t status,
+                                 uint32_t max_mapq, vlr_fragpileup_obs& o) {
+    if (status != 0) { pr = 0.0; pa = 0.0; pos = VLR_BASEPILEUP_NO_READ_POSITION; strand = vlr_bp::STRAND_NONE; third = 0; }
+    else if (strand == vlr_bp::STRAND_NONE) return false;
+    uint32_t orient = l.orientation;
+    if (r != nullptr) {
+        if (l.orientation == ORIENT_INVALID || r->orientation == ORIENT_INVALID) orient = ORIENT_INVALID;
+        else if (l.orientation != r->orientation) orient = VLR_FRAG_ORIENT_NONE;
+    }
+    if (orient == ORIENT_INVALID) { status |= VLR_FRAGPILEUP_OBS_INVALID_RO; orient = VLR_FRAG_ORIENT_NONE; }
+    const uint32_t min_mapq = r != nullptr && r->mapq < l.mapq ? r->mapq : l.mapq;
+    uint32_t bits = 0;
+    if ((l.bits & M_SOFTCLIPPED) || (r != nullptr && (r->bits & M_SOFTCLIPPED))) bits |= VLR_FRAGPILEUP_SOFTCLIPPED;
+    if (l.flag & 0x1u) bits |= VLR_FRAGPILEUP_PAIRED;
+    if (min_mapq == max_mapq) bits |= VLR_FRAGPILEUP_MAX_MAPQ;
+    if ((l.bits & M_HAS_XA) || (r != nullptr && (r->bits & M_HAS_XA))) bits |= VLR_FRAGPILEUP_HAS_XA;
+    o.prob_ref = pr; o.prob_alt = pa;
+    o.left = l.ordinal;
+    o.right = r != nullptr ? r->ordinal : VLR_FRAGPILEUP_NO_RECORD;
+    o.read_position = pos;
+    o.third_allele = third;
+    o.len_sum = l.l_seq + (r != nullptr ? r->l_seq : 0u);
+    o.min_mapq = (uint8_t)min_mapq;
+    o.orientation = (uint8_t)orient;
+    o.strand = (uint8_t)strand;
+    o.bits = (uint8_t)bits;
+    o.status = (uint8_t)status;
+    o.alt_locus = VLR_ALTLOCUS_NONE;   // (set once the locus' major alt locus is known)
+    for (int k = 0; k < 6; ++k) o.pad[k] = 0;
+    return true;
+}
+
 // The observation of a fragment (`right` may be null): false = none (the pair is ambiguous, no record encloses the locus, no support,
 // or the merged strand is None).
 VLR_BP_HD inline bool make_obs(const Member& l, const Member* r, uint32_t max_mapq, vlr_fragpileup_obs& o) {
@@ -441,7 +597,55 @@ VLR_BP_HD inline bool make_obs(const Member& l, const Member* r, uint32_t max_ma
     return true;
 }
 
-// The fragment of the run of equal names that begins at sorted position i (idx[i .. n), members M): its observation, if any.
+// The observation of a fragment of an indel locus (an indel session; the head of this file has the rule).  sl / sr: the Side records
+// of the two members; x: the insert size (0 = none), the two read lengths, VLR_FRAGPILEUP_INDEL_* flags.
+VLR_BP_HD inline bool make_obs_indel(const Member& l, const Member* r, const Side& sl, const Side* sr, uint32_t kind, int64_t locus_start, int64_t locus_len,
+                                     bool has_insert_size, uint32_t max_mapq, vlr_fragpileup_obs& o, vlr_fragpileup_indel_obs& x) {
+    const bool with_isize = r != nullptr && sr != nullptr && kind == VLR_INDELPILEUP_DELETION && has_insert_size;
+    if (r != nullptr) {
+        if (l.mapq == 0 || r->mapq == 0) return false;
+        if (!(l.bits & M_OVERLAPS) && !(r->bits & M_OVERLAPS)) return false;
+        if (with_isize) {
+            const int64_t c = centerpoint(locus_start, locus_len);
+            if (!(sl.pos < c && sr->end_pos > c)) return false;
+        }
+    } else if (!(l.bits & M_OVERLAPS)) return false;
+    double pr = l.prob_ref, pa = l.prob_alt;
+    uint32_t strand = l.strand, status = l.status;
+    if (r != nullptr) {   // AlleleSupport::merge: *r into l (no read positions, no third-allele evidence)
+        pr += r->prob_ref; pa += r->prob_alt;
+        if (strand == vlr_bp::STRAND_NONE) strand = r->strand;
+        else if (r->strand != vlr_bp::STRAND_NONE && strand != r->strand) strand = vlr_bp::STRAND_BOTH;
+        status |= r->status;
+    }
+    if (!finish_obs(l, r, pr, pa, VLR_BASEPILEUP_NO_READ_POSITION, strand, 0u, status, max_mapq, o)) return false;
+    x.insert_size = 0;
+    x.len_left = l.l_seq;
+    x.len_right = r != nullptr ? r->l_seq : 0u;
+    x.flags = 0; x.pad = 0;
+    if (with_isize) {
+        x.insert_size = insert_size(sl, *sr);
+        if (x.insert_size <= 0) x.flags |= VLR_FRAGPILEUP_INDEL_NONPOSITIVE_ISIZE;
+    }
+    return true;
+}
+
+// The pair of the run of equal names that begins at sorted position i (idx[i .. n), members M; mod.rs:325-338): the first member is
+// `left`, every later one replaces `right` unless both are first AND last in template; *right_member = 0xffffffff for a single read
+template <class Index>
+VLR_BP_HD inline void run_pair(const Member* M, const uint8_t* names, const Index* idx, uint32_t i, uint32_t n, uint32_t* left_member, uint32_t* right_member) {
+    const Member& left = M[idx[i]];
+    *left_member = (uint32_t)idx[i];
+    *right_member = 0xffffffffu;
+    for (uint32_t j = i + 1; j < n; ++j) {
+        const Member& rec = M[idx[j]];
+        if (compare_names(names, left, rec) != 0) break;
+        if (skipped_as_partial(left, rec)) continue;
+        *right_member = (uint32_t)idx[j];
+    }
+}
+
+// The fragment of that run: its observation, if any (the loop of run_pair, as it always stood here).
 template <class Index>
 VLR_BP_HD inline bool run_obs(const Member* M, const uint8_t* names, const Index* idx, uint32_t i, uint32_t n, uint32_t max_mapq, vlr_fragpileup_obs& o,
                               uint32_t* left_member, uint32_t* right_member) {
@@ -457,6 +661,17 @@ VLR_BP_HD inline bool run_obs(const Member* M, const uint8_t* names, const Index
         *right_member = (uint32_t)idx[j];
     }
     return make_obs(left, right, max_mapq, o);
+}
+
+// the same for an indel locus (S: the Side records parallel to M)
+template <class Index>
+VLR_BP_HD inline bool run_obs_indel(const Member* M, const Side* S, const uint8_t* names, const Index* idx, uint32_t i, uint32_t n, uint32_t kind, int64_t locus_start,
+                                    int64_t locus_len, bool has_insert_size, uint32_t max_mapq, vlr_fragpileup_obs& o, vlr_fragpileup_indel_obs& x,
+                                    uint32_t* left_member, uint32_t* right_member) {
+    run_pair(M, names, idx, i, n, left_member, right_member);
+    const bool pair = *right_member != 0xffffffffu;
+    return make_obs_indel(M[*left_member], pair ? &M[*right_member] : nullptr, S[*left_member], pair ? &S[*right_member] : nullptr, kind, locus_start, locus_len,
+                          has_insert_size, max_mapq, o, x);
 }
 
 // does this observation's read position count for major_read_position (read_observation.rs:549-559)?

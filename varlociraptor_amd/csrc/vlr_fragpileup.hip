@@ -37,6 +37,14 @@
 //   frag_apply_kernel          one evidence per thread: vlr_fp::apply_realigned writes the supports into the member and clears the flag
 // An evidence's place is a prefix sum over the record order; the ranges only decide which launch scores a pair, not its bytes.
 //
+// An indel session (vlr_fragpileup_open_indel) is a realigning session whose loci are deletions / insertions with their own alt allele
+// windows: the indel kernels of the count and fill bodies (frag_count_indel_kernel, frag_fill_indel_kernel) take the indel arm of vlr_fp::record_members (every member an evidence,
+// the overlap bit, a Side record per member at sides[member], first_candidate bounded by the session's longest locus), the fill kernel
+// folds the record's CIGAR maxima into its loci (atomic maxima over a total order: order-independent, they decide no place), the gather
+// kernel is instantiated with IndelAltWindows, and frag_locus_indel_kernel / frag_gather_indel_kernel apply the validity
+// rule of the locus's kind (vlr_fp::make_obs_indel) and carry a vlr_fragpileup_indel_obs beside each observation.  The arrays are
+// allocated by such a session alone; the other kernels keep the signatures every session had before (the bodies are shared templates).
+//
 // LDS of frag_locus_kernel: 4 B index + 2 B rank per member + 2 KiB of scan cells = 26 KiB at VLR_FRAGPILEUP_MAX_MEMBERS = 4096, six
 // workgroups per CU by LDS.
 // Bounds: a record is read only after vlr_bp::decode checked it; members[k] is written for k < member capacity, names[k] for
@@ -55,6 +63,9 @@ static_assert(sizeof(vlr_fragpileup_obs) == 56, "observation layout");
 static_assert(sizeof(vlr_fragpileup_locus) == 24, "locus record layout");
 static_assert(sizeof(vlr_fp::Member) == 72, "member layout");
 static_assert(sizeof(vlr_fp::AltKey) == 16, "key layout");
+static_assert(sizeof(vlr_fp::Side) == 32, "side record layout");
+static_assert(sizeof(vlr_fragpileup_indel_obs) == 24, "indel side record layout");
+static_assert(sizeof(vlr_fragpileup_indel_locus) == 16, "indel locus record layout");
 
 namespace vlr_fp {
 
@@ -80,6 +91,30 @@ struct EvFill {
     uint32_t* member;                       // [cap] the member of an evidence
     uint64_t *gx, *gy;                      // [2 * cap + 1] session-wide offsets of the pairs
     vlr_ip::Src* src;                       // [n_ev] chunk-local
+};
+
+// what the fill kernel of an indel session needs beyond that (on = false: every other session)
+struct IndelFill {
+    bool on;
+    int64_t max_locus_len;
+    uint64_t member_cap;
+    Side* sides;                            // [member_cap] parallel to the members
+    uint32_t *max_del, *max_ins;            // [n_loci]
+    unsigned long long* max_clip;           // [n_loci] clip << 32 | l_seq (vlr_fp::clip_frac_greater)
+};
+
+// the windows of an indel candidate's evidence in the fragment session: the alt allele window is the locus's own (vlr_bp::Loci::alt_bases
+// at base_off), computed by the caller as for vlr_indelpileup_open
+struct IndelAltWindows {
+    vlr_bp::Loci L;
+    const uint8_t* const* ctg;
+    Realign ra;
+    __device__ int64_t n_loci() const { return L.n; }
+    __device__ int32_t ref_id(uint32_t locus) const { return L.ref_id[locus]; }
+    __device__ const uint8_t* contig(int32_t ref_id) const { return ctg[ref_id]; }
+    __device__ int64_t contig_len(int32_t ref_id) const { return ra.ctg_len[ref_id]; }
+    __device__ uint32_t alt_len(uint32_t locus, int64_t) const { return (uint32_t)(L.base_off[locus + 1] - L.base_off[locus]); }
+    __device__ uint8_t alt_byte(uint32_t locus, const uint8_t*, int64_t, uint32_t k) const { return L.alt_bases[L.base_off[locus] + k]; }
 };
 
 // the windows of a realigned SNV / MNV evidence: the alt allele window is the contig with the locus bytes replaced (vlr_fp::alt_window)
@@ -109,18 +144,20 @@ __global__ __launch_bounds__(kThreads) void frag_apply_kernel(const vlr_indelpil
     apply_realigned(members[m], hits[e], norm[2 * e], norm[2 * e + 1]);
 }
 
-// kRealign: the instance of a realigning session; the other instance is the kernel every session had before
-template <bool kRealign>
-__global__ __launch_bounds__(kThreads) void frag_count_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
+// The bodies of the member pass.  kRealign: a realigning session; kIndel (with kRealign): an indel session.  The kernels below keep the
+// signatures and names every session had before; the indel session has kernels of its own with the arguments only it needs.
+template <bool kRealign, bool kIndel>
+__device__ __forceinline__ void frag_count_body(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
                                                               vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
                                                               uint32_t* __restrict__ cnt, uint32_t* __restrict__ nbytes, uint32_t* __restrict__ nxa,
                                                               unsigned long long* __restrict__ counters, Realign ra, uint32_t* __restrict__ nev,
-                                                              uint32_t* __restrict__ nxb, uint32_t* __restrict__ nyb) {
+                                                              uint32_t* __restrict__ nxb, uint32_t* __restrict__ nyb, int64_t max_locus_len) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t o = starts[i], end = starts[i + 1];
+    const Indel ia{max_locus_len, nullptr};
     const RecMembers r = record_members(t, L, base + o, end - o, rec0 + (uint64_t)i, realign != 0, window, coeff, nullptr, 0, 0, nullptr, 0, nullptr, 0,
-                                        kRealign ? &ra : nullptr);
+                                        kRealign ? &ra : nullptr, nullptr, 0, kIndel ? &ia : nullptr);
     cnt[i] = r.n_members;
     nbytes[i] = r.name_bytes;
     nxa[i] = r.n_xa;
@@ -129,13 +166,13 @@ __global__ __launch_bounds__(kThreads) void frag_count_kernel(const uint8_t* __r
     if (r.cls == vlr_bp::REC_BAD) { atomicAdd(&counters[C_BAD], 1ull); atomicMin(&counters[C_FIRST_BAD], (unsigned long long)(rec0 + (uint64_t)i)); }
 }
 
-template <bool kRealign>
-__global__ __launch_bounds__(kThreads) void frag_fill_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
+template <bool kRealign, bool kIndel>
+__device__ __forceinline__ void frag_fill_body(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
                                                              vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
                                                              const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ nbytes, const uint64_t* __restrict__ off,
                                                              const uint64_t* __restrict__ noff, const uint64_t* __restrict__ xoff, uint64_t member0, uint64_t member_cap,
                                                              uint64_t name0, uint64_t name_cap, uint64_t key0, uint64_t key_cap, Member* __restrict__ members,
-                                                             uint8_t* __restrict__ names, AltKey* __restrict__ keys, uint32_t* __restrict__ locus_cnt, EvFill ev) {
+                                                             uint8_t* __restrict__ names, AltKey* __restrict__ keys, uint32_t* __restrict__ locus_cnt, EvFill ev, IndelFill in) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     // the end of the chunk's pairs, for the last evidence's windows (index 2 * (ev0 + n_ev) <= 2 * capacity: the arrays hold one more)
     if (kRealign && i == 0 && ev.on) { ev.gx[2 * (ev.ev0 + ev.n_ev)] = ev.x0 + ev.x_bytes; ev.gy[2 * (ev.ev0 + ev.n_ev)] = ev.y0 + ev.y_bytes; }
@@ -151,17 +188,24 @@ __global__ __launch_bounds__(kThreads) void frag_fill_kernel(const uint8_t* __re
     // (a realigning fill runs only when every member and every evidence of the chunk fits its buffer)
     const uint64_t e_first = kRealign && ev.on ? ev.ev0 + ev.eoff[i] : 0;
     const uint64_t e_room = kRealign && ev.on && e_first < ev.cap ? ev.cap - e_first : 0;
+    // (first < member_cap == in.member_cap: the Side records of the record's members lie at sides[first ...) below the same room)
+    const Indel ia{in.max_locus_len, kIndel && in.on && first < in.member_cap ? in.sides + first : nullptr};
+    // an indel session realigns every member: its record_members takes the indel arm only with the Realign (ev.on); without it (an
+    // overflow: nothing more is kept) the members are not written either
+    if (kIndel && !(ev.on && in.on)) return;
     const RecMembers r = record_members(t, L, base + o, end - o, rec0 + (uint64_t)i, realign != 0, window, coeff, members + first, room, name_at, name_dst, key_at,
-                                        key_room ? keys + key_at : nullptr, key_room, kRealign && ev.on ? &ev.ra : nullptr, e_room ? ev.hits + e_first : nullptr, e_room);
+                                        key_room ? keys + key_at : nullptr, key_room, kRealign && ev.on ? &ev.ra : nullptr, e_room ? ev.hits + e_first : nullptr, e_room,
+                                        kIndel ? &ia : nullptr);
     const uint64_t written = std::min<uint64_t>(r.n_members, room);
     if (kRealign && e_room) {   // the evidences of the record: their members, the offsets of their pairs, where their read windows come from
         uint64_t x = ev.x0 + ev.xoff[i], y = ev.y0 + ev.yoff[i], e = 0;
         for (uint64_t k = 0; k < written && e < r.n_ev && e < e_room && ev.eoff[i] + e < ev.n_ev; ++k) {
             const Member& m = members[first + k];
-            if (!(m.bits & M_ENCLOSING) || !(m.status & VLR_BASEPILEUP_HIT_NEEDS_REALIGN)) continue;
+            if (!kIndel && (!(m.bits & M_ENCLOSING) || !(m.status & VLR_BASEPILEUP_HIT_NEEDS_REALIGN))) continue;
             const vlr_indelpileup_hit h = ev.hits[e_first + e];
             uint64_t alt = 0;
-            if (!h.status) { int64_t ab, ae; alt_window(L, (int64_t)h.locus, ev.ra.ctg_len[L.ref_id[h.locus]], ev.ra.window, &ab, &ae); alt = (uint64_t)(ae - ab); }
+            if (kIndel) { if (!h.status && (int64_t)h.locus < L.n) alt = L.base_off[h.locus + 1] - L.base_off[h.locus]; }
+            else if (!h.status) { int64_t ab, ae; alt_window(L, (int64_t)h.locus, ev.ra.ctg_len[L.ref_id[h.locus]], ev.ra.window, &ab, &ae); alt = (uint64_t)(ae - ab); }
             const uint64_t pr = 2 * (e_first + e);
             ev.member[e_first + e] = (uint32_t)(first + k);
             ev.gx[pr] = x; x += h.ref_len;
@@ -175,7 +219,58 @@ __global__ __launch_bounds__(kThreads) void frag_fill_kernel(const uint8_t* __re
     for (uint64_t k = 0; k < written; ++k) {
         const uint32_t li = members[first + k].locus;
         if ((int64_t)li < L.n) atomicAdd(&locus_cnt[li], 1u);
+        if (kIndel && in.on && (int64_t)li < L.n) {   // the record's CIGAR maxima into the locus: maxima over total orders
+            if (r.max_del) atomicMax(&in.max_del[li], r.max_del);
+            if (r.max_ins) atomicMax(&in.max_ins[li], r.max_ins);
+            if (r.max_clip && r.l_seq) {
+                const unsigned long long mine = ((unsigned long long)r.max_clip << 32) | (unsigned long long)r.l_seq;
+                unsigned long long seen = in.max_clip[li];
+                while (clip_frac_greater(mine, seen)) {
+                    const unsigned long long was = atomicCAS(&in.max_clip[li], seen, mine);
+                    if (was == seen) break;
+                    seen = was;
+                }
+            }
+        }
     }
+}
+
+// kRealign: the instance of a realigning session; the other instance is the kernel every session had before
+template <bool kRealign>
+__global__ __launch_bounds__(kThreads) void frag_count_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
+                                                              vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
+                                                              uint32_t* __restrict__ cnt, uint32_t* __restrict__ nbytes, uint32_t* __restrict__ nxa,
+                                                              unsigned long long* __restrict__ counters, Realign ra, uint32_t* __restrict__ nev,
+                                                              uint32_t* __restrict__ nxb, uint32_t* __restrict__ nyb) {
+    frag_count_body<kRealign, false>(base, starts, n, rec0, t, L, realign, window, coeff, cnt, nbytes, nxa, counters, ra, nev, nxb, nyb, 0);
+}
+__global__ __launch_bounds__(kThreads) void frag_count_indel_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
+                                                                    vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
+                                                                    uint32_t* __restrict__ cnt, uint32_t* __restrict__ nbytes, uint32_t* __restrict__ nxa,
+                                                                    unsigned long long* __restrict__ counters, Realign ra, uint32_t* __restrict__ nev,
+                                                                    uint32_t* __restrict__ nxb, uint32_t* __restrict__ nyb, int64_t max_locus_len) {
+    frag_count_body<true, true>(base, starts, n, rec0, t, L, realign, window, coeff, cnt, nbytes, nxa, counters, ra, nev, nxb, nyb, max_locus_len);
+}
+
+template <bool kRealign>
+__global__ __launch_bounds__(kThreads) void frag_fill_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
+                                                             vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
+                                                             const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ nbytes, const uint64_t* __restrict__ off,
+                                                             const uint64_t* __restrict__ noff, const uint64_t* __restrict__ xoff, uint64_t member0, uint64_t member_cap,
+                                                             uint64_t name0, uint64_t name_cap, uint64_t key0, uint64_t key_cap, Member* __restrict__ members,
+                                                             uint8_t* __restrict__ names, AltKey* __restrict__ keys, uint32_t* __restrict__ locus_cnt, EvFill ev) {
+    frag_fill_body<kRealign, false>(base, starts, n, rec0, t, L, realign, window, coeff, cnt, nbytes, off, noff, xoff, member0, member_cap, name0, name_cap, key0, key_cap,
+                                    members, names, keys, locus_cnt, ev, IndelFill{});
+}
+__global__ __launch_bounds__(kThreads) void frag_fill_indel_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
+                                                                   vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
+                                                                   const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ nbytes, const uint64_t* __restrict__ off,
+                                                                   const uint64_t* __restrict__ noff, const uint64_t* __restrict__ xoff, uint64_t member0, uint64_t member_cap,
+                                                                   uint64_t name0, uint64_t name_cap, uint64_t key0, uint64_t key_cap, Member* __restrict__ members,
+                                                                   uint8_t* __restrict__ names, AltKey* __restrict__ keys, uint32_t* __restrict__ locus_cnt, EvFill ev,
+                                                                   IndelFill in) {
+    frag_fill_body<true, true>(base, starts, n, rec0, t, L, realign, window, coeff, cnt, nbytes, off, noff, xoff, member0, member_cap, name0, name_cap, key0, key_cap,
+                               members, names, keys, locus_cnt, ev, in);
 }
 
 __global__ __launch_bounds__(kThreads) void frag_scatter_kernel(const Member* __restrict__ members, uint64_t n_members, int64_t n_loci, const uint64_t* __restrict__ locus_off,
@@ -214,12 +309,22 @@ __device__ inline void bitonic(uint32_t* v, uint32_t P, Less less) {
     }
 }
 
-__global__ __launch_bounds__(kLocusThreads) void frag_locus_kernel(const Member* __restrict__ M, const uint8_t* __restrict__ names, const AltKey* __restrict__ keys,
+// what the fragment pass of an indel session needs beyond the members (the kIndel instances of the two kernels below)
+struct IndelPass {
+    const Side* sides;                      // parallel to the members
+    vlr_bp::Loci L;                         // kind, start, len of the loci
+    int has_insert_size;
+    vlr_fragpileup_indel_obs* tmpx;         // parallel to tmp
+    vlr_fragpileup_indel_obs* outx;         // parallel to the output
+};
+
+template <bool kIndel>
+__device__ __forceinline__ void frag_locus_body(const Member* __restrict__ M, const uint8_t* __restrict__ names, const AltKey* __restrict__ keys,
                                                                    const uint32_t* __restrict__ perm, const uint64_t* __restrict__ locus_off,
                                                                    const uint32_t* __restrict__ locus_cnt, uint32_t max_mapq, vlr_fragpileup_obs* tmp, uint32_t* pair_left,
                                                                    uint32_t* pair_right, uint16_t* __restrict__ rank_out, uint32_t* __restrict__ n_obs,
                                                                    uint32_t* __restrict__ major, AltKey* __restrict__ major_key, uint32_t* __restrict__ have_major_key,
-                                                                   uint32_t* __restrict__ lstatus) {
+                                                                   uint32_t* __restrict__ lstatus, IndelPass ip) {
     __shared__ uint32_t idx[kMax];
     __shared__ uint16_t rnk[kMax];
     __shared__ uint32_t part[2][kLocusThreads];
@@ -244,7 +349,12 @@ __global__ __launch_bounds__(kLocusThreads) void frag_locus_kernel(const Member*
         if (i == 0 || compare_names(names, M[idx[i - 1]], M[idx[i]]) != 0) {
             vlr_fragpileup_obs o;
             uint32_t ml, mr;
-            if (run_obs(M, names, idx, i, n, max_mapq, o, &ml, &mr)) { tmp[base + i] = o; pair_left[base + i] = ml; pair_right[base + i] = mr; flag = 1; }
+            if constexpr (kIndel) {
+                vlr_fragpileup_indel_obs x;
+                if (run_obs_indel(M, ip.sides, names, idx, i, n, ip.L.kind[l], ip.L.start[l], (int64_t)ip.L.len[l], ip.has_insert_size != 0, max_mapq, o, x, &ml, &mr)) {
+                    tmp[base + i] = o; ip.tmpx[base + i] = x; pair_left[base + i] = ml; pair_right[base + i] = mr; flag = 1;
+                }
+            } else if (run_obs(M, names, idx, i, n, max_mapq, o, &ml, &mr)) { tmp[base + i] = o; pair_left[base + i] = ml; pair_right[base + i] = mr; flag = 1; }
         }
         rnk[i] = flag;
     }
@@ -335,12 +445,13 @@ __global__ __launch_bounds__(kLocusThreads) void frag_locus_kernel(const Member*
     }
 }
 
-__global__ __launch_bounds__(kLocusThreads) void frag_gather_kernel(const Member* __restrict__ M, const AltKey* __restrict__ keys, const vlr_fragpileup_obs* __restrict__ tmp,
+template <bool kIndel>
+__device__ __forceinline__ void frag_gather_body(const Member* __restrict__ M, const AltKey* __restrict__ keys, const vlr_fragpileup_obs* __restrict__ tmp,
                                                                     const uint32_t* __restrict__ pair_left, const uint32_t* __restrict__ pair_right,
                                                                     const uint16_t* __restrict__ rank, const uint64_t* __restrict__ locus_off,
                                                                     const uint32_t* __restrict__ locus_cnt, const uint32_t* __restrict__ n_obs, const uint64_t* __restrict__ obs_off,
                                                                     const uint32_t* __restrict__ major, const AltKey* __restrict__ major_key,
-                                                                    const uint32_t* __restrict__ have_major_key, uint64_t out_cap, vlr_fragpileup_obs* __restrict__ out) {
+                                                                    const uint32_t* __restrict__ have_major_key, uint64_t out_cap, vlr_fragpileup_obs* __restrict__ out, IndelPass ip) {
     const uint32_t l = blockIdx.x;
     const uint32_t n = locus_cnt[l];
     if (n == 0 || n > kMax || n_obs[l] == 0) return;
@@ -357,7 +468,44 @@ __global__ __launch_bounds__(kLocusThreads) void frag_gather_kernel(const Member
         const uint32_t mr = pair_right[base + i];
         o.alt_locus = alt_locus_class(keys, M[pair_left[base + i]], mr != kSentinel ? &M[mr] : nullptr, have, mk);
         out[at + r] = o;
+        if constexpr (kIndel) ip.outx[at + r] = ip.tmpx[base + i];
     }
+}
+
+__global__ __launch_bounds__(kLocusThreads) void frag_locus_kernel(const Member* __restrict__ M, const uint8_t* __restrict__ names, const AltKey* __restrict__ keys,
+                                                                   const uint32_t* __restrict__ perm, const uint64_t* __restrict__ locus_off,
+                                                                   const uint32_t* __restrict__ locus_cnt, uint32_t max_mapq, vlr_fragpileup_obs* tmp, uint32_t* pair_left,
+                                                                   uint32_t* pair_right, uint16_t* __restrict__ rank_out, uint32_t* __restrict__ n_obs,
+                                                                   uint32_t* __restrict__ major, AltKey* __restrict__ major_key, uint32_t* __restrict__ have_major_key,
+                                                                   uint32_t* __restrict__ lstatus) {
+    frag_locus_body<false>(M, names, keys, perm, locus_off, locus_cnt, max_mapq, tmp, pair_left, pair_right, rank_out, n_obs, major, major_key, have_major_key, lstatus,
+                           IndelPass{});
+}
+__global__ __launch_bounds__(kLocusThreads) void frag_locus_indel_kernel(const Member* __restrict__ M, const uint8_t* __restrict__ names, const AltKey* __restrict__ keys,
+                                                                         const uint32_t* __restrict__ perm, const uint64_t* __restrict__ locus_off,
+                                                                         const uint32_t* __restrict__ locus_cnt, uint32_t max_mapq, vlr_fragpileup_obs* tmp,
+                                                                         uint32_t* pair_left, uint32_t* pair_right, uint16_t* __restrict__ rank_out,
+                                                                         uint32_t* __restrict__ n_obs, uint32_t* __restrict__ major, AltKey* __restrict__ major_key,
+                                                                         uint32_t* __restrict__ have_major_key, uint32_t* __restrict__ lstatus, IndelPass ip) {
+    frag_locus_body<true>(M, names, keys, perm, locus_off, locus_cnt, max_mapq, tmp, pair_left, pair_right, rank_out, n_obs, major, major_key, have_major_key, lstatus, ip);
+}
+
+__global__ __launch_bounds__(kLocusThreads) void frag_gather_kernel(const Member* __restrict__ M, const AltKey* __restrict__ keys, const vlr_fragpileup_obs* __restrict__ tmp,
+                                                                    const uint32_t* __restrict__ pair_left, const uint32_t* __restrict__ pair_right,
+                                                                    const uint16_t* __restrict__ rank, const uint64_t* __restrict__ locus_off,
+                                                                    const uint32_t* __restrict__ locus_cnt, const uint32_t* __restrict__ n_obs, const uint64_t* __restrict__ obs_off,
+                                                                    const uint32_t* __restrict__ major, const AltKey* __restrict__ major_key,
+                                                                    const uint32_t* __restrict__ have_major_key, uint64_t out_cap, vlr_fragpileup_obs* __restrict__ out) {
+    frag_gather_body<false>(M, keys, tmp, pair_left, pair_right, rank, locus_off, locus_cnt, n_obs, obs_off, major, major_key, have_major_key, out_cap, out, IndelPass{});
+}
+__global__ __launch_bounds__(kLocusThreads) void frag_gather_indel_kernel(const Member* __restrict__ M, const AltKey* __restrict__ keys, const vlr_fragpileup_obs* __restrict__ tmp,
+                                                                          const uint32_t* __restrict__ pair_left, const uint32_t* __restrict__ pair_right,
+                                                                          const uint16_t* __restrict__ rank, const uint64_t* __restrict__ locus_off,
+                                                                          const uint32_t* __restrict__ locus_cnt, const uint32_t* __restrict__ n_obs,
+                                                                          const uint64_t* __restrict__ obs_off, const uint32_t* __restrict__ major,
+                                                                          const AltKey* __restrict__ major_key, const uint32_t* __restrict__ have_major_key, uint64_t out_cap,
+                                                                          vlr_fragpileup_obs* __restrict__ out, IndelPass ip) {
+    frag_gather_body<true>(M, keys, tmp, pair_left, pair_right, rank, locus_off, locus_cnt, n_obs, obs_off, major, major_key, have_major_key, out_cap, out, ip);
 }
 
 }  // namespace vlr_fp
@@ -400,6 +548,15 @@ struct vlr_fragpileup : vlr_bam::Session {
     std::vector<vlr_indelpileup_hit> ev;           // the scored evidences, record-major
     double rt[4] = {0, 0, 0, 0};
     vlr_fp::Realign ra() const { return vlr_fp::Realign{rl_window, (int64_t)ctg.h_len.size() - 1, ctg.d_len}; }
+    // an indel session (vlr_fragpileup_open_indel): a realigning session with these beside it
+    bool indel = false;
+    int has_insert_size = 0;
+    int64_t max_locus_len = 0;
+    vlr_fp::Side* d_sides = nullptr;                 // [member_cap]
+    uint32_t *d_max_del = nullptr, *d_max_ins = nullptr; unsigned long long* d_max_clip = nullptr;   // [n_loci]
+    std::vector<vlr_fragpileup_indel_obs> obsx;      // parallel to obs
+    std::vector<vlr_fragpileup_indel_locus> locusx;  // [n_loci]
+    vlr_fp::IndelFill indel_fill() const { return vlr_fp::IndelFill{indel, max_locus_len, member_cap, d_sides, d_max_del, d_max_ins, d_max_clip}; }
 };
 
 namespace vlr_fp {
@@ -431,7 +588,10 @@ int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
     const uint64_t rec0 = s->n_records;
     const size_t stride = s->rec_cap;
     uint32_t *d_cnt = (uint32_t*)s->d_cnt, *d_nbytes = d_cnt + K_NAME * stride, *d_nxa = d_cnt + K_XA * stride;
-    if (s->realigning)
+    if (s->indel)
+        hipLaunchKernelGGL(frag_count_indel_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff,
+                           d_cnt, d_nbytes, d_nxa, s->d_counters, s->ra(), d_cnt + K_EV * stride, d_cnt + K_X * stride, d_cnt + K_Y * stride, s->max_locus_len);
+    else if (s->realigning)
         hipLaunchKernelGGL(frag_count_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt,
                            d_nbytes, d_nxa, s->d_counters, s->ra(), d_cnt + K_EV * stride, d_cnt + K_X * stride, d_cnt + K_Y * stride);
     else
@@ -454,7 +614,11 @@ int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
         ev.hits = s->d_ev; ev.member = s->d_evm; ev.gx = s->d_gx; ev.gy = s->d_gy; ev.src = s->d_src;
     }
     if (total[K_MEMBERS] && fits && s->n_members < s->member_cap) {
-        if (s->realigning)
+        if (s->indel)
+            hipLaunchKernelGGL(frag_fill_indel_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt,
+                               d_nbytes, s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys,
+                               s->key_cap, s->d_members, s->d_names, s->d_keys, s->d_lcnt, ev, s->indel_fill());
+        else if (s->realigning)
             hipLaunchKernelGGL(frag_fill_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt, d_nbytes,
                                s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys, s->key_cap,
                                s->d_members, s->d_names, s->d_keys, s->d_lcnt, ev);
@@ -467,9 +631,13 @@ int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
         if (ev.on) {   // the windows of the chunk's evidences, while its records are resident
             double tg = now_s();
             const unsigned waves_per_block = vlr_ip::kThreads / 64;
-            hipLaunchKernelGGL((vlr_ip::indelpileup_gather_kernel<SnvWindows, uint64_t>), dim3((unsigned)((ev.n_ev + waves_per_block - 1) / waves_per_block)), dim3(vlr_ip::kThreads),
-                               0, st, d_base, ev.n_ev, s->d_ev + ev.ev0, SnvWindows{s->dl.loci, s->ctg.d_ctg, ev.ra}, s->d_src, s->d_gx + 2 * ev.ev0, s->d_gy + 2 * ev.ev0, s->d_xb,
-                               s->d_yb, s->d_yq);
+            const dim3 grid((unsigned)((ev.n_ev + waves_per_block - 1) / waves_per_block));
+            if (s->indel)
+                hipLaunchKernelGGL((vlr_ip::indelpileup_gather_kernel<IndelAltWindows, uint64_t>), grid, dim3(vlr_ip::kThreads), 0, st, d_base, ev.n_ev, s->d_ev + ev.ev0,
+                                   IndelAltWindows{s->dl.loci, s->ctg.d_ctg, ev.ra}, s->d_src, s->d_gx + 2 * ev.ev0, s->d_gy + 2 * ev.ev0, s->d_xb, s->d_yb, s->d_yq);
+            else
+                hipLaunchKernelGGL((vlr_ip::indelpileup_gather_kernel<SnvWindows, uint64_t>), grid, dim3(vlr_ip::kThreads), 0, st, d_base, ev.n_ev, s->d_ev + ev.ev0,
+                                   SnvWindows{s->dl.loci, s->ctg.d_ctg, ev.ra}, s->d_src, s->d_gx + 2 * ev.ev0, s->d_gy + 2 * ev.ev0, s->d_xb, s->d_yb, s->d_yq);
             if ((rc = vlr_ip::sync_stage(st, s->rt[0], tg)) != VLR_OK) return rc;
         }
     }
@@ -556,8 +724,10 @@ int realign_pass(vlr_fragpileup* s) {
 int fragment_pass(vlr_fragpileup* s) {
     const size_t nm = (size_t)s->n_members, nl = (size_t)s->n_loci;
     uint32_t *d_perm = nullptr, *d_left = nullptr, *d_right = nullptr; uint16_t* d_rank = nullptr; vlr_fragpileup_obs *d_tmp = nullptr, *d_out = nullptr;
+    vlr_fragpileup_indel_obs *d_tmpx = nullptr, *d_outx = nullptr;   // an indel session: beside d_tmp and d_out
     int rc = VLR_OK;
     auto step = [&](int r) { if (rc == VLR_OK) rc = r; };
+    if (s->indel) step(guarded(d_tmpx, nm));
     step(guarded(d_perm, nm));
     step(guarded(d_rank, nm));
     step(guarded(d_left, nm));
@@ -568,8 +738,13 @@ int fragment_pass(vlr_fragpileup* s) {
         hipLaunchKernelGGL(vlr_bam::scan_kernel<uint32_t>, dim3(1), dim3(kScanThreads), 0, 0, s->d_lcnt, (int64_t)nl, (int64_t)0, s->d_loff, s->d_total);
         hipLaunchKernelGGL(frag_scatter_kernel, dim3((unsigned)((nm + kThreads - 1) / kThreads)), dim3(kThreads), 0, 0, s->d_members, (uint64_t)nm, s->n_loci, s->d_loff,
                            s->d_lcnt, s->d_cursor, d_perm);
-        hipLaunchKernelGGL(frag_locus_kernel, dim3((unsigned)nl), dim3(kLocusThreads), 0, 0, s->d_members, s->d_names, s->d_keys, d_perm, s->d_loff, s->d_lcnt, s->max_mapq,
-                           d_tmp, d_left, d_right, d_rank, s->d_nobs, s->d_major, s->d_major_key, s->d_have_key, s->d_lstatus);
+        IndelPass ip{s->d_sides, s->dl.loci, s->has_insert_size, d_tmpx, nullptr};
+        if (s->indel)
+            hipLaunchKernelGGL(frag_locus_indel_kernel, dim3((unsigned)nl), dim3(kLocusThreads), 0, 0, s->d_members, s->d_names, s->d_keys, d_perm, s->d_loff, s->d_lcnt, s->max_mapq,
+                               d_tmp, d_left, d_right, d_rank, s->d_nobs, s->d_major, s->d_major_key, s->d_have_key, s->d_lstatus, ip);
+        else
+            hipLaunchKernelGGL(frag_locus_kernel, dim3((unsigned)nl), dim3(kLocusThreads), 0, 0, s->d_members, s->d_names, s->d_keys, d_perm, s->d_loff, s->d_lcnt, s->max_mapq,
+                               d_tmp, d_left, d_right, d_rank, s->d_nobs, s->d_major, s->d_major_key, s->d_have_key, s->d_lstatus);
         hipLaunchKernelGGL(vlr_bam::scan_kernel<uint32_t>, dim3(1), dim3(kScanThreads), 0, 0, s->d_nobs, (int64_t)nl, (int64_t)0, s->d_obsoff, s->d_total + 1);
         VLR_HIP_OK(hipDeviceSynchronize());
         VLR_HIP_OK(hipGetLastError());
@@ -578,8 +753,14 @@ int fragment_pass(vlr_fragpileup* s) {
         // the output is sized by the observations, not by the members
         int r = guarded(d_out, (size_t)total_obs);
         if (r != VLR_OK) return r;
-        hipLaunchKernelGGL(frag_gather_kernel, dim3((unsigned)nl), dim3(kLocusThreads), 0, 0, s->d_members, s->d_keys, d_tmp, d_left, d_right, d_rank, s->d_loff, s->d_lcnt,
-                           s->d_nobs, s->d_obsoff, s->d_major, s->d_major_key, s->d_have_key, total_obs, d_out);
+        if (s->indel && (r = guarded(d_outx, (size_t)total_obs)) != VLR_OK) return r;
+        ip.outx = d_outx;
+        if (s->indel)
+            hipLaunchKernelGGL(frag_gather_indel_kernel, dim3((unsigned)nl), dim3(kLocusThreads), 0, 0, s->d_members, s->d_keys, d_tmp, d_left, d_right, d_rank, s->d_loff, s->d_lcnt,
+                               s->d_nobs, s->d_obsoff, s->d_major, s->d_major_key, s->d_have_key, total_obs, d_out, ip);
+        else
+            hipLaunchKernelGGL(frag_gather_kernel, dim3((unsigned)nl), dim3(kLocusThreads), 0, 0, s->d_members, s->d_keys, d_tmp, d_left, d_right, d_rank, s->d_loff, s->d_lcnt,
+                               s->d_nobs, s->d_obsoff, s->d_major, s->d_major_key, s->d_have_key, total_obs, d_out);
         VLR_HIP_OK(hipDeviceSynchronize());
         VLR_HIP_OK(hipGetLastError());
         bool ok = true;
@@ -589,6 +770,8 @@ int fragment_pass(vlr_fragpileup* s) {
         if (r == VLR_OK) r = guard_intact(d_right, nm, &ok);
         if (r == VLR_OK) r = guard_intact(d_tmp, nm, &ok);
         if (r == VLR_OK) r = guard_intact(d_out, (size_t)total_obs, &ok);
+        if (s->indel && r == VLR_OK) r = guard_intact(d_tmpx, nm, &ok);
+        if (s->indel && r == VLR_OK) r = guard_intact(d_outx, (size_t)total_obs, &ok);
         if (r != VLR_OK) return r;
         if (!ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
         const double t1 = now_s();
@@ -605,13 +788,31 @@ int fragment_pass(vlr_fragpileup* s) {
             s->locus_rec[k] = vlr_fragpileup_locus{(int64_t)ooff[k], lcnt[k], nobs[k], major[k], lst[k]};
             if (lst[k]) ++s->n_too_deep;
         }
+        if (s->indel) {
+            s->obsx.resize((size_t)total_obs);
+            if (total_obs) VLR_HIP_OK(hipMemcpy(s->obsx.data(), d_outx, (size_t)total_obs * sizeof(vlr_fragpileup_indel_obs), hipMemcpyDeviceToHost));
+        }
         s->t[7] += now_s() - t1;
         return VLR_OK;
     };
     if (rc == VLR_OK) rc = body();
-    void* p[] = {d_perm, d_rank, d_left, d_right, d_tmp, d_out};
+    void* p[] = {d_perm, d_rank, d_left, d_right, d_tmp, d_out, d_tmpx, d_outx};
     for (void* q : p) if (q) (void)hipFree(q);
     return rc;
+}
+
+// the per-locus CIGAR maxima of an indel session, to the host
+int read_maxima(vlr_fragpileup* s) {
+    const size_t nl = (size_t)s->n_loci;
+    std::vector<uint32_t> md(nl), mi(nl);
+    std::vector<unsigned long long> mc(nl);
+    if (nl) {
+        VLR_HIP_OK(hipMemcpy(md.data(), s->d_max_del, nl * 4, hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(mi.data(), s->d_max_ins, nl * 4, hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(mc.data(), s->d_max_clip, nl * 8, hipMemcpyDeviceToHost));
+    }
+    for (size_t k = 0; k < nl; ++k) s->locusx[k] = vlr_fragpileup_indel_locus{md[k], mi[k], (uint32_t)(mc[k] >> 32), (uint32_t)(mc[k] & 0xffffffffull)};
+    return VLR_OK;
 }
 
 }  // namespace vlr_fp
@@ -620,10 +821,35 @@ namespace vlr_fp {
 
 // what vlr_fragpileup_open_realign gives beyond vlr_fragpileup_open
 struct RealignOpen { const char* fasta; int window; vlr_ip::ScoreParams score; int64_t evidence_capacity, pair_byte_limit; };
+// what vlr_fragpileup_open_indel gives beyond that: the loci's alt allele windows lie at alt_bases[alt_offset[k] .. alt_offset[k + 1])
+struct IndelOpen { const uint64_t* alt_offset; int has_insert_size; };
+
+// the deletion / insertion loci of an indel session: kind, interval, order, the limits; base_off = alt_offset
+int check_indel_loci(const char* api, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int32_t* len, const uint8_t* kind, const uint64_t* alt_offset,
+                     int realign_window, std::vector<uint64_t>& base_off, int64_t* max_locus_len, uint64_t* max_alt_len) {
+    const uint64_t alt_limit = (uint64_t)VLR_FRAGPILEUP_MAX_INDEL_LEN + 2ull * ((uint64_t)realign_window * 3 / 2);
+    base_off.assign((size_t)n_loci + 1, 0);
+    *max_locus_len = 1; *max_alt_len = 0;
+    for (int64_t k = 0; k < n_loci; ++k) {
+        if ((kind[k] != VLR_INDELPILEUP_DELETION && kind[k] != VLR_INDELPILEUP_INSERTION) || ref_id[k] < 0 || start[k] < 0 || len[k] < 1 ||
+            (kind[k] == VLR_INDELPILEUP_INSERTION && len[k] != 1) || alt_offset[k + 1] < alt_offset[k] || (k == 0 && alt_offset[0] != 0))
+            return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: locus %lld: kind %d over %d bases (a deletion or an insertion; an insertion has 1), or its alt window's offsets", api,
+                         (long long)k, (int)kind[k], (int)len[k]);
+        if (len[k] > VLR_FRAGPILEUP_MAX_INDEL_LEN || alt_offset[k + 1] - alt_offset[k] > alt_limit)
+            return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: locus %lld is %d bases long with an alt window of %llu: a session takes at most %d and %llu", api, (long long)k, (int)len[k],
+                         (unsigned long long)(alt_offset[k + 1] - alt_offset[k]), VLR_FRAGPILEUP_MAX_INDEL_LEN, (unsigned long long)alt_limit);
+        if (k > 0 && (ref_id[k] < ref_id[k - 1] || (ref_id[k] == ref_id[k - 1] && start[k] < start[k - 1])))
+            return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: loci are not sorted by (ref_id, start) at %lld", api, (long long)k);
+        base_off[(size_t)k + 1] = alt_offset[k + 1];
+        *max_locus_len = std::max<int64_t>(*max_locus_len, len[k]);
+        *max_alt_len = std::max<uint64_t>(*max_alt_len, alt_offset[k + 1] - alt_offset[k]);
+    }
+    return VLR_OK;
+}
 
 int open_impl(const char* api, int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int32_t* len, const uint8_t* kind, const uint8_t* ref_bases,
               const uint8_t* alt_bases, int realign_indel_reads, int64_t window, int max_mapq, int max_read_len, int64_t member_capacity, int64_t name_capacity,
-              int64_t key_capacity, int64_t window_bytes, const RealignOpen* ro, vlr_fragpileup** out) {
+              int64_t key_capacity, int64_t window_bytes, const RealignOpen* ro, vlr_fragpileup** out, const IndelOpen* io = nullptr) {
     if (!out || n_loci < 0 || n_loci > 0x7fffffff || member_capacity < 0 || member_capacity > 0x7fffffff || name_capacity < 0 || key_capacity < 0 || key_capacity > 0x7fffffff ||
         window_bytes < 0 || window < 0 ||
         window > ((int64_t)1 << 40) || max_mapq < 0 || max_mapq > 255 || (n_loci > 0 && (!ref_id || !start || !len || !kind || !ref_bases || !alt_bases)))
@@ -631,7 +857,9 @@ int open_impl(const char* api, int device, int64_t n_loci, const int32_t* ref_id
     if (max_read_len <= 0) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: max_read_len must be positive", api);
     *out = nullptr;
     std::vector<uint64_t> base_off;
-    int rc = vlr_bp::check_snv_mnv_loci(api, n_loci, ref_id, start, len, kind, base_off);
+    int64_t max_locus_len = 0; uint64_t max_alt_len = 0;
+    int rc = io != nullptr && ro != nullptr ? check_indel_loci(api, n_loci, ref_id, start, len, kind, io->alt_offset, ro->window, base_off, &max_locus_len, &max_alt_len)
+                                            : vlr_bp::check_snv_mnv_loci(api, n_loci, ref_id, start, len, kind, base_off);
     if (rc != VLR_OK || (rc = vlr_bam::use_device(device)) != VLR_OK) return rc;
     vlr_fragpileup* s = new vlr_fragpileup();
     s->realign = realign_indel_reads ? 1 : 0;
@@ -659,6 +887,15 @@ int open_impl(const char* api, int device, int64_t n_loci, const int32_t* ref_id
         // 2 * window <= 128 bases, twice
         const uint64_t rw = (uint64_t)ro->window * 3 / 2;
         s->x_cap = s->ev_cap * (4 * rw + VLR_BASEPILEUP_MAX_LEN);
+        if (io != nullptr) {   // an indel session: a ref window of at most 2 rw bases and the longest of the loci's own alt windows
+            s->indel = true;
+            s->has_insert_size = io->has_insert_size ? 1 : 0;
+            s->max_locus_len = max_locus_len;
+            s->x_cap = s->ev_cap * (2 * rw + max_alt_len);
+            s->locusx.assign((size_t)n_loci, vlr_fragpileup_indel_locus{0, 0, 0, 0});
+            step(guarded(s->d_sides, (size_t)s->member_cap));
+            step(zeros(s->d_max_del, (size_t)n_loci)); step(zeros(s->d_max_ins, (size_t)n_loci)); step(zeros(s->d_max_clip, (size_t)n_loci));
+        }
         s->y_cap = s->ev_cap * 2 * (uint64_t)vlr_ip::kMaxPatternLen;
         step(vlr_bam::read_fai(s->ctg.fasta, s->ctg.fai));
         step(guarded(s->d_ev, (size_t)s->ev_cap));
@@ -738,6 +975,10 @@ int vlr_fragpileup_result(vlr_fragpileup* s, vlr_fragpileup_counts* r) {
             if (rc == VLR_OK) rc = guard_intact(s->d_yb, (size_t)s->y_cap, &ok);
             if (rc == VLR_OK) rc = guard_intact(s->d_yq, (size_t)s->y_cap, &ok);
         }
+        if (s->indel) {
+            if (rc == VLR_OK) rc = guard_intact(s->d_sides, (size_t)s->member_cap, &ok);
+            if (rc == VLR_OK) rc = read_maxima(s);
+        }
         if (rc != VLR_OK) return rc;
         if (!ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
         if (vlr_bam::bad_record_seen(*s)) s->status |= VLR_FRAGPILEUP_BAD_RECORD;
@@ -802,6 +1043,44 @@ int vlr_fragpileup_read_realigned(vlr_fragpileup* s, vlr_indelpileup_hit* hits, 
     return VLR_OK;
 }
 
+int vlr_fragpileup_open_indel(int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int64_t* end, const uint8_t* kind,
+                              const uint64_t* alt_offset, const uint8_t* alt_bases, int64_t window, int max_mapq, int max_read_len,
+                              int64_t member_capacity, int64_t name_capacity, int64_t key_capacity, int64_t window_bytes, const char* fasta_path,
+                              int realign_window, int mode, const double gap[4], const double* hop, int64_t evidence_capacity,
+                              int64_t pair_byte_limit, int has_insert_size, vlr_fragpileup** out) {
+    using namespace vlr_fp;
+    if (!fasta_path || !gap || evidence_capacity < 0 || evidence_capacity > 0x7fffffff || pair_byte_limit < 0 || n_loci < 0 || n_loci > 0x7fffffff ||
+        (n_loci > 0 && (!start || !end || !alt_offset || !alt_bases)))
+        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_open_indel: bad argument");
+    RealignOpen ro{fasta_path, realign_window, vlr_ip::ScoreParams(), evidence_capacity, pair_byte_limit};
+    const int rc = vlr_ip::check_score_params("vlr_fragpileup_open_indel", realign_window, mode, gap, hop, ro.score);
+    if (rc != VLR_OK) return rc;
+    // the loci as the session's tables hold them: len = end - start (the limit is checked on the 64-bit value)
+    std::vector<int32_t> len((size_t)n_loci);
+    for (int64_t k = 0; k < n_loci; ++k) {
+        const int64_t l = end[k] - start[k];
+        if (start[k] < 0 || l < 1 || l > VLR_FRAGPILEUP_MAX_INDEL_LEN)
+            return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_open_indel: locus %lld [%lld, %lld) is empty or longer than the %d bases a session takes", (long long)k,
+                         (long long)start[k], (long long)end[k], VLR_FRAGPILEUP_MAX_INDEL_LEN);
+        len[(size_t)k] = (int32_t)l;
+    }
+    const IndelOpen io{alt_offset, has_insert_size};
+    // (an indel session has no ref allele bytes: Loci::ref_bases is never read by an indel arm — base_off is the ALT offsets, so the alt windows
+    // stand in for them rather than a null pointer.  Nothing may read ref_bases of such a session.)
+    return open_impl("vlr_fragpileup_open_indel", device, n_loci, ref_id, start, len.data(), kind, alt_bases, alt_bases, 1, window, max_mapq, max_read_len,
+                     member_capacity, name_capacity, key_capacity, window_bytes, &ro, out, &io);
+}
+
+int vlr_fragpileup_read_indel(vlr_fragpileup* s, vlr_fragpileup_indel_obs* extra_obs, int64_t n_obs, vlr_fragpileup_indel_locus* extra_loci, int64_t n_loci) {
+    using namespace vlr_fp;
+    if (!s || !s->collected || !s->indel) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_read_indel: call vlr_fragpileup_result on a session of vlr_fragpileup_open_indel first");
+    if (n_obs != (int64_t)s->obsx.size() || n_loci != s->n_loci || (n_obs > 0 && !extra_obs) || (n_loci > 0 && !extra_loci))
+        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_read_indel: sizes differ from vlr_fragpileup_result and the loci given at open");
+    if (n_obs) memcpy(extra_obs, s->obsx.data(), (size_t)n_obs * sizeof(vlr_fragpileup_indel_obs));
+    if (n_loci) memcpy(extra_loci, s->locusx.data(), (size_t)n_loci * sizeof(vlr_fragpileup_indel_locus));
+    return VLR_OK;
+}
+
 void vlr_fragpileup_close(vlr_fragpileup* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -809,7 +1088,7 @@ void vlr_fragpileup_close(vlr_fragpileup* s) {
     s->dl.free();
     s->ctg.free();
     void* p[] = {s->d_members, s->d_names, s->d_keys, s->d_major_key, s->d_have_key, s->d_lcnt, s->d_cursor, s->d_nobs, s->d_major, s->d_lstatus, s->d_loff, s->d_obsoff,
-                 s->d_ev, s->d_evm, s->d_gx, s->d_gy, s->d_xb, s->d_yb, s->d_yq, s->d_src};
+                 s->d_ev, s->d_evm, s->d_gx, s->d_gy, s->d_xb, s->d_yb, s->d_yq, s->d_src, s->d_sides, s->d_max_del, s->d_max_ins, s->d_max_clip};
     for (void* q : p) if (q) (void)hipFree(q);
     delete s;
 }

@@ -38,7 +38,9 @@ with the record's ordinal: a CIGAR that begins with N (read_pos fails) and a rec
 
 NOT mirrored (callers must know): `alt_variants`; without a RealignSpec the realignment (with realign_indel_reads=True such
 observations come back flagged NEEDS_REALIGN and `observations` raises), `max_depth` subsampling (the `rand` crate's StdRng),
-`report_fragment_ids` (None), indel / SV / breakend candidates with their insert-size terms, haplotype blocks, methylation.
+`report_fragment_ids` (None), replacement / SV / breakend candidates, haplotype blocks, methylation.  Deletion and insertion candidates
+are built on request (`indel_candidates`, --indel-candidates): the section "deletion and insertion candidates" below has their rule
+and what of it is not mirrored.
 `preprocess_variants` is the command `python -m varlociraptor_amd preprocess variants`; it says what it does not do as errors.
 """
 from __future__ import annotations
@@ -633,6 +635,7 @@ class ObsTable:
     records: List[Tuple[int, ...]]
     major_read_position: Optional[int] = None
     major_alt_locus: Optional[Tuple[bytes, int]] = None
+    prob_sample_alt: Optional[np.ndarray] = None   # an indel candidate (None: ln 1, an SNV / MNV)
 
     def __len__(self):
         return len(self.prob_alt)
@@ -693,17 +696,60 @@ def table_of(obs: Sequence[FragObs], props: Props, t: Tables, omit_mapq_adjustme
                     np.array([o.third_allele for o in obs], np.uint32), [(o.left,) if o.right is None else (o.left, o.right) for o in obs], major, major_alt)
 
 
+class _Inputs:
+    """what one call of `observations` reads of its files, once: the reference, the contigs of the first BAM's header, and — only when
+    a restatement needs them — the records of the BAMs"""
+    def __init__(self, bams, fasta):
+        from . import alignprops
+        self.bams = list(bams)
+        self.seqs = read_fasta(fasta)
+        contigs, _ = alignprops.bam_header(alignprops.inflate_bgzf(self.bams[0]), self.bams[0])
+        self.tid = {name: k for k, (name, _) in enumerate(contigs)}
+        self._records: Optional[List[BamRecord]] = None
+
+    def records(self) -> List[BamRecord]:
+        if self._records is None:
+            self._records = [r for b in self.bams for r in read_bam(b)[1]]
+        return self._records
+
+
 def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, bytes]], props, device=0, omit_mapq_adjustment: bool = False,
-                 realign_indel_reads: bool = False, window_bytes: int = 0, realign: Optional[RealignSpec] = None) -> List[ObsTable]:
+                 realign_indel_reads: bool = False, window_bytes: int = 0, realign: Optional[RealignSpec] = None,
+                 indel_candidates: Optional[RealignSpec] = None, indel_props: Optional[IndelProps] = None, _inputs: Optional["_Inputs"] = None) -> List[ObsTable]:
     """Per candidate (contig, 0-based position, REF, ALT), in the order given, its processed pileup.  device="cpu": the restatement; a
     device number: the kernels, finished as the module header says.  `realign`: indel-bearing reads are realigned (module header);
-    realign_indel_reads=True without it raises NeedsRealign for such a read."""
-    from . import alignprops
-    props = props_of(props)
+    realign_indel_reads=True without it raises NeedsRealign for such a read.  `indel_candidates`: deletion / insertion candidates
+    (REF and ALT of different lengths) are built, every member realigned with this spec, through the indel session (`indel_tables`;
+    `indel_props`: what they need of the alignment properties, default: read from `props`); the SNV / MNV candidates of the same call
+    go the way they always went."""
     bams = [bam] if isinstance(bam, str) else list(bam)
-    seqs = read_fasta(fasta)
-    contigs, _ = alignprops.bam_header(alignprops.inflate_bgzf(bams[0]), bams[0])
-    tid = {name: k for k, (name, _) in enumerate(contigs)}
+    inp = _inputs if _inputs is not None else _Inputs(bams, fasta)      # (read once, shared by the SNV / MNV and the indel part of a mixed call)
+    seqs, tid = inp.seqs, inp.tid
+    ind = [k for k, c in enumerate(candidates) if len(c[2]) != len(c[3])]
+    if ind:
+        if indel_candidates is None:
+            raise ValueError("candidate %s:%d is not an SNV or MNV (indel_candidates builds deletions and insertions)" % (candidates[ind[0]][0], candidates[ind[0]][1] + 1))
+        ip = indel_props if indel_props is not None else indel_props_of(props)
+        ind_set = set(ind)
+        rest = [k for k in range(len(candidates)) if k not in ind_set]
+        out: List[Optional[ObsTable]] = [None] * len(candidates)
+        if rest:
+            for k, tab in zip(rest, observations(bam, fasta, [candidates[k] for k in rest], props, device, omit_mapq_adjustment, realign_indel_reads, window_bytes, realign,
+                                                 _inputs=inp)):
+                out[k] = tab
+        sites, what = [], []
+        for k in ind:
+            c, pos, ref, alt = candidates[k]
+            if c not in tid or c not in seqs:
+                raise ValueError("contig %s is not in the BAM header and the reference" % c)
+            what.append("%s:%d %s>%s" % (c, pos + 1, bytes(ref).decode(), bytes(alt).decode()))
+            sites.append(indel_site(seqs[c], tid[c], int(pos), ref, alt, indel_candidates.window, what[-1]))
+        ref_seqs = {tid[c]: seqs[c].upper() for c in set(candidates[k][0] for k in ind)}
+        for k, tab in zip(ind, indel_tables(bams, fasta, sites, what, props_of(props), ip, indel_candidates, device, omit_mapq_adjustment, window_bytes, ref_seqs,
+                                           records=inp.records)):
+            out[k] = tab
+        return out
+    props = props_of(props)
     loci = []
     for c, pos, ref, alt in candidates:
         if c not in tid or c not in seqs:
@@ -711,13 +757,7 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
         loci.append(basecalls.locus(seqs[c], tid[c], int(pos), ref, alt))
     ref_seqs = {tid[c]: seqs[c].upper() for c in set(c for c, _, _, _ in candidates)} if realign is not None else None
     order = sorted(range(len(loci)), key=lambda k: (loci[k].ref_id, loci[k].start))
-    recs: Optional[List[BamRecord]] = None
-
-    def records():
-        nonlocal recs
-        if recs is None:
-            recs = [r for b in bams for r in read_bam(b)[1]]
-        return recs
+    records = inp.records
     out: List[Optional[ObsTable]] = [None] * len(loci)
     if device == "cpu":
         t = basecalls.TABLES
@@ -776,25 +816,559 @@ def pileup(tables: Sequence[ObsTable], candidates: Sequence[Tuple[str, int, byte
         cols["prob_alt"].append(pa)
         cols["prob_ref"].append(pr)
         cols["prob_missed_allele"].append(np.logaddexp(pa, pr) - math.log(2.0))
-        cols["prob_sample_alt"].append(np.zeros(n))
+        cols["prob_sample_alt"].append(np.zeros(n) if s.prob_sample_alt is None else s.prob_sample_alt)
         cols["prob_double_overlap"].append(np.where(s.strand == abi.STRAND_BOTH, 0.0, -np.inf))
         cols["prob_hit_base"].append(s.prob_hit_base)
         cols["flags"].append(abi.pack_flags(s.strand, pack_orientation(s.orientation), s.read_position_major, s.softclipped, s.paired, s.is_max_mapq, s.alt_locus))
         third.append(s.third_allele.astype(np.int32))
     cat = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in cols.items()}
-    snv = np.array([len(c[2]) == 1 for c in candidates], bool)
-    lf = 0
+    indel = np.array([len(c[2]) != len(c[3]) for c in candidates], bool)
+    snv = np.array([len(c[2]) == 1 for c in candidates], bool) & ~indel
+    lf = lf_indel = 0
     for bit in (abi.BIAS_ORIENTATION, abi.BIAS_STRAND, abi.BIAS_POSITION, abi.BIAS_SOFTCLIP, abi.BIAS_ALTLOCUS):
         if not omit_bias_mask & bit:
             lf |= bit
+            if bit in (abi.BIAS_STRAND, abi.BIAS_ALTLOCUS):   # what obsfmt.read_observation_vcf sets for a precise indel without a homopolymer length
+                lf_indel |= bit
     if not omit_bias_mask & abi.BIAS_ORIENTATION:
         lf |= abi.LOCUS_REMOVE_NONSTANDARD
-    loc = {"locus_flags": (np.full(len(tables), lf, np.uint8) | np.where(snv, abi.LOCUS_HAS_SNV, 0).astype(np.uint8)),
-           "variant_type": np.where(snv, abi.VT_SNV, abi.VT_MNV).astype(np.uint8),
-           "ref_base": np.array([bytes(c[2]).upper()[0] if len(c[2]) == 1 else 0 for c in candidates], np.uint8),
-           "alt_base": np.array([bytes(c[3]).upper()[0] if len(c[3]) == 1 else 0 for c in candidates], np.uint8)}
+    loc = {"locus_flags": (np.where(indel, lf_indel, lf).astype(np.uint8) | np.where(snv, abi.LOCUS_HAS_SNV, 0).astype(np.uint8)),
+           "variant_type": np.where(indel, abi.VT_INDEL, np.where(snv, abi.VT_SNV, abi.VT_MNV)).astype(np.uint8),
+           "ref_base": np.array([bytes(c[2]).upper()[0] if len(c[2]) == 1 and len(c[3]) == 1 else 0 for c in candidates], np.uint8),
+           "alt_base": np.array([bytes(c[3]).upper()[0] if len(c[2]) == 1 and len(c[3]) == 1 else 0 for c in candidates], np.uint8)}
     batch = PileupBatch(1, off.astype(np.uint32), {k: (np.asarray(v, np.float32) if k != "flags" else np.asarray(v, np.uint32)) for k, v in cat.items()}, loc)
     return batch, (np.concatenate(third) if third else np.zeros(0, np.int32))
+
+
+# ---------------------------------------------------------------------------------------------- deletion and insertion candidates
+# What the reference runs for a deletion / insertion candidate between the per-read supports (readwindows.py) and the pileup:
+#   Deletion::new / centerpoint, fetch loci          deletion.rs:41-85 (start, start + round(len / 2) with f64::round, end - 1)
+#   Fetches::push                                    sample.rs:163-178 (merged when locus.start - W <= last.end + W)
+#   is_valid_evidence                                deletion.rs:158-197, insertion.rs:139-157
+#   allele_support (every member is realigned)       deletion.rs:204-262, insertion.rs:165-204, Realigner::allele_support (mod.rs:161-424)
+#   estimate_insert_size                             insert_size.rs:17-45
+#   allele_support_isize, isize_pmf, is_within_sd    types/mod.rs:197-240, sampling_bias/fragments.rs:32-44, 147-166
+#   prob_sample_alt                                  deletion.rs:264-293, insertion.rs:206-227, sampling_bias/reads.rs, fragments.rs:17-145
+#   update_max_cigar_ops_len while reading           types/mod.rs:310, alignment_properties.rs:94-144 (only what is already Some)
+# Only deletions whose three fetch loci merge into one fetch are built (`fetches_merge`): membership is then is_member on [start, end).
+# The kernels (vlr_fragpileup_open_indel) give members, evidences, fragments with the validity rule, insert sizes, read lengths and
+# the per-locus CIGAR maxima; `isize_support`, `prob_sample_alt` and the running maxima need libm and are these functions on both
+# paths, so the two agree with ==.  Phi is 0.5 erfc(-x / sqrt 2) from libm where the reference calls GSL's ugaussian_P: unpinned.
+# NOT mirrored: the read-inferred third allele, alt_variants, homopolymer_indel_len and the two prob_observable_at_homopolymer_*
+# fields (none: the Myers traceback of the `bio` crate), max_depth subsampling, report_fragment_ids, replacements, SVs, breakends,
+# deletions with more than one fetch, and — in a file that mixes candidates — what records that are members of SNV / MNV candidates
+# only would add to the running maxima.
+MAX_INDEL_LEN = abi.FRAGPILEUP_MAX_INDEL_LEN
+
+
+class UnrealisticIsizeSd(FragPileupError):
+    """Error::UnrealisticIsizeSd: an insert-size standard deviation of 0"""
+
+
+class NonPositiveInsertSize(FragPileupError):
+    """the assertion of insert_size.rs:38-42"""
+
+
+@dataclass
+class IndelProps:
+    """what an indel candidate needs of the alignment properties beyond Props; the three maxima rise while records are read"""
+    insert_size: Optional[Tuple[float, float]]     # (mean, sd)
+    max_del_cigar_len: Optional[int]
+    max_ins_cigar_len: Optional[int]
+    frac_max_softclip: Optional[float]
+
+    def key(self):
+        return (self.insert_size, self.max_del_cigar_len, self.max_ins_cigar_len, self.frac_max_softclip)
+
+
+def indel_props_of(p) -> IndelProps:
+    if isinstance(p, IndelProps):
+        return p
+    g = p.get if isinstance(p, dict) else (lambda k: getattr(p, k, None))
+    ins = g("insert_size")
+    if ins is not None and not isinstance(ins, tuple):
+        ins = (float(ins["mean"]), float(ins["sd"])) if isinstance(ins, dict) else (float(ins.mean), float(ins.sd))
+    return IndelProps(ins, g("max_del_cigar_len"), g("max_ins_cigar_len"), g("frac_max_softclip"))
+
+
+@dataclass
+class IndelSite:
+    """a deletion / insertion candidate: readwindows.IndelLocus on its contig"""
+    ref_id: int
+    locus: "object"
+
+    @property
+    def kind(self):
+        return self.locus.kind
+
+    @property
+    def start(self):
+        return self.locus.start
+
+    @property
+    def end(self):
+        return self.locus.end
+
+    @property
+    def length(self) -> int:
+        """enclosable_len: the deleted / the inserted bases"""
+        return abs(self.locus.len_diff)
+
+
+def centerpoint(start: int, length: int) -> int:
+    """deletion.rs:45: start + (len as f64 / 2.0).round() — f64::round rounds half away from zero, unlike Python's round()"""
+    return start + (length + 1) // 2
+
+
+def fetches_merge(start: int, end: int, window: int) -> bool:
+    """do the three fetch loci of the deletion [start, end) merge into one fetch (Fetches::push)?"""
+    c = centerpoint(start, end - start)
+    last_end = start + 1
+    for s, e in ((c, c + 1), (end - 1, end)):
+        if max(s - window, 0) > last_end + window:
+            return False
+        last_end = e
+    return True
+
+
+def clips(rec: BamRecord) -> Tuple[int, int, int, int]:
+    """(leading soft, leading hard, trailing soft, trailing hard) as rust-htslib counts them: a soft clip behind one hard clip counts"""
+    c = rec.cigar
+    if not c:
+        return 0, 0, 0, 0
+    lh = c[0][1] if c[0][0] == "H" else 0
+    first = (c[1] if len(c) > 1 else None) if lh or c[0][0] == "H" else c[0]
+    th = c[-1][1] if c[-1][0] == "H" else 0
+    last = (c[-2] if len(c) > 1 else None) if th or c[-1][0] == "H" else c[-1]
+    return (first[1] if first and first[0] == "S" else 0), lh, (last[1] if last and last[0] == "S" else 0), th
+
+
+def estimate_insert_size(left: BamRecord, right: BamRecord) -> int:
+    """insert_size.rs:17-45 as written; the caller raises for a value <= 0"""
+    def aln(r):
+        ls, lh, ts, th = clips(r)
+        return max(r.pos - (ls + lh), 0), r.end_pos() + ts + th
+    (l0, l1), (r0, r1) = aln(left), aln(right)
+    return (r0 - l1) + (l1 - l0) + (r1 - r0)
+
+
+def ugaussian_p(x: float) -> float:
+    return 0.5 * math.erfc(-x / math.sqrt(2.0))
+
+
+def isize_pmf(value: float, mean: float, sd: float) -> float:
+    """sampling_bias/fragments.rs:164-166: the difference of two Phi values, as written (its underflow to ln 0 is what isize_support keys on)"""
+    d = ugaussian_p((value + 0.5 - mean) / sd) - ugaussian_p((value - 0.5 - mean) / sd)
+    return math.log(d) if d > 0.0 else -math.inf
+
+
+def isize_support(insert_size: int, length: int, ip: IndelProps) -> Tuple[float, float]:
+    """(ln P(insert size | ref), ln P(insert size | alt)) of allele_support_isize (types/mod.rs:197-240)"""
+    mean, sd = ip.insert_size
+    if sd == 0.0:
+        raise UnrealisticIsizeSd("the insert size standard deviation of the alignment properties is 0")
+    p_ref = isize_pmf(float(insert_size), mean, sd)
+    p_alt = isize_pmf(float(insert_size), mean + float(length), sd)
+
+    def within_sd(shift):
+        return abs(float(insert_size) - (mean + shift)) <= sd
+    if (p_ref == -math.inf and not within_sd(float(length))) or (p_alt == -math.inf and not within_sd(0.0)):
+        return 0.0, 0.0
+    return p_ref, p_alt
+
+
+def feasible_bases(site: IndelSite, read_len: int, ip: IndelProps) -> Optional[int]:
+    """deletion.rs:95-110, insertion.rs:102-117"""
+    maxlen = ip.max_del_cigar_len if site.kind == "deletion" else ip.max_ins_cigar_len
+    if maxlen is not None and site.length <= maxlen:
+        return read_len
+    return None if ip.frac_max_softclip is None else int(read_len * ip.frac_max_softclip)
+
+
+def prob_sample_alt_read(site: IndelSite, read_len: int, ip: IndelProps) -> float:
+    """sampling_bias/reads.rs:20-40"""
+    feasible = feasible_bases(site, read_len, ip)
+    if feasible is None:
+        return 0.0
+    n_alt = min(site.length, read_len)
+    n_alt_valid = min(n_alt, feasible)
+    return (math.log(n_alt_valid) if n_alt_valid else -math.inf) - (math.log(n_alt) if n_alt else -math.inf)
+
+
+def isize_pmf_range(ip: IndelProps) -> range:
+    """fragments.rs:20-29 (f64::round: half away from zero)"""
+    mean, sd = ip.insert_size
+    m = int(math.floor(abs(mean) + 0.5)) if mean >= 0 else 0
+    s = int(math.ceil(sd)) * 6
+    return range(max(m - s, 0), m + s)
+
+
+def expected_prob_sample_alt(left_len: int, right_len: int, left_feasible: int, right_feasible: int, delta_ref: int, delta_alt: int, enclose_only: bool,
+                             ip: IndelProps) -> float:
+    """fragments.rs:47-116"""
+    inf_l, inf_r = max(left_len - left_feasible, 0), max(right_len - right_feasible, 0)
+    if not enclose_only:
+        inf_l, inf_r = max(inf_l - left_feasible, 0), max(inf_r - right_feasible, 0)
+    infeasible_read_pos = inf_l + inf_r
+    mean, sd = ip.insert_size
+    ps = []
+    for x in isize_pmf_range(ip):
+        internal = max(max(x - left_len, 0) - right_len, 0)
+        infeasible_alt = infeasible_read_pos + max(internal + 1 - delta_alt, 0)
+        infeasible_ref = max(internal + 1 - delta_ref, 0)
+        valid_alt = max(max(x - delta_alt, 0) - infeasible_alt, 0)
+        valid_ref = max(x - infeasible_ref, 0)
+        if x <= delta_alt or x <= delta_alt + infeasible_alt or x <= infeasible_ref:
+            continue
+        ps.append(isize_pmf(float(x), mean, sd) + (math.log(valid_alt) - math.log(valid_ref)))
+    p = basecalls.ln_sum_exp(ps)
+    if p > 0.0:                         # cap_numerical_overshoot(NUMERICAL_EPSILON = 1e-3)
+        if p > 1e-3:
+            raise FragPileupError("expected_prob_sample_alt: ln probability %g above 0" % p)
+        p = 0.0
+    return p
+
+
+def prob_sample_alt(site: IndelSite, len_left: int, len_right: Optional[int], ip: IndelProps, memo: Optional[Dict] = None) -> float:
+    """deletion.rs:264-293, insertion.rs:206-227; len_right = None for a single read.  `memo`: {(len_left, len_right): value} of one
+    candidate under one state of the properties"""
+    key = (len_left, len_right)
+    if memo is not None and key in memo:
+        return memo[key]
+    if len_right is None:
+        p = prob_sample_alt_read(site, len_left, ip)
+    elif site.kind == "deletion" and ip.insert_size is not None:
+        lf, rf = feasible_bases(site, len_left, ip), feasible_bases(site, len_right, ip)
+        p = expected_prob_sample_alt(len_left, len_right, lf, rf, site.length, 0, True, ip) if lf is not None and rf is not None else -math.inf
+    else:
+        one = basecalls.ln_one_minus_exp
+        p = one(one(prob_sample_alt_read(site, len_left, ip)) + one(prob_sample_alt_read(site, len_right, ip)))
+    if memo is not None:
+        memo[key] = p
+    return p
+
+
+def cigar_maxima(rec: BamRecord) -> Tuple[int, int, int]:
+    """(longest D, longest I, largest S) of a record: what update_max_cigar_ops_len looks at"""
+    m = {"D": 0, "I": 0, "S": 0}
+    for op, l in rec.cigar:
+        if op in m and l > m[op]:
+            m[op] = l
+    return m["D"], m["I"], m["S"]
+
+
+def clip_frac_greater(a: Tuple[int, int], b: Tuple[int, int]) -> bool:
+    """the order of the soft-clip fractions (clip, l_seq): by the fraction, then by the clip; l_seq == 0 is the least"""
+    if a[1] == 0:
+        return False
+    if b[1] == 0:
+        return True
+    x, y = a[0] * b[1], b[0] * a[1]
+    return x > y if x != y else a[0] > b[0]
+
+
+def raised(ip: IndelProps, max_del: int, max_ins: int, clip: Tuple[int, int]) -> IndelProps:
+    """the properties after the members of a locus were read: each maximum rises only where it is already Some (`initial` is false)"""
+    frac = ip.frac_max_softclip
+    if frac is not None and clip[1] > 0:
+        frac = max(frac, clip[0] / clip[1])
+    return IndelProps(ip.insert_size, None if ip.max_del_cigar_len is None else max(ip.max_del_cigar_len, max_del),
+                      None if ip.max_ins_cigar_len is None else max(ip.max_ins_cigar_len, max_ins), frac)
+
+
+@dataclass
+class IndelObs:
+    """a fragment observation of an indel locus before the host-side terms: FragObs and what the side record carries"""
+    obs: FragObs
+    insert_size: int                 # 0 = none
+    len_left: int
+    len_right: int                   # 0 for a single read
+    flags: int = 0
+
+    def key(self):
+        return self.obs.key() + (self.insert_size, self.len_left, self.len_right, self.flags)
+
+
+def indel_evidence(rec: BamRecord, site: IndelSite, li: int, ordinal: int, ref_seq: bytes, window: int) -> RealignEvidence:
+    """the windows of a member of an indel locus: realign_evidence with the locus's own alt allele window"""
+    from . import readwindows as rw
+    from . import realign
+    flag = rec.flag & (0x1 | 0x10 | 0x40)
+
+    def refused(status):
+        return RealignEvidence(li, rw.Evidence(ordinal, status, (0, 0), (0, 0), b"", b"", b"", flag, rec.mapq), b"")
+    try:
+        reg = rw.candidate_region(rec, site.start, site.end, len(ref_seq), window)
+    except ValueError:
+        return refused(rw.LEADING_REFSKIP)
+    if basecalls.aux_tag_strand_info(rec) is not None:
+        return refused(abi.INDELPILEUP_HIT_STRAND_INFO)
+    ro, re_ = reg.read_interval
+    if not reg.overlap or re_ - ro < 1:
+        return refused(rw.NO_OVERLAP)
+    rb, re2 = reg.ref_interval
+    rb = min(rb, re2)
+    return RealignEvidence(li, rw.Evidence(ordinal, 0, (ro, re_), (rb, re2), rec.seq[ro:re_].upper(), bytes(rec.qual[ro:re_]),
+                                           realign.ref_allele(ref_seq, rb, re2).upper(), flag, rec.mapq), bytes(site.locus.alt_allele))
+
+
+def indel_fragment_observation(left: Tuple[int, BamRecord], right: Optional[Tuple[int, BamRecord]], site: IndelSite, li: int, max_mapq: int,
+                               has_insert_size: bool, hits: Dict) -> Optional[IndelObs]:
+    """is_valid_evidence and evidence_to_observation of a deletion / insertion for one candidate fragment; `hits`: {(ordinal, locus):
+    Hit} of the realigned members (realigned_hit).  The insert-size term is not in it: isize_support adds it."""
+    from .readwindows import overlaps
+    lo, lr = left
+    with_isize = right is not None and site.kind == "deletion" and has_insert_size
+    if right is not None:
+        if lr.mapq == 0 or right[1].mapq == 0:
+            return None
+        if not overlaps(lr, site.start, site.end) and not overlaps(right[1], site.start, site.end):
+            return None
+        if with_isize:
+            c = centerpoint(site.start, site.end - site.start)
+            if not (lr.pos < c and right[1].end_pos() > c):
+                return None
+    elif not overlaps(lr, site.start, site.end):
+        return None
+    h = hits[(lo, li)]
+    if right is not None:
+        h = basecalls.merge(h, hits[(right[0], li)])
+    status = h.status
+    if status:
+        h = Hit(li, lo, 0.0, 0.0, abi.STRAND_NONE, None, 0, 0, 0, status)
+    elif h.strand == abi.STRAND_NONE:
+        return None
+    orient = record_orientation(lr)
+    if right is not None:
+        o2 = record_orientation(right[1])
+        if ORIENT_INVALID in (orient, o2):
+            orient = ORIENT_INVALID
+        elif orient != o2:
+            orient = abi.FRAG_ORIENT_NONE
+    if orient == ORIENT_INVALID:
+        status |= INVALID_RO
+        orient = abi.FRAG_ORIENT_NONE
+    recs = [lr] + ([right[1]] if right is not None else [])
+    min_mapq = min(r.mapq for r in recs)
+    ob = FragObs(h.prob_ref, h.prob_alt, lo, right[0] if right is not None else None, None, 0, sum(len(r.seq) for r in recs), min_mapq, orient, h.strand,
+                 any(softclipped(r) for r in recs), bool(lr.flag & 0x1), min_mapq == max_mapq, any(has_xa(r) for r in recs), status,
+                 [a for r in recs for a in alt_loci(r)])
+    isz = estimate_insert_size(lr, right[1]) if with_isize else 0
+    return IndelObs(ob, isz, len(lr.seq), len(right[1].seq) if right is not None else 0, abi.FRAGPILEUP_INDEL_NONPOSITIVE_ISIZE if with_isize and isz <= 0 else 0)
+
+
+@dataclass
+class IndelRestated:
+    per_locus: List[List[IndelObs]]
+    n_members: List[int]
+    maxima: List[Tuple[int, int, Tuple[int, int]]]          # per locus (max D, max I, (clip, l_seq))
+    evidences: List[RealignEvidence]                        # record-major, loci ascending within a record
+    n_records: int = 0
+    n_rejected: int = 0
+    bad_records: List[int] = field(default_factory=list)
+
+
+def restate_indel(records: Sequence[BamRecord], sites: Sequence[IndelSite], props: Props, has_insert_size: bool, spec: RealignSpec, ref_seqs: Dict[int, bytes],
+                  device="cpu", first_ordinal: int = 0) -> IndelRestated:
+    """The fragment observations of deletion / insertion loci (sorted by (ref_id, start)) from `records` in file order, before the
+    host-side terms: what the indel session of the kernels computes, restated."""
+    out = IndelRestated([[] for _ in sites], [0] * len(sites), [(0, 0, (0, 0))] * len(sites), [], len(records))
+    good = []
+    for k, rec in enumerate(records):
+        if not basecalls.is_valid_record(rec.flag):
+            out.n_rejected += 1
+        elif basecalls.record_is_bad(rec):
+            out.bad_records.append(first_ordinal + k)
+        elif rec.ref_id >= 0 and rec.pos >= 0:
+            good.append((first_ordinal + k, rec))
+    recs_of = []
+    for o, rec in good:
+        for li, site in enumerate(sites):
+            if is_member(rec, site, props.window):
+                out.evidences.append(indel_evidence(rec, site, li, o, ref_seqs[site.ref_id], spec.window))
+                recs_of.append(rec)
+    dist, lnp = score_pairs(evidence_pair_batch(out.evidences), spec, device)
+    hits = {}
+    for k, (e, rec) in enumerate(zip(out.evidences, recs_of)):
+        e.ln_ref, e.ln_alt, e.dist_ref, e.dist_alt = float(lnp[2 * k]), float(lnp[2 * k + 1]), int(dist[2 * k]), int(dist[2 * k + 1])
+        hits[(e.ev.record, e.locus)] = realigned_hit(e, rec)
+    for li, site in enumerate(sites):
+        members = [(o, r) for o, r in good if is_member(r, site, props.window)]
+        out.n_members[li] = len(members)
+        md, mi, mc = 0, 0, (0, 0)
+        cand: Dict[bytes, List] = {}
+        for o, rec in members:
+            d, i, s = cigar_maxima(rec)
+            md, mi = max(md, d), max(mi, i)
+            if s and len(rec.seq) and clip_frac_greater((s, len(rec.seq)), mc):
+                mc = (s, len(rec.seq))
+            name = rec.raw_name if rec.raw_name is not None else rec.qname.encode()
+            c = cand.get(name)
+            if c is None:
+                cand[name] = [(o, rec), None]
+                continue
+            lf, f = c[0][1].flag, rec.flag
+            if (lf & 0x40 and f & 0x40) and (lf & 0x80 and f & 0x80):
+                continue
+            c[1] = (o, rec)
+        out.maxima[li] = (md, mi, mc)
+        for name in sorted(cand):
+            ob = indel_fragment_observation(cand[name][0], cand[name][1], site, li, props.max_mapq, has_insert_size, hits)
+            if ob is not None:
+                out.per_locus[li].append(ob)
+    return out
+
+
+def device_indel_observations(bams, sites: Sequence[IndelSite], props: Props, has_insert_size: bool, spec: RealignSpec, fasta: str, device: int = 0,
+                              member_capacity: Optional[int] = None, name_capacity: Optional[int] = None, key_capacity: Optional[int] = None,
+                              evidence_capacity: Optional[int] = None, window_bytes: int = 0, pair_byte_limit: int = 0, retry: bool = True):
+    """(observations abi.FRAGPILEUP_OBS_DTYPE, their side records abi.FRAGPILEUP_INDEL_OBS_DTYPE, locus records abi.FRAGPILEUP_LOCUS_DTYPE,
+    per-locus maxima abi.FRAGPILEUP_INDEL_LOCUS_DTYPE, abi.FragPileupCounts, evidences abi.INDELPILEUP_HIT_DTYPE record-major,
+    abi.FragPileupRealignCounts) from the kernels (vlr_fragpileup_open_indel).  `sites` sorted by (ref_id, start).  An overflow of a
+    capacity is retried once with the needed ones unless retry=False."""
+    import ctypes as C
+    from . import engine
+    from . import realign as rl
+    from .readwindows import MODES
+    L = engine.lib()
+    if isinstance(bams, str):
+        bams = [bams]
+    n = len(sites)
+    kinds = {"deletion": abi.INDELPILEUP_DELETION, "insertion": abi.INDELPILEUP_INSERTION, "replacement": abi.INDELPILEUP_REPLACEMENT}
+    ref_id = np.array([s.ref_id for s in sites], np.int32)
+    start = np.array([s.start for s in sites], np.int64)
+    end = np.array([s.end for s in sites], np.int64)
+    kind = np.array([kinds[s.kind] for s in sites], np.uint8)
+    alt_off = np.zeros(n + 1, np.uint64)
+    alt_off[1:] = np.cumsum([len(s.locus.alt_allele) for s in sites])
+    altb = np.frombuffer(b"".join(bytes(s.locus.alt_allele) for s in sites) or b"\0", np.uint8).copy()
+    mcap = int(member_capacity) if member_capacity is not None else max(1 << 16, 256 * n)
+    ncap = int(name_capacity) if name_capacity is not None else max(1 << 20, 4096 * n)
+    kcap = int(key_capacity) if key_capacity is not None else max(1 << 16, 256 * n)
+    ecap = int(evidence_capacity) if evidence_capacity is not None else mcap
+    gap = (spec.gap or rl.GapParams()).as_array()
+    hop = (spec.hop or rl.HopParams()).as_array() if spec.mode == "homopolymer" else None
+    while True:
+        h = C.c_void_p()
+        engine._check(L.vlr_fragpileup_open_indel(int(device), n, ref_id.ctypes.data, start.ctypes.data, end.ctypes.data, kind.ctypes.data, alt_off.ctypes.data,
+                                                  altb.ctypes.data, int(props.window), int(props.max_mapq), int(props.max_read_len), mcap, ncap, kcap, int(window_bytes),
+                                                  fasta.encode(), int(spec.window), MODES[spec.mode], gap, hop, ecap, int(pair_byte_limit), int(bool(has_insert_size)),
+                                                  C.byref(h)))
+        try:
+            for b in bams:
+                engine._check(L.vlr_fragpileup_add_bam(h, b.encode()))
+            res = abi.FragPileupCounts()
+            engine._check(L.vlr_fragpileup_result(h, C.byref(res)))
+            if res.status & abi.FRAGPILEUP_GUARD_DAMAGED:
+                raise FragPileupError("the guard words behind a buffer of the fragment session changed")
+            rres = abi.FragPileupRealignCounts()
+            engine._check(L.vlr_fragpileup_realign_result(h, C.byref(rres)))
+            over = abi.FRAGPILEUP_ANY_OVERFLOW | abi.FRAGPILEUP_EVIDENCE_OVERFLOW
+            if res.status & over and retry:
+                mcap, ncap, kcap = max(mcap, int(res.needed_members)), max(ncap, int(res.needed_name_bytes)), max(kcap, int(res.needed_keys))
+                ecap = max(ecap, int(rres.needed_evidences))
+                retry = False
+                continue
+            obs = np.zeros(int(res.n_obs), abi.FRAGPILEUP_OBS_DTYPE)
+            obx = np.zeros(int(res.n_obs), abi.FRAGPILEUP_INDEL_OBS_DTYPE)
+            loc = np.zeros(n, abi.FRAGPILEUP_LOCUS_DTYPE)
+            lox = np.zeros(n, abi.FRAGPILEUP_INDEL_LOCUS_DTYPE)
+            ev = np.zeros(int(rres.n_evidences), abi.INDELPILEUP_HIT_DTYPE)
+            if not res.status & over:
+                engine._check(L.vlr_fragpileup_read(h, obs.ctypes.data, len(obs), loc.ctypes.data, n))
+                engine._check(L.vlr_fragpileup_read_indel(h, obx.ctypes.data, len(obx), lox.ctypes.data, n))
+                if len(ev):
+                    engine._check(L.vlr_fragpileup_read_realigned(h, ev.ctypes.data, len(ev)))
+            return obs, obx, loc, lox, res, ev, rres
+        finally:
+            L.vlr_fragpileup_close(h)
+
+
+def indel_obs_from_arrays(a: np.ndarray, x: np.ndarray) -> List[IndelObs]:
+    return [IndelObs(o, int(r["insert_size"]), int(r["len_left"]), int(r["len_right"]), int(r["flags"])) for o, r in zip(obs_from_array(a), x)]
+
+
+def indel_table_of(obs: Sequence[IndelObs], site: IndelSite, props: Props, ip: IndelProps, t: Tables, omit_mapq_adjustment: bool = False) -> ObsTable:
+    """The processed pileup of an indel candidate from its fragment observations: the insert-size term merged into the supports
+    (deletion.rs:253-257: strand none, so nothing else changes), prob_sample_alt, then `process` as for every candidate.  `ip`: the
+    properties after this candidate's members were read."""
+    memo: Dict = {}
+    finished, psa = [], []
+    for io in obs:
+        o = io.obs
+        if o.status & REALIGN_STRAND_INFO:     # (every member of an indel candidate is realigned, with or without an indel operation of its own)
+            raise RealignStrandInfo("record %d%s carries an SI:Z tag: REALIGN_STRAND_INFO (every record at an indel candidate is realigned, and strand "
+                                    "information over the realigned interval is not built)" % (o.left, "" if o.right is None else " or its mate, record %d," % o.right))
+        raise_for_status(o)
+        if io.flags & abi.FRAGPILEUP_INDEL_NONPOSITIVE_ISIZE:
+            raise NonPositiveInsertSize("bug: insert size %d is smaller than zero (records %d and %d)" % (io.insert_size, o.left, o.right))
+        if io.insert_size:
+            p_ref, p_alt = isize_support(io.insert_size, site.length, ip)
+            o = FragObs(o.prob_ref + p_ref, o.prob_alt + p_alt, *o.key()[2:], alt_loci=o.alt_loci, alt_locus=o.alt_locus)
+        finished.append(o)
+        psa.append(prob_sample_alt(site, io.len_left, io.len_right if o.right is not None else None, ip, memo))
+    tab = table_of(finished, props, t, omit_mapq_adjustment, None)
+    tab.prob_sample_alt = np.array(psa, float)
+    return tab
+
+
+def indel_site(seq: bytes, ref_id: int, pos: int, ref: bytes, alt: bytes, window: int, what: str) -> IndelSite:
+    """the deletion / insertion candidate `what` (for messages), or the refusal that names it"""
+    from .readwindows import indel_locus
+    loc = indel_locus(seq.upper(), pos, ref, alt, window)
+    if loc.kind == "replacement":
+        raise PreprocessError("candidate %s is a replacement: only deletions (ALT = the first base of REF) and insertions (REF = the first base of ALT) are built" % what)
+    if loc.end - loc.start > MAX_INDEL_LEN or abs(loc.len_diff) > MAX_INDEL_LEN:
+        raise PreprocessError("candidate %s: an indel of %d bases is longer than the %d a fragment session takes" % (what, abs(loc.len_diff), MAX_INDEL_LEN))
+    return IndelSite(ref_id, loc)
+
+
+def indel_tables(bams, fasta: str, sites: Sequence[IndelSite], what: Sequence[str], props: Props, ip: IndelProps, spec: RealignSpec, device=0,
+                 omit_mapq_adjustment: bool = False, window_bytes: int = 0, ref_seqs: Optional[Dict[int, bytes]] = None, records=None) -> List[ObsTable]:
+    """Per deletion / insertion candidate, in the order given (the order of the candidate file: the running maxima follow it), its
+    processed pileup.  device="cpu": the restatement with the CPU pair HMMs; a device number: the kernels."""
+    for s, w in zip(sites, what):
+        if s.kind == "deletion" and not fetches_merge(s.start, s.end, props.window):
+            raise PreprocessError("candidate %s: the three fetch loci of the deletion (start, centerpoint, end - 1) do not merge into one fetch with a window of %d; "
+                                  "deletions with more than one fetch are not built" % (w, props.window))
+    order = sorted(range(len(sites)), key=lambda k: (sites[k].ref_id, sites[k].start))
+    sorted_sites = [sites[k] for k in order]
+    has_isize = ip.insert_size is not None
+    per: List[Optional[List[IndelObs]]] = [None] * len(sites)
+    maxima: List = [None] * len(sites)
+    t = basecalls.TABLES if device == "cpu" else basecalls.library_tables()
+    host = list(range(len(order)))
+    if device != "cpu":
+        obs, obx, loc, lox, res, _, _ = device_indel_observations(bams, sorted_sites, props, has_isize, spec, fasta, int(device), window_bytes=window_bytes)
+        blist = [bams] if isinstance(bams, str) else list(bams)
+        if res.status & abi.FRAGPILEUP_BAD_RECORD:
+            raise FragPileupError("%s: record %d is malformed" % (blist[0], int(res.first_bad_record)))
+        if res.status & (abi.FRAGPILEUP_ANY_OVERFLOW | abi.FRAGPILEUP_EVIDENCE_OVERFLOW):
+            raise FragPileupError("%s: the members or evidences do not fit the buffers of the fragment session" % blist[0])
+        deep = abi.FRAGPILEUP_LOCUS_TOO_MANY_MEMBERS | abi.FRAGPILEUP_LOCUS_TOO_MANY_ALT_LOCI
+        host = []
+        for j, k in enumerate(order):
+            maxima[k] = (int(lox[j]["max_del"]), int(lox[j]["max_ins"]), (int(lox[j]["max_clip"]), int(lox[j]["max_clip_l_seq"])))
+            if loc[j]["status"] & deep:
+                host.append(j)
+                continue
+            o0 = int(loc[j]["obs_offset"])
+            per[k] = indel_obs_from_arrays(obs[o0:o0 + int(loc[j]["n_obs"])], obx[o0:o0 + int(loc[j]["n_obs"])])
+    if host:   # the restatement: everything on the CPU path, the flagged loci of the device path (scored on the device)
+        blist = [bams] if isinstance(bams, str) else list(bams)
+        recs = records() if records is not None else [r for b in blist for r in read_bam(b)[1]]      # (`records`: the caller's, read once)
+        if ref_seqs is None:
+            raise ValueError("the restatement needs the contigs of the loci (ref_seqs)")
+        rs = restate_indel(recs, [sorted_sites[j] for j in host], props, has_isize, spec, ref_seqs, device)
+        if rs.bad_records:
+            raise FragPileupError("%s: record %d is malformed" % (blist[0], rs.bad_records[0]))
+        for i, j in enumerate(host):
+            per[order[j]], maxima[order[j]] = rs.per_locus[i], rs.maxima[i]
+    out = []
+    for k, site in enumerate(sites):    # candidate order: the properties rise as the reference reads
+        ip = raised(ip, *maxima[k])
+        out.append(indel_table_of(per[k], site, props, ip, t, omit_mapq_adjustment))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- preprocess variants
@@ -835,10 +1409,13 @@ def read_candidates(path: str) -> List[Tuple[str, int, str, str, str]]:
 
 def preprocess_variants(reference: str, candidates: str, bam: str, output: str, alignment_properties: Optional[str] = None, device=0,
                         atomic_candidate_variants: bool = False, omit_mapq_adjustment: bool = False, max_depth: int = 200,
-                        score_indel_reads_from_alignment: bool = False, warn=None, realign: Optional[RealignSpec] = None) -> int:
+                        score_indel_reads_from_alignment: bool = False, warn=None, realign: Optional[RealignSpec] = None,
+                        indel_candidates: Optional[RealignSpec] = None) -> int:
     """`preprocess variants` for SNV / MNV candidates of one sample: the observation BCF `output` (format v15) that `call variants`
     reads.  Returns the number of records written.  `realign` (--realign-indel-reads): indel-bearing reads over a candidate are
-    realigned as the reference does by default; its gap / hop parameters default to those of the alignment properties."""
+    realigned as the reference does by default; its gap / hop parameters default to those of the alignment properties.
+    `indel_candidates` (--indel-candidates): deletion and insertion candidates are built too, one observation per fragment (the
+    section "deletion and insertion candidates" above); the file may mix them with SNVs / MNVs, records keep the candidate order."""
     import json
     from . import ingest
     if not atomic_candidate_variants:
@@ -848,7 +1425,9 @@ def preprocess_variants(reference: str, candidates: str, bam: str, output: str, 
     cands = []
     for chrom, pos, rid, ref, alt in sites:
         sym = alt.startswith("<") or "[" in alt or "]" in alt or alt in ("*", ".")
-        if sym or len(ref) != len(alt) or not ref:
+        if indel_candidates is not None and (sym or not ref or not alt):
+            raise PreprocessError("candidate %s:%d %s>%s is a symbolic or breakend allele: only SNVs, MNVs, deletions and insertions are built" % (chrom, pos, ref, alt))
+        if indel_candidates is None and (sym or len(ref) != len(alt) or not ref):
             raise PreprocessError("candidate %s:%d %s>%s is not an SNV or MNV: indel, structural and breakend candidates are not built" % (chrom, pos, ref, alt))
         cands.append((chrom, pos - 1, ref.encode(), alt.encode()))
     if realign is not None and score_indel_reads_from_alignment:
@@ -861,9 +1440,12 @@ def preprocess_variants(reference: str, candidates: str, bam: str, output: str, 
     props = props_of(pj)
     if realign is not None and realign.gap is None and realign.hop is None:
         realign = RealignSpec(realign.window, realign.mode, *gap_hop_of(pj))
+    if indel_candidates is not None and indel_candidates.gap is None and indel_candidates.hop is None:
+        indel_candidates = RealignSpec(indel_candidates.window, indel_candidates.mode, *gap_hop_of(pj))
     try:
         tabs = observations(bam, reference, cands, props, device=device, omit_mapq_adjustment=omit_mapq_adjustment,
-                            realign_indel_reads=not score_indel_reads_from_alignment, realign=realign)
+                            realign_indel_reads=not score_indel_reads_from_alignment, realign=realign, indel_candidates=indel_candidates,
+                            indel_props=indel_props_of(pj) if indel_candidates is not None else None)
     except NeedsRealign as e:
         raise PreprocessError(str(e) + "; --score-indel-reads-from-alignment scores such reads as they are aligned, --realign-indel-reads realigns them") from e
     deep = sum(1 for t in tabs if len(t) > max_depth)
