@@ -1,5 +1,6 @@
 """The stand-alone host programs of csrc/ (vlr_*_host.cpp: a kernel's header compiled for the CPU, with a main of its own) built under
-the sanitizers, for test_basepileup_host.py, test_indelpileup_host.py and test_fragpileup_host.py.  A plain helper module: the `program`
+the sanitizers, for test_basepileup_host.py, test_indelpileup_host.py, test_fragpileup_host.py, test_fragrealign_host_program.py and
+test_fragment_indel_host.py.  A plain helper module: the `program`
 fixtures stay in those files."""
 import os
 import shutil

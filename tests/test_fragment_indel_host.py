@@ -1,5 +1,5 @@
 """Deletion and insertion candidates of `preprocess variants` on the CPU (no GPU): the restatement of varlociraptor_amd/fragments.py with
-expectations stated from the records, and csrc/vlr_fragindel_host.cpp — the indel arms of csrc/vlr_fragpileup.h compiled with
+expectations stated from the records, and csrc/vlr_fragpileup_host.cpp — the indel arms of csrc/vlr_fragpileup.h compiled with
 -fsanitize=address,undefined into a stand-alone program (nothing is preloaded into any process; every record, contig, alt window,
 member array and gathered window lies in a heap block of exactly its size) — against that restatement, f64 compared with ==."""
 import math
@@ -171,7 +171,7 @@ def test_running_maxima_cross_the_feasible_bases_boundary():
 # ---------------------------------------------------------------------------------------------- the header's text under the sanitizers
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    return host_program.build(tmp_path_factory, "vlr_fragindel_host")
+    return host_program.build(tmp_path_factory, "vlr_fragpileup_host")
 
 
 def run_program(program, tmp, contigs, sites, records, props, has_isize, spec, evidences):

@@ -168,6 +168,37 @@ def test_determinism_and_capacities(oracle, tmp_path, case):
     assert again[4].status == 0 and again[0].tobytes() == base[0].tobytes()
 
 
+def test_member_name_and_key_capacities_at_the_edge(oracle, tmp_path, case):
+    """The Side records of an indel session are sized by the member capacity, the names and the alt-locus keys by theirs: each of the
+    three one short of what the input needs is reported as that overflow alone (no guard word behind a buffer changed) with the needed
+    sizes counted on; all three exactly at need, and all three at 1 with the retry, give what a roomy session gives.  (The records of
+    `case` carry no XA tag, so two that do stand in front of them: a key capacity of need - 1 = -1 would be a refused argument.  The
+    counts are compared field by field without their `seconds`, which are timers.)"""
+    from varlociraptor_amd import alignprops
+    ref, sites, recs = case
+    xa = [ic.read_at(ref, 40, "xa%d" % k, False, aux=alignprops.aux_field("XA", "Z", "i2,+%d,40M,0;i3,-77,40M,1;" % (100 + k))) for k in range(2)]
+    bam, fa = bc.write_case(tmp_path, "caps", {"i1": ref}, xa + recs)        # (the reads of `case` start at 40 or behind it: still sorted)
+    roomy = device(bam, sites, fa=fa)
+    need = {"member_capacity": int(roomy[4].needed_members), "name_capacity": int(roomy[4].needed_name_bytes), "key_capacity": int(roomy[4].needed_keys)}
+    n_ev = int(roomy[6].needed_evidences)
+    assert roomy[4].status == 0 and min(need.values()) > 0 and len(roomy[0]) > 60
+
+    def fields(c):
+        return [(f, getattr(c, f)) for f, _ in c._fields_ if f != "seconds"]
+
+    def assert_equals_roomy(got):
+        for k in (0, 1, 2, 3, 5):
+            assert got[k].dtype == roomy[k].dtype and got[k].tobytes() == roomy[k].tobytes(), k
+        assert fields(got[4]) == fields(roomy[4]) and fields(got[6]) == fields(roomy[6])
+    for cap, bit in (("member_capacity", abi.FRAGPILEUP_MEMBER_OVERFLOW), ("name_capacity", abi.FRAGPILEUP_NAME_OVERFLOW), ("key_capacity", abi.FRAGPILEUP_KEY_OVERFLOW)):
+        res = device(bam, sites, fa=fa, evidence_capacity=n_ev, retry=False, **dict(need, **{cap: need[cap] - 1}))[4]
+        print(cap, need[cap] - 1, "status", res.status)
+        assert res.status == bit and not res.status & abi.FRAGPILEUP_GUARD_DAMAGED, (cap, res.status)
+        assert (int(res.needed_members), int(res.needed_name_bytes), int(res.needed_keys)) == tuple(need.values()), cap
+    assert_equals_roomy(device(bam, sites, fa=fa, evidence_capacity=n_ev, retry=False, **need))
+    assert_equals_roomy(device(bam, sites, fa=fa, member_capacity=1, name_capacity=1, key_capacity=1))
+
+
 def test_refusals(oracle, tmp_path):
     ref = ic.contig(6000, 2)
     ok = [("i1", 100, ref[100:100 + abi.FRAGPILEUP_MAX_INDEL_LEN + 1], ref[100:101])]

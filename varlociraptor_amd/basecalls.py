@@ -440,6 +440,14 @@ class BasePileupError(ValueError):
     pass
 
 
+def locus_arrays(loci: Sequence[Locus]):
+    """(ref_id, start, length, kind, ref bases, alt bases) of `loci` as the open calls of the SNV / MNV sessions take them"""
+    def bases(attr):
+        return np.frombuffer(b"".join(getattr(l, attr) for l in loci) or b"\0", np.uint8).copy()
+    return (np.array([l.ref_id for l in loci], np.int32), np.array([l.start for l in loci], np.int64), np.array([len(l.ref) for l in loci], np.int32),
+            np.array([l.kind for l in loci], np.uint8), bases("ref"), bases("alt"))
+
+
 def device_hits(bam: str, loci: Sequence[Locus], device: int = 0, realign_indel_reads: bool = False, hit_capacity: Optional[int] = None,
                 window_bytes: int = 0, retry: bool = True):
     """(hits as a numpy array of abi.BASEPILEUP_HIT_DTYPE, locus-major; abi.BasePileupCounts) from the kernel.  `loci` sorted by
@@ -449,12 +457,7 @@ def device_hits(bam: str, loci: Sequence[Locus], device: int = 0, realign_indel_
     from . import engine
     L = engine.lib()
     n = len(loci)
-    ref_id = np.array([l.ref_id for l in loci], np.int32)
-    start = np.array([l.start for l in loci], np.int64)
-    length = np.array([len(l.ref) for l in loci], np.int32)
-    kind = np.array([l.kind for l in loci], np.uint8)
-    refb = np.frombuffer(b"".join(l.ref for l in loci) or b"\0", np.uint8).copy()
-    altb = np.frombuffer(b"".join(l.alt for l in loci) or b"\0", np.uint8).copy()
+    ref_id, start, length, kind, refb, altb = locus_arrays(loci)
     cap = int(hit_capacity) if hit_capacity is not None else max(1 << 16, 64 * n)
     while True:
         h = C.c_void_p()

@@ -1,6 +1,6 @@
 // vlr_bamsession.h — what the device sessions over BAM records have in common (vlr_basepileup.hip, vlr_indelpileup.hip,
 // vlr_fragpileup.hip; the error macro, the buffer helpers and the contig loader also serve vlr_bamstats.hip): the error macro, the
-// device buffer helpers, the one-workgroup prefix sum, the state every session keeps, the wiring of a file into the device reader
+// device buffer helpers and the owner of a session's or a pass's buffers, the one-workgroup prefix sum, the state every session keeps, the wiring of a file into the device reader
 // (vlr_bamstream.h), the bad-record rule, the host's locus-major sort and the SNV / MNV loci on the device.  Structs and free
 // functions; every session keeps its own kernels, the body of its run_chunk and its open / result / read.  Internal to those .hip files.
 #pragma once
@@ -62,6 +62,29 @@ template <class T> int guard_intact(const T* d, size_t n, bool* ok) {
     for (uint8_t b : g) if (b != (uint8_t)kGuardByte) *ok = false;
     return VLR_OK;
 }
+
+// The device buffers of a session, or the scratch of one pass: handed out here and remembered here, the guarded ones with the bytes in
+// front of their guard, so that the check of the guards and the release name no buffer and no size again.
+struct Buffers {
+    struct Buf { void* p; size_t bytes; bool guard; };
+    std::vector<Buf> bufs;
+    template <class T> int upload(T*& d, const T* h, size_t n) { const int rc = vlr_bam::upload(d, h, n); keep(d, 0, false); return rc; }
+    template <class T> int zeros(T*& d, size_t n) { const int rc = vlr_bam::zeros(d, n); keep(d, 0, false); return rc; }
+    template <class T> int guarded(T*& d, size_t n) { const int rc = vlr_bam::guarded(d, n); keep(d, n * sizeof(T), true); return rc; }
+    // *ok = false when the guard bytes behind any guarded buffer changed; the first HIP error ends the check
+    int guards_intact(bool* ok) const {
+        for (const Buf& b : bufs) {
+            const int rc = b.guard ? guard_intact((const uint8_t*)b.p, b.bytes, ok) : VLR_OK;
+            if (rc != VLR_OK) return rc;
+        }
+        return VLR_OK;
+    }
+    void free() {
+        for (const Buf& b : bufs) (void)hipFree(b.p);
+        bufs.clear();
+    }
+    void keep(void* p, size_t bytes, bool guard) { if (p) bufs.push_back(Buf{p, bytes, guard}); }   // (a failed step may have allocated: it is released too)
+};
 
 inline int use_device(int device) {
     int ndev = 0;

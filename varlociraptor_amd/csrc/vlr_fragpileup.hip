@@ -50,7 +50,8 @@
 // Bounds: a record is read only after vlr_bp::decode checked it; members[k] is written for k < member capacity, names[k] for
 // k < name capacity, keys[k] for k < key capacity; perm / tmp / rank / the pair arrays are sized by the member count and every index into
 // them is below a locus' count, which sums to it; the output is sized by the scanned observation count; guard bytes behind every one of
-// these buffers are checked at the end (vlr_bam::guarded / guard_intact).  The session's common state, the wiring of a file into the
+// these buffers are checked at the end: the session and each pass own their buffers through a vlr_bam::Buffers, which checks the guards
+// of all of them in one call and releases them.  The session's common state, the wiring of a file into the
 // device reader and the SNV / MNV loci on the device are vlr_bamsession.h's.
 #include <cstring>
 
@@ -518,6 +519,7 @@ struct vlr_fragpileup : vlr_bam::Session {
     uint64_t member_cap = 0, name_cap = 0, key_cap = 0, coeff = 1;
     // device state (the record arrays of the base: [K_N][rec_cap] u32 counts and their offsets; d_total[K_N])
     vlr_bp::DeviceLoci dl;
+    vlr_bam::Buffers buf;                // owns every d_ below but d_src, which grows
     vlr_fp::Member* d_members = nullptr;
     uint8_t* d_names = nullptr;
     vlr_fp::AltKey *d_keys = nullptr, *d_major_key = nullptr;
@@ -561,10 +563,7 @@ struct vlr_fragpileup : vlr_bam::Session {
 
 namespace vlr_fp {
 using vlr_bam::bfail;
-using vlr_bam::guard_intact;
-using vlr_bam::guarded;
 using vlr_bam::now_s;
-using vlr_bam::zeros;
 
 // a realigning session: the contig table of a file; every locus must lie inside its contig
 int on_header(vlr_fragpileup* s, const std::vector<std::string>& names, const char* path) {
@@ -664,6 +663,7 @@ int realign_pass(vlr_fragpileup* s) {
         if (gx[p] > gx[p + 1] || gy[p] > gy[p + 1] || gx[p + 1] > s->x_cap || gy[p + 1] > s->y_cap) return bfail(VLR_ERR_HIP, "vlr_fragpileup_result: the pair offsets of evidence %zu are not ascending", p / 2);
     uint32_t *d_xoff = nullptr, *d_yoff = nullptr; int32_t *d_band = nullptr, *d_dist = nullptr; double *d_lnp = nullptr, *d_norm = nullptr;
     std::vector<uint32_t> xo, yo;
+    vlr_bam::Buffers scratch;
     auto body = [&]() -> int {
         int rc;
         hipStream_t st = 0;
@@ -673,8 +673,8 @@ int realign_pass(vlr_fragpileup* s) {
             const size_t np = 2 * (e1 - e0);
             if (gx[2 * e1] - gx[2 * e0] >= (1ull << 32) || gy[2 * e1] - gy[2 * e0] >= (1ull << 32)) return bfail(VLR_ERR_UNSUPPORTED, "evidence %zu: its windows take 4 GiB or more", e0);
             if (!d_xoff) {   // sized once, by the first (largest possible) range: at most all pairs
-                if ((rc = guarded(d_xoff, 2 * ne + 1)) != VLR_OK || (rc = guarded(d_yoff, 2 * ne + 1)) != VLR_OK || (rc = guarded(d_band, 2 * ne)) != VLR_OK ||
-                    (rc = guarded(d_dist, 2 * ne)) != VLR_OK || (rc = guarded(d_lnp, 2 * ne)) != VLR_OK)
+                if ((rc = scratch.guarded(d_xoff, 2 * ne + 1)) != VLR_OK || (rc = scratch.guarded(d_yoff, 2 * ne + 1)) != VLR_OK ||
+                    (rc = scratch.guarded(d_band, 2 * ne)) != VLR_OK || (rc = scratch.guarded(d_dist, 2 * ne)) != VLR_OK || (rc = scratch.guarded(d_lnp, 2 * ne)) != VLR_OK)
                     return rc;
             }
             xo.resize(np + 1); yo.resize(np + 1);
@@ -700,24 +700,18 @@ int realign_pass(vlr_fragpileup* s) {
             norm[2 * e] = s->ev[e].ln_ref; norm[2 * e + 1] = s->ev[e].ln_alt;
             normalize_support(&norm[2 * e], &norm[2 * e + 1]);
         }
-        if ((rc = guarded(d_norm, 2 * ne)) != VLR_OK) return rc;
+        if ((rc = scratch.guarded(d_norm, 2 * ne)) != VLR_OK) return rc;
         VLR_HIP_OK(hipMemcpy(d_norm, norm.data(), 2 * ne * 8, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(frag_apply_kernel, dim3((unsigned)((ne + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, s->d_ev, s->d_evm, d_norm, (uint64_t)ne,
                            std::min<uint64_t>(s->n_members, s->member_cap), s->d_members);
         if ((rc = vlr_ip::sync_stage(st, s->rt[3], t0)) != VLR_OK) return rc;
         bool ok = true;
-        rc = guard_intact(d_xoff, 2 * ne + 1, &ok);
-        if (rc == VLR_OK) rc = guard_intact(d_yoff, 2 * ne + 1, &ok);
-        if (rc == VLR_OK) rc = guard_intact(d_band, 2 * ne, &ok);
-        if (rc == VLR_OK) rc = guard_intact(d_dist, 2 * ne, &ok);
-        if (rc == VLR_OK) rc = guard_intact(d_lnp, 2 * ne, &ok);
-        if (rc == VLR_OK) rc = guard_intact(d_norm, 2 * ne, &ok);
+        rc = scratch.guards_intact(&ok);
         if (rc == VLR_OK && !ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
         return rc;
     };
     const int rc = body();
-    void* p[] = {d_xoff, d_yoff, d_band, d_dist, d_lnp, d_norm};
-    for (void* q : p) if (q) (void)hipFree(q);
+    scratch.free();
     return rc;
 }
 
@@ -725,14 +719,15 @@ int fragment_pass(vlr_fragpileup* s) {
     const size_t nm = (size_t)s->n_members, nl = (size_t)s->n_loci;
     uint32_t *d_perm = nullptr, *d_left = nullptr, *d_right = nullptr; uint16_t* d_rank = nullptr; vlr_fragpileup_obs *d_tmp = nullptr, *d_out = nullptr;
     vlr_fragpileup_indel_obs *d_tmpx = nullptr, *d_outx = nullptr;   // an indel session: beside d_tmp and d_out
+    vlr_bam::Buffers scratch;
     int rc = VLR_OK;
     auto step = [&](int r) { if (rc == VLR_OK) rc = r; };
-    if (s->indel) step(guarded(d_tmpx, nm));
-    step(guarded(d_perm, nm));
-    step(guarded(d_rank, nm));
-    step(guarded(d_left, nm));
-    step(guarded(d_right, nm));
-    step(guarded(d_tmp, nm));
+    if (s->indel) step(scratch.guarded(d_tmpx, nm));
+    step(scratch.guarded(d_perm, nm));
+    step(scratch.guarded(d_rank, nm));
+    step(scratch.guarded(d_left, nm));
+    step(scratch.guarded(d_right, nm));
+    step(scratch.guarded(d_tmp, nm));
     auto body = [&]() -> int {
         uint64_t total_obs = 0;
         hipLaunchKernelGGL(vlr_bam::scan_kernel<uint32_t>, dim3(1), dim3(kScanThreads), 0, 0, s->d_lcnt, (int64_t)nl, (int64_t)0, s->d_loff, s->d_total);
@@ -751,9 +746,9 @@ int fragment_pass(vlr_fragpileup* s) {
         VLR_HIP_OK(hipMemcpy(&total_obs, s->d_total + 1, 8, hipMemcpyDeviceToHost));
         if (total_obs > nm) return bfail(VLR_ERR_HIP, "vlr_fragpileup_result: more observations than members");
         // the output is sized by the observations, not by the members
-        int r = guarded(d_out, (size_t)total_obs);
+        int r = scratch.guarded(d_out, (size_t)total_obs);
         if (r != VLR_OK) return r;
-        if (s->indel && (r = guarded(d_outx, (size_t)total_obs)) != VLR_OK) return r;
+        if (s->indel && (r = scratch.guarded(d_outx, (size_t)total_obs)) != VLR_OK) return r;
         ip.outx = d_outx;
         if (s->indel)
             hipLaunchKernelGGL(frag_gather_indel_kernel, dim3((unsigned)nl), dim3(kLocusThreads), 0, 0, s->d_members, s->d_keys, d_tmp, d_left, d_right, d_rank, s->d_loff, s->d_lcnt,
@@ -764,15 +759,7 @@ int fragment_pass(vlr_fragpileup* s) {
         VLR_HIP_OK(hipDeviceSynchronize());
         VLR_HIP_OK(hipGetLastError());
         bool ok = true;
-        r = guard_intact(d_perm, nm, &ok);
-        if (r == VLR_OK) r = guard_intact(d_rank, nm, &ok);
-        if (r == VLR_OK) r = guard_intact(d_left, nm, &ok);
-        if (r == VLR_OK) r = guard_intact(d_right, nm, &ok);
-        if (r == VLR_OK) r = guard_intact(d_tmp, nm, &ok);
-        if (r == VLR_OK) r = guard_intact(d_out, (size_t)total_obs, &ok);
-        if (s->indel && r == VLR_OK) r = guard_intact(d_tmpx, nm, &ok);
-        if (s->indel && r == VLR_OK) r = guard_intact(d_outx, (size_t)total_obs, &ok);
-        if (r != VLR_OK) return r;
+        if ((r = scratch.guards_intact(&ok)) != VLR_OK) return r;
         if (!ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
         const double t1 = now_s();
         s->obs.resize((size_t)total_obs);
@@ -796,8 +783,7 @@ int fragment_pass(vlr_fragpileup* s) {
         return VLR_OK;
     };
     if (rc == VLR_OK) rc = body();
-    void* p[] = {d_perm, d_rank, d_left, d_right, d_tmp, d_out, d_tmpx, d_outx};
-    for (void* q : p) if (q) (void)hipFree(q);
+    scratch.free();
     return rc;
 }
 
@@ -872,6 +858,7 @@ int open_impl(const char* api, int device, int64_t n_loci, const int32_t* ref_id
     s->coeff = 10ull * (uint64_t)max_read_len;
     s->locus_rec.assign((size_t)n_loci, vlr_fragpileup_locus{0, 0, 0, VLR_BASEPILEUP_NO_READ_POSITION, 0});
     const size_t nl = (size_t)n_loci;
+    vlr_bam::Buffers& buf = s->buf;
     auto step = [&](int r) { if (rc == VLR_OK) rc = r; };
     if (ro != nullptr) {
         s->realigning = true;
@@ -893,30 +880,31 @@ int open_impl(const char* api, int device, int64_t n_loci, const int32_t* ref_id
             s->max_locus_len = max_locus_len;
             s->x_cap = s->ev_cap * (2 * rw + max_alt_len);
             s->locusx.assign((size_t)n_loci, vlr_fragpileup_indel_locus{0, 0, 0, 0});
-            step(guarded(s->d_sides, (size_t)s->member_cap));
-            step(zeros(s->d_max_del, (size_t)n_loci)); step(zeros(s->d_max_ins, (size_t)n_loci)); step(zeros(s->d_max_clip, (size_t)n_loci));
+            step(buf.guarded(s->d_sides, (size_t)s->member_cap));
+            step(buf.zeros(s->d_max_del, nl)); step(buf.zeros(s->d_max_ins, nl)); step(buf.zeros(s->d_max_clip, nl));
         }
         s->y_cap = s->ev_cap * 2 * (uint64_t)vlr_ip::kMaxPatternLen;
         step(vlr_bam::read_fai(s->ctg.fasta, s->ctg.fai));
-        step(guarded(s->d_ev, (size_t)s->ev_cap));
-        step(guarded(s->d_evm, (size_t)s->ev_cap));
-        step(guarded(s->d_gx, 2 * (size_t)s->ev_cap + 1));
-        step(guarded(s->d_gy, 2 * (size_t)s->ev_cap + 1));
-        step(guarded(s->d_xb, (size_t)s->x_cap));
-        step(guarded(s->d_yb, (size_t)s->y_cap));
-        step(guarded(s->d_yq, (size_t)s->y_cap));
+        const size_t n_off = 2 * (size_t)s->ev_cap + 1;   // the pair offsets of the evidences and their end
+        step(buf.guarded(s->d_ev, (size_t)s->ev_cap));
+        step(buf.guarded(s->d_evm, (size_t)s->ev_cap));
+        step(buf.guarded(s->d_gx, n_off));
+        step(buf.guarded(s->d_gy, n_off));
+        step(buf.guarded(s->d_xb, (size_t)s->x_cap));
+        step(buf.guarded(s->d_yb, (size_t)s->y_cap));
+        step(buf.guarded(s->d_yq, (size_t)s->y_cap));
         // offsets nobody wrote read as empty windows
-        if (rc == VLR_OK && (hipMemset(s->d_gx, 0, (2 * (size_t)s->ev_cap + 1) * 8) != hipSuccess || hipMemset(s->d_gy, 0, (2 * (size_t)s->ev_cap + 1) * 8) != hipSuccess))
+        if (rc == VLR_OK && (hipMemset(s->d_gx, 0, n_off * 8) != hipSuccess || hipMemset(s->d_gy, 0, n_off * 8) != hipSuccess))
             rc = bfail(VLR_ERR_HIP, "%s: hipMemset of the pair offsets failed", api);
     }
     step(vlr_bam::open_session(*s, device, window_bytes, s->k_n));
     step(s->dl.upload(n_loci, ref_id, start, len, kind, base_off, ref_bases, alt_bases));
-    step(zeros(s->d_major_key, nl)); step(zeros(s->d_have_key, nl));
-    step(zeros(s->d_lcnt, nl)); step(zeros(s->d_cursor, nl)); step(zeros(s->d_nobs, nl)); step(zeros(s->d_major, nl)); step(zeros(s->d_lstatus, nl));
-    step(zeros(s->d_loff, nl)); step(zeros(s->d_obsoff, nl));
-    step(guarded(s->d_members, (size_t)s->member_cap));
-    step(guarded(s->d_names, (size_t)s->name_cap));
-    step(guarded(s->d_keys, (size_t)s->key_cap));
+    step(buf.zeros(s->d_major_key, nl)); step(buf.zeros(s->d_have_key, nl));
+    step(buf.zeros(s->d_lcnt, nl)); step(buf.zeros(s->d_cursor, nl)); step(buf.zeros(s->d_nobs, nl)); step(buf.zeros(s->d_major, nl)); step(buf.zeros(s->d_lstatus, nl));
+    step(buf.zeros(s->d_loff, nl)); step(buf.zeros(s->d_obsoff, nl));
+    step(buf.guarded(s->d_members, (size_t)s->member_cap));
+    step(buf.guarded(s->d_names, (size_t)s->name_cap));
+    step(buf.guarded(s->d_keys, (size_t)s->key_cap));
     if (rc != VLR_OK) { vlr_fragpileup_close(s); return rc; }
     *out = s;
     return VLR_OK;
@@ -963,22 +951,8 @@ int vlr_fragpileup_result(vlr_fragpileup* s, vlr_fragpileup_counts* r) {
     if (!s->collected) {
         bool ok = true;
         int rc = vlr_bam::read_counters(*s);
-        if (rc == VLR_OK) rc = guard_intact(s->d_members, (size_t)s->member_cap, &ok);
-        if (rc == VLR_OK) rc = guard_intact(s->d_names, (size_t)s->name_cap, &ok);
-        if (rc == VLR_OK) rc = guard_intact(s->d_keys, (size_t)s->key_cap, &ok);
-        if (s->realigning) {
-            if (rc == VLR_OK) rc = guard_intact(s->d_ev, (size_t)s->ev_cap, &ok);
-            if (rc == VLR_OK) rc = guard_intact(s->d_evm, (size_t)s->ev_cap, &ok);
-            if (rc == VLR_OK) rc = guard_intact(s->d_gx, 2 * (size_t)s->ev_cap + 1, &ok);
-            if (rc == VLR_OK) rc = guard_intact(s->d_gy, 2 * (size_t)s->ev_cap + 1, &ok);
-            if (rc == VLR_OK) rc = guard_intact(s->d_xb, (size_t)s->x_cap, &ok);
-            if (rc == VLR_OK) rc = guard_intact(s->d_yb, (size_t)s->y_cap, &ok);
-            if (rc == VLR_OK) rc = guard_intact(s->d_yq, (size_t)s->y_cap, &ok);
-        }
-        if (s->indel) {
-            if (rc == VLR_OK) rc = guard_intact(s->d_sides, (size_t)s->member_cap, &ok);
-            if (rc == VLR_OK) rc = read_maxima(s);
-        }
+        if (rc == VLR_OK) rc = s->buf.guards_intact(&ok);
+        if (rc == VLR_OK && s->indel) rc = read_maxima(s);
         if (rc != VLR_OK) return rc;
         if (!ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
         if (vlr_bam::bad_record_seen(*s)) s->status |= VLR_FRAGPILEUP_BAD_RECORD;
@@ -1087,9 +1061,8 @@ void vlr_fragpileup_close(vlr_fragpileup* s) {
     vlr_bam::close_session(*s);
     s->dl.free();
     s->ctg.free();
-    void* p[] = {s->d_members, s->d_names, s->d_keys, s->d_major_key, s->d_have_key, s->d_lcnt, s->d_cursor, s->d_nobs, s->d_major, s->d_lstatus, s->d_loff, s->d_obsoff,
-                 s->d_ev, s->d_evm, s->d_gx, s->d_gy, s->d_xb, s->d_yb, s->d_yq, s->d_src, s->d_sides, s->d_max_del, s->d_max_ins, s->d_max_clip};
-    for (void* q : p) if (q) (void)hipFree(q);
+    s->buf.free();
+    if (s->d_src) (void)hipFree(s->d_src);
     delete s;
 }
 

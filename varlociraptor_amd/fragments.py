@@ -512,8 +512,41 @@ def restate(records: Sequence[BamRecord], loci: Sequence[Locus], props: Props, t
 
 
 # ---------------------------------------------------------------------------------------------- the device
-def _bases(loci, attr):
-    return np.frombuffer(b"".join(getattr(l, attr) for l in loci) or b"\0", np.uint8).copy()
+def _capacities(n: int, member_capacity, name_capacity, key_capacity):
+    return (int(member_capacity) if member_capacity is not None else max(1 << 16, 256 * n), int(name_capacity) if name_capacity is not None else max(1 << 20, 4096 * n),
+            int(key_capacity) if key_capacity is not None else max(1 << 16, 256 * n))
+
+
+def _session(L, open_call, args_of, caps, bams, retry: bool, realigning: bool, read):
+    """One fragment session run to its result: open_call(*args_of(member, name, key, evidence capacity), the handle), every BAM added,
+    abi.FragPileupCounts (and abi.FragPileupRealignCounts of a `realigning` session) read, FragPileupError for damaged guards; an
+    overflow of a capacity is retried once with the needed ones while `retry`; then what read(handle, counts, realign counts, fits)
+    returns — fits: no capacity overflowed.  The session is closed whatever happens."""
+    import ctypes as C
+    from . import engine
+    mcap, ncap, kcap, ecap = caps
+    while True:
+        h = C.c_void_p()
+        engine._check(open_call(*args_of(mcap, ncap, kcap, ecap), C.byref(h)))
+        try:
+            for b in [bams] if isinstance(bams, str) else bams:
+                engine._check(L.vlr_fragpileup_add_bam(h, b.encode()))
+            res = abi.FragPileupCounts()
+            engine._check(L.vlr_fragpileup_result(h, C.byref(res)))
+            if res.status & abi.FRAGPILEUP_GUARD_DAMAGED:
+                raise FragPileupError("the guard words behind a buffer of the fragment session changed")
+            rres = abi.FragPileupRealignCounts()
+            if realigning:
+                engine._check(L.vlr_fragpileup_realign_result(h, C.byref(rres)))
+            over = abi.FRAGPILEUP_ANY_OVERFLOW | abi.FRAGPILEUP_EVIDENCE_OVERFLOW
+            if res.status & over and retry:
+                mcap, ncap, kcap = max(mcap, int(res.needed_members)), max(ncap, int(res.needed_name_bytes)), max(kcap, int(res.needed_keys))
+                ecap = max(ecap, int(rres.needed_evidences))
+                retry = False
+                continue
+            return read(h, res, rres, not res.status & over)
+        finally:
+            L.vlr_fragpileup_close(h)
 
 
 def device_observations(bams, loci: Sequence[Locus], props: Props, device: int = 0, realign_indel_reads: bool = False, member_capacity: Optional[int] = None,
@@ -526,21 +559,13 @@ def device_observations(bams, loci: Sequence[Locus], props: Props, device: int =
     `realign` (with `fasta`): indel-bearing reads are realigned in the same pass (vlr_fragpileup_open_realign; realign_indel_reads is
     implied); evidences=True adds (the realigned evidences as abi.INDELPILEUP_HIT_DTYPE, record-major; abi.FragPileupRealignCounts) to
     the result."""
-    import ctypes as C
     from . import engine
     L = engine.lib()
-    if isinstance(bams, str):
-        bams = [bams]
     n = len(loci)
-    ref_id = np.array([l.ref_id for l in loci], np.int32)
-    start = np.array([l.start for l in loci], np.int64)
-    length = np.array([len(l.ref) for l in loci], np.int32)
-    kind = np.array([l.kind for l in loci], np.uint8)
-    refb, altb = _bases(loci, "ref"), _bases(loci, "alt")
-    mcap = int(member_capacity) if member_capacity is not None else max(1 << 16, 256 * n)
-    ncap = int(name_capacity) if name_capacity is not None else max(1 << 20, 4096 * n)
-    kcap = int(key_capacity) if key_capacity is not None else max(1 << 16, 256 * n)
-    ecap = int(evidence_capacity) if evidence_capacity is not None else 1 << 14
+    arrays = basecalls.locus_arrays(loci)
+    head = (int(device), n) + tuple(a.ctypes.data for a in arrays) + (int(bool(realign_indel_reads or realign is not None)), int(props.window), int(props.max_mapq),
+                                                                     int(props.max_read_len))
+    caps = _capacities(n, member_capacity, name_capacity, key_capacity) + (int(evidence_capacity) if evidence_capacity is not None else 1 << 14,)
     if realign is not None:
         from . import realign as rl
         from .readwindows import MODES
@@ -548,43 +573,34 @@ def device_observations(bams, loci: Sequence[Locus], props: Props, device: int =
             raise ValueError("realignment needs the reference (fasta)")
         gap = (realign.gap or rl.GapParams()).as_array()
         hop = (realign.hop or rl.HopParams()).as_array() if realign.mode == "homopolymer" else None
-    while True:
-        h = C.c_void_p()
-        head = (int(device), n, ref_id.ctypes.data, start.ctypes.data, length.ctypes.data, kind.ctypes.data, refb.ctypes.data, altb.ctypes.data)
-        caps = (int(props.window), int(props.max_mapq), int(props.max_read_len), mcap, ncap, kcap, int(window_bytes))
-        if realign is None:
-            engine._check(L.vlr_fragpileup_open(*head, int(bool(realign_indel_reads)), *caps, C.byref(h)))
-        else:
-            engine._check(L.vlr_fragpileup_open_realign(*head, 1, *caps, fasta.encode(), int(realign.window), MODES[realign.mode], gap, hop, ecap, int(pair_byte_limit),
-                                                        C.byref(h)))
-        try:
-            for b in bams:
-                engine._check(L.vlr_fragpileup_add_bam(h, b.encode()))
-            res = abi.FragPileupCounts()
-            engine._check(L.vlr_fragpileup_result(h, C.byref(res)))
-            if res.status & abi.FRAGPILEUP_GUARD_DAMAGED:
-                raise FragPileupError("the guard words behind a buffer of the fragment session changed")
-            rres = abi.FragPileupRealignCounts()
-            if realign is not None:
-                engine._check(L.vlr_fragpileup_realign_result(h, C.byref(rres)))
-            over = abi.FRAGPILEUP_ANY_OVERFLOW | abi.FRAGPILEUP_EVIDENCE_OVERFLOW
-            if res.status & over and retry:
-                mcap, ncap, kcap = max(mcap, int(res.needed_members)), max(ncap, int(res.needed_name_bytes)), max(kcap, int(res.needed_keys))
-                ecap = max(ecap, int(rres.needed_evidences))
-                retry = False
-                continue
-            obs = np.zeros(int(res.n_obs), abi.FRAGPILEUP_OBS_DTYPE)
-            loc = np.zeros(n, abi.FRAGPILEUP_LOCUS_DTYPE)
-            if not res.status & over:
-                engine._check(L.vlr_fragpileup_read(h, obs.ctypes.data, len(obs), loc.ctypes.data, n))
-            if not evidences:
-                return obs, loc, res
-            ev = np.zeros(int(rres.n_evidences), abi.INDELPILEUP_HIT_DTYPE)
-            if realign is not None and len(ev):
-                engine._check(L.vlr_fragpileup_read_realigned(h, ev.ctypes.data, len(ev)))
-            return obs, loc, res, ev, rres
-        finally:
-            L.vlr_fragpileup_close(h)
+        score = (fasta.encode(), int(realign.window), MODES[realign.mode], gap, hop)
+
+    def args_of(mcap, ncap, kcap, ecap):
+        args = head + (mcap, ncap, kcap, int(window_bytes))
+        return args if realign is None else args + score + (ecap, int(pair_byte_limit))
+
+    def read(h, res, rres, fits):
+        obs = np.zeros(int(res.n_obs), abi.FRAGPILEUP_OBS_DTYPE)
+        loc = np.zeros(n, abi.FRAGPILEUP_LOCUS_DTYPE)
+        if fits:
+            engine._check(L.vlr_fragpileup_read(h, obs.ctypes.data, len(obs), loc.ctypes.data, n))
+        if not evidences:
+            return obs, loc, res
+        ev = np.zeros(int(rres.n_evidences), abi.INDELPILEUP_HIT_DTYPE)
+        if realign is not None and len(ev):    # (not under `fits`, unlike the indel session's: after an overflow a session reports no evidences)
+            engine._check(L.vlr_fragpileup_read_realigned(h, ev.ctypes.data, len(ev)))
+        return obs, loc, res, ev, rres
+    return _session(L, L.vlr_fragpileup_open if realign is None else L.vlr_fragpileup_open_realign, args_of, caps, bams, retry, realign is not None, read)
+
+
+def _locus_slices(bam: str, res, lrec):
+    """What the locus records of a session say: FragPileupError for a malformed record of `bam`; then (the loci that go to the restatement,
+    flagged with too many members or alt loci; per other locus, (its index, the slice of its observations))."""
+    if res.status & abi.FRAGPILEUP_BAD_RECORD:
+        raise FragPileupError("%s: record %d is malformed" % (bam, int(res.first_bad_record)))
+    deep = abi.FRAGPILEUP_LOCUS_TOO_MANY_MEMBERS | abi.FRAGPILEUP_LOCUS_TOO_MANY_ALT_LOCI
+    flagged = [j for j in range(len(lrec)) if lrec[j]["status"] & deep]
+    return flagged, [(j, slice(int(lrec[j]["obs_offset"]), int(lrec[j]["obs_offset"]) + int(lrec[j]["n_obs"]))) for j in range(len(lrec)) if not lrec[j]["status"] & deep]
 
 
 def obs_from_array(a: np.ndarray) -> List[FragObs]:
@@ -770,17 +786,11 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
     t = basecalls.library_tables()
     short = [k for k in order if len(loci[k].ref) <= basecalls.MAX_LEN]
     arr, lrec, res = device_observations(bams, [loci[k] for k in short], props, int(device), realign_indel_reads, window_bytes=window_bytes, realign=realign, fasta=fasta)
-    if res.status & abi.FRAGPILEUP_BAD_RECORD:
-        raise FragPileupError("%s: record %d is malformed" % (bams[0], int(res.first_bad_record)))
-    deep = abi.FRAGPILEUP_LOCUS_TOO_MANY_MEMBERS | abi.FRAGPILEUP_LOCUS_TOO_MANY_ALT_LOCI
-    host = [k for k in order if len(loci[k].ref) > basecalls.MAX_LEN] + [k for j, k in enumerate(short) if lrec[j]["status"] & deep]
-    for j, k in enumerate(short):
-        if lrec[j]["status"] & deep:
-            continue
-        o0 = int(lrec[j]["obs_offset"])
-        obs = obs_from_array(arr[o0:o0 + int(lrec[j]["n_obs"])])
+    flagged, slices = _locus_slices(bams[0], res, lrec)
+    host = [k for k in order if len(loci[k].ref) > basecalls.MAX_LEN] + [short[j] for j in flagged]
+    for j, sl in slices:
         mj = int(lrec[j]["major_read_position"])
-        out[k] = table_of(obs, props, t, omit_mapq_adjustment, None if mj == abi.BASEPILEUP_NO_READ_POSITION else mj)
+        out[short[j]] = table_of(obs_from_array(arr[sl]), props, t, omit_mapq_adjustment, None if mj == abi.BASEPILEUP_NO_READ_POSITION else mj)
     if host:
         rs = restate(records(), [loci[k] for k in host], props, t, realign_indel_reads, realign=realign, ref_seqs=ref_seqs, device=int(device))
         for j, k in enumerate(host):
@@ -1226,62 +1236,35 @@ def device_indel_observations(bams, sites: Sequence[IndelSite], props: Props, ha
     per-locus maxima abi.FRAGPILEUP_INDEL_LOCUS_DTYPE, abi.FragPileupCounts, evidences abi.INDELPILEUP_HIT_DTYPE record-major,
     abi.FragPileupRealignCounts) from the kernels (vlr_fragpileup_open_indel).  `sites` sorted by (ref_id, start).  An overflow of a
     capacity is retried once with the needed ones unless retry=False."""
-    import ctypes as C
     from . import engine
     from . import realign as rl
-    from .readwindows import MODES
+    from .readwindows import MODES, locus_arrays
     L = engine.lib()
-    if isinstance(bams, str):
-        bams = [bams]
     n = len(sites)
-    kinds = {"deletion": abi.INDELPILEUP_DELETION, "insertion": abi.INDELPILEUP_INSERTION, "replacement": abi.INDELPILEUP_REPLACEMENT}
-    ref_id = np.array([s.ref_id for s in sites], np.int32)
-    start = np.array([s.start for s in sites], np.int64)
-    end = np.array([s.end for s in sites], np.int64)
-    kind = np.array([kinds[s.kind] for s in sites], np.uint8)
-    alt_off = np.zeros(n + 1, np.uint64)
-    alt_off[1:] = np.cumsum([len(s.locus.alt_allele) for s in sites])
-    altb = np.frombuffer(b"".join(bytes(s.locus.alt_allele) for s in sites) or b"\0", np.uint8).copy()
-    mcap = int(member_capacity) if member_capacity is not None else max(1 << 16, 256 * n)
-    ncap = int(name_capacity) if name_capacity is not None else max(1 << 20, 4096 * n)
-    kcap = int(key_capacity) if key_capacity is not None else max(1 << 16, 256 * n)
-    ecap = int(evidence_capacity) if evidence_capacity is not None else mcap
+    arrays = locus_arrays([s.ref_id for s in sites], [s.locus for s in sites])
+    caps = _capacities(n, member_capacity, name_capacity, key_capacity)
+    caps += (int(evidence_capacity) if evidence_capacity is not None else caps[0],)
     gap = (spec.gap or rl.GapParams()).as_array()
     hop = (spec.hop or rl.HopParams()).as_array() if spec.mode == "homopolymer" else None
-    while True:
-        h = C.c_void_p()
-        engine._check(L.vlr_fragpileup_open_indel(int(device), n, ref_id.ctypes.data, start.ctypes.data, end.ctypes.data, kind.ctypes.data, alt_off.ctypes.data,
-                                                  altb.ctypes.data, int(props.window), int(props.max_mapq), int(props.max_read_len), mcap, ncap, kcap, int(window_bytes),
-                                                  fasta.encode(), int(spec.window), MODES[spec.mode], gap, hop, ecap, int(pair_byte_limit), int(bool(has_insert_size)),
-                                                  C.byref(h)))
-        try:
-            for b in bams:
-                engine._check(L.vlr_fragpileup_add_bam(h, b.encode()))
-            res = abi.FragPileupCounts()
-            engine._check(L.vlr_fragpileup_result(h, C.byref(res)))
-            if res.status & abi.FRAGPILEUP_GUARD_DAMAGED:
-                raise FragPileupError("the guard words behind a buffer of the fragment session changed")
-            rres = abi.FragPileupRealignCounts()
-            engine._check(L.vlr_fragpileup_realign_result(h, C.byref(rres)))
-            over = abi.FRAGPILEUP_ANY_OVERFLOW | abi.FRAGPILEUP_EVIDENCE_OVERFLOW
-            if res.status & over and retry:
-                mcap, ncap, kcap = max(mcap, int(res.needed_members)), max(ncap, int(res.needed_name_bytes)), max(kcap, int(res.needed_keys))
-                ecap = max(ecap, int(rres.needed_evidences))
-                retry = False
-                continue
-            obs = np.zeros(int(res.n_obs), abi.FRAGPILEUP_OBS_DTYPE)
-            obx = np.zeros(int(res.n_obs), abi.FRAGPILEUP_INDEL_OBS_DTYPE)
-            loc = np.zeros(n, abi.FRAGPILEUP_LOCUS_DTYPE)
-            lox = np.zeros(n, abi.FRAGPILEUP_INDEL_LOCUS_DTYPE)
-            ev = np.zeros(int(rres.n_evidences), abi.INDELPILEUP_HIT_DTYPE)
-            if not res.status & over:
-                engine._check(L.vlr_fragpileup_read(h, obs.ctypes.data, len(obs), loc.ctypes.data, n))
-                engine._check(L.vlr_fragpileup_read_indel(h, obx.ctypes.data, len(obx), lox.ctypes.data, n))
-                if len(ev):
-                    engine._check(L.vlr_fragpileup_read_realigned(h, ev.ctypes.data, len(ev)))
-            return obs, obx, loc, lox, res, ev, rres
-        finally:
-            L.vlr_fragpileup_close(h)
+    head = (int(device), n) + tuple(a.ctypes.data for a in arrays) + (int(props.window), int(props.max_mapq), int(props.max_read_len))
+    score = (fasta.encode(), int(spec.window), MODES[spec.mode], gap, hop)
+
+    def args_of(mcap, ncap, kcap, ecap):
+        return head + (mcap, ncap, kcap, int(window_bytes)) + score + (ecap, int(pair_byte_limit), int(bool(has_insert_size)))
+
+    def read(h, res, rres, fits):
+        obs = np.zeros(int(res.n_obs), abi.FRAGPILEUP_OBS_DTYPE)
+        obx = np.zeros(int(res.n_obs), abi.FRAGPILEUP_INDEL_OBS_DTYPE)
+        loc = np.zeros(n, abi.FRAGPILEUP_LOCUS_DTYPE)
+        lox = np.zeros(n, abi.FRAGPILEUP_INDEL_LOCUS_DTYPE)
+        ev = np.zeros(int(rres.n_evidences), abi.INDELPILEUP_HIT_DTYPE)
+        if fits:
+            engine._check(L.vlr_fragpileup_read(h, obs.ctypes.data, len(obs), loc.ctypes.data, n))
+            engine._check(L.vlr_fragpileup_read_indel(h, obx.ctypes.data, len(obx), lox.ctypes.data, n))
+            if len(ev):
+                engine._check(L.vlr_fragpileup_read_realigned(h, ev.ctypes.data, len(ev)))
+        return obs, obx, loc, lox, res, ev, rres
+    return _session(L, L.vlr_fragpileup_open_indel, args_of, caps, bams, retry, True, read)
 
 
 def indel_obs_from_arrays(a: np.ndarray, x: np.ndarray) -> List[IndelObs]:
@@ -1341,19 +1324,13 @@ def indel_tables(bams, fasta: str, sites: Sequence[IndelSite], what: Sequence[st
     if device != "cpu":
         obs, obx, loc, lox, res, _, _ = device_indel_observations(bams, sorted_sites, props, has_isize, spec, fasta, int(device), window_bytes=window_bytes)
         blist = [bams] if isinstance(bams, str) else list(bams)
-        if res.status & abi.FRAGPILEUP_BAD_RECORD:
-            raise FragPileupError("%s: record %d is malformed" % (blist[0], int(res.first_bad_record)))
+        host, slices = _locus_slices(blist[0], res, loc)
         if res.status & (abi.FRAGPILEUP_ANY_OVERFLOW | abi.FRAGPILEUP_EVIDENCE_OVERFLOW):
             raise FragPileupError("%s: the members or evidences do not fit the buffers of the fragment session" % blist[0])
-        deep = abi.FRAGPILEUP_LOCUS_TOO_MANY_MEMBERS | abi.FRAGPILEUP_LOCUS_TOO_MANY_ALT_LOCI
-        host = []
         for j, k in enumerate(order):
             maxima[k] = (int(lox[j]["max_del"]), int(lox[j]["max_ins"]), (int(lox[j]["max_clip"]), int(lox[j]["max_clip_l_seq"])))
-            if loc[j]["status"] & deep:
-                host.append(j)
-                continue
-            o0 = int(loc[j]["obs_offset"])
-            per[k] = indel_obs_from_arrays(obs[o0:o0 + int(loc[j]["n_obs"])], obx[o0:o0 + int(loc[j]["n_obs"])])
+        for j, sl in slices:
+            per[order[j]] = indel_obs_from_arrays(obs[sl], obx[sl])
     if host:   # the restatement: everything on the CPU path, the flagged loci of the device path (scored on the device)
         blist = [bams] if isinstance(bams, str) else list(bams)
         recs = records() if records is not None else [r for b in blist for r in read_bam(b)[1]]      # (`records`: the caller's, read once)

@@ -379,6 +379,18 @@ class PairArrays:
         return self.x_offset, self.x_bases, self.y_offset, self.y_bases, self.y_quals, self.band
 
 
+def locus_arrays(ref_id, loci: List[IndelLocus]):
+    """(ref_id, start, end, kind, alt_off, alt bases) of `loci` on the contigs `ref_id` as the open calls of the indel sessions take them:
+    the alt allele window of locus k lies at alt bases[alt_off[k] .. alt_off[k + 1])"""
+    import numpy as np
+    from . import abi
+    kinds = {"deletion": abi.INDELPILEUP_DELETION, "insertion": abi.INDELPILEUP_INSERTION, "replacement": abi.INDELPILEUP_REPLACEMENT}
+    alt_off = np.zeros(len(loci) + 1, np.uint64)
+    alt_off[1:] = np.cumsum([len(l.alt_allele) for l in loci])
+    return (np.array(list(ref_id), np.int32), np.array([l.start for l in loci], np.int64), np.array([l.end for l in loci], np.int64),
+            np.array([kinds[l.kind] for l in loci], np.uint8), alt_off, np.frombuffer(b"".join(bytes(l.alt_allele) for l in loci) or b"\0", np.uint8).copy())
+
+
 def device_hits(bams, fasta: str, ref_id, loci: List[IndelLocus], mode: str = "exact", gap=None, hop=None, window: int = 64, device: int = 0,
                 hit_capacity: Optional[int] = None, window_bytes: int = 0, keep_pairs: bool = False, retry: bool = True):
     """(hits as a numpy array of abi.INDELPILEUP_HIT_DTYPE, locus-major; abi.IndelPileupCounts; PairArrays or None) from the kernels.
@@ -392,14 +404,7 @@ def device_hits(bams, fasta: str, ref_id, loci: List[IndelLocus], mode: str = "e
     if mode not in MODES:
         raise ValueError("mode must be one of %s" % ", ".join(MODES))
     n = len(loci)
-    kinds = {"deletion": abi.INDELPILEUP_DELETION, "insertion": abi.INDELPILEUP_INSERTION, "replacement": abi.INDELPILEUP_REPLACEMENT}
-    rid = np.array(list(ref_id), np.int32)
-    start = np.array([l.start for l in loci], np.int64)
-    end = np.array([l.end for l in loci], np.int64)
-    kind = np.array([kinds[l.kind] for l in loci], np.uint8)
-    alt_off = np.zeros(n + 1, np.uint64)
-    alt_off[1:] = np.cumsum([len(l.alt_allele) for l in loci])
-    altb = np.frombuffer(b"".join(bytes(l.alt_allele) for l in loci) or b"\0", np.uint8).copy()
+    rid, start, end, kind, alt_off, altb = locus_arrays(ref_id, loci)
     g = (gap or realign.GapParams()).as_array()
     if mode == "homopolymer":
         h_ = (hop or realign.HopParams()).as_array()
