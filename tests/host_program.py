@@ -1,7 +1,7 @@
 """The stand-alone host programs of csrc/ (vlr_*_host.cpp: a kernel's header compiled for the CPU, with a main of its own) built under
-the sanitizers, for test_basepileup_host.py, test_indelpileup_host.py, test_fragpileup_host.py, test_fragrealign_host_program.py and
-test_fragment_indel_host.py.  A plain helper module: the `program`
-fixtures stay in those files."""
+the sanitizers, for test_basepileup_host.py, test_indelpileup_host.py, test_fragpileup_host.py, test_fragrealign_host_program.py,
+test_fragment_indel_host.py and test_ingest_host_program.py (whose program links the host units of the front door).  A plain helper
+module: the `program` fixtures stay in those files."""
 import os
 import shutil
 import subprocess
@@ -13,8 +13,9 @@ CSRC = os.path.join(ROOT, "varlociraptor_amd", "csrc")
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 
-def build(tmp_path_factory, source_name):
-    """path of the program built from csrc/<source_name>.cpp with -fsanitize=address,undefined; skips without a compiler that can"""
+def build(tmp_path_factory, source_name, extra_sources=(), libs=()):
+    """path of the program built from csrc/<source_name>.cpp (and the csrc/ files `extra_sources`, linked with `libs`) with
+    -fsanitize=address,undefined; skips without a compiler that can"""
     cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
     if cxx is None:
         pytest.skip("no system C++ compiler")
@@ -36,5 +37,6 @@ def build(tmp_path_factory, source_name):
     else:
         pytest.skip("the system compiler has no usable -fsanitize=address,undefined: " + r.stderr[-200:])
     exe = os.path.join(out, source_name)
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-ffp-contract=off"] + flags + [os.path.join(CSRC, source_name + ".cpp"), "-o", exe])
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-ffp-contract=off"] + flags +
+                          [os.path.join(CSRC, f) for f in (source_name + ".cpp",) + tuple(extra_sources)] + ["-o", exe] + list(libs))
     return exe

@@ -4,7 +4,7 @@ The expected number of coding variants per megabase as a function of the (minimu
 annotated calls file gives one entry per sample and ALT allele, (FORMAT/AF, probability of the chosen events, signature), and each
 output value is the ln_sum_exp of the probabilities of one signature within one VAF range, scaled to the coding genome size.  The
 reduction over (range, group) cells has a HIP kernel behind the C ABI (`vlr_range_group_lse`, csrc/vlr_callstats.hip) and the
-record pass runs in the engine (`vlr_calls_mutational_burden`, csrc/vlr_ingest.cpp); next to them is the host restatement
+record pass runs in the engine (`vlr_calls_mutational_burden`, csrc/vlr_callsfile.cpp); next to them is the host restatement
 (`device="cpu"`: the htslib-free reader of bcfio.py and numpy) that the CPU suite and the comparisons use.
 
 Row order is this project's: the reference iterates a HashMap, so its order is unspecified.  Rows come by range index, then by

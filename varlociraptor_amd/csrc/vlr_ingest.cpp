@@ -13,442 +13,19 @@
 // No htslib: BGZF members are located through their BSIZE fields and inflated in parallel with zlib, BCF records are decoded in
 // place, every stage runs on a pool of std::threads over contiguous record ranges.  Pure host code; the only device-related call
 // is vlr_host_alloc (page-locked result arrays so that vlr_batch_run_host copies them by direct DMA).
-#include <dlfcn.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-#include <sched.h>
-#include <zlib.h>
-
-#include <algorithm>
-#include <atomic>
-#include <cmath>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <condition_variable>
-#include <deque>
 #include <functional>
-#include <limits>
 #include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <unordered_map>
 #include <unordered_set>
-#include <vector>
 
-#include "../../include/vlr.h"
-#include "vlr_gpuio.h"
-#include "vlr_callstats.h"
+#include "vlr_hostio.h"
 
-extern "C" void vlr_set_error(const char* msg);  // vlr_host.cpp: the text behind vlr_last_error()
+// (The structs behind the C ABI and the device reader's StageRing / DevFileStream keep the default visibility they had, so that the
+// dynamic symbols of libvlr.so stay what they were; GCC remarks that fields of theirs have hidden types, which is intended.)
+#if defined(__GNUC__) && !defined(__clang__)
+#pragma GCC diagnostic ignored "-Wattributes"
+#endif
 
-#include <chrono>
 namespace {
-
-// stage timings of the last vlr_obs_read / vlr_calls_write of this process (vlr_ingest_last_timings): measurement aid
-double g_ingest_t[16] = {0};
-double g_ingest_total[16] = {0};  // the same stages summed over every call since the last reset (streaming reader / writer)
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-int ifail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    vlr_set_error(buf);
-    return code;
-}
-
-// ------------------------------------------------------------------------------------------------ threads
-// CPUs this process may actually use: the affinity mask and the cgroup CPU quota (containers report the host's hardware threads)
-int effective_cpus() {
-    unsigned h = std::thread::hardware_concurrency();
-    int n = (int)(h ? h : 1u);
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::min(n, std::max(1, CPU_COUNT(&set)));
-    if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {  // cgroup v2: "<quota> <period>" or "max <period>"
-        char q[64];
-        long period = 0;
-        if (fscanf(f, "%63s %ld", q, &period) == 2 && strcmp(q, "max") != 0 && period > 0) n = std::min(n, (int)std::max(1L, (atol(q) + period - 1) / period));
-        fclose(f);
-    } else {
-        long quota = -1, period = 0;
-        if (FILE* g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) { if (fscanf(g, "%ld", &quota) != 1) quota = -1; fclose(g); }
-        if (FILE* g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(g, "%ld", &period) != 1) period = 0; fclose(g); }
-        if (quota > 0 && period > 0) n = std::min(n, (int)std::max(1L, (quota + period - 1) / period));
-    }
-    return std::max(1, n);
-}
-int pick_threads(int n) {
-    if (n > 0) return n;
-    if (const char* ev = getenv("VLR_INGEST_THREADS")) { const int v = atoi(ev); if (v > 0) return v; }
-    static const int eff = effective_cpus();
-    return std::max(1, std::min(eff, 256));
-}
-// fn(begin, end, worker) over [0, n) in contiguous ranges
-template <typename F>
-void parallel_ranges(int64_t n, int n_threads, F&& fn) {
-    if (n <= 0) return;
-    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, n));
-    if (T == 1) { fn((int64_t)0, n, 0); return; }
-    std::vector<std::thread> th;
-    th.reserve(T);
-    for (int t = 0; t < T; ++t) {
-        const int64_t b = n * t / T, e = n * (t + 1) / T;
-        th.emplace_back([&fn, b, e, t] { fn(b, e, t); });
-    }
-    for (auto& x : th) x.join();
-}
-// dynamic work items (blocks of very different cost)
-template <typename F>
-void parallel_items(int64_t n, int n_threads, F&& fn) {
-    if (n <= 0) return;
-    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, n));
-    std::atomic<int64_t> next{0};
-    auto body = [&](int t) {
-        for (;;) {
-            const int64_t i = next.fetch_add(1);
-            if (i >= n) break;
-            fn(i, t);
-        }
-    };
-    if (T == 1) { body(0); return; }
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t) th.emplace_back(body, t);
-    for (auto& x : th) x.join();
-}
-
-// ------------------------------------------------------------------------------------------------ files, BGZF
-// an uninitialised byte buffer (std::vector would zero gigabytes on one thread before the workers overwrite them)
-struct Blob {
-    uint8_t* p = nullptr;
-    size_t n = 0;
-    Blob() = default;
-    Blob(const Blob&) = delete;
-    Blob& operator=(const Blob&) = delete;
-    bool mapped = false;
-    // (unmapping a file of gigabytes walks all its touched pages — 65 ms for the 2 GB of a million-record run: off the caller's thread)
-    void release() {
-        if (p) {
-            if (mapped && n >= ((size_t)64 << 20)) { uint8_t* q = p; const size_t m = n; std::thread([q, m] { munmap(q, m); }).detach(); }
-            else if (mapped) munmap(p, n ? n : 1);
-            else free(p);
-        }
-        p = nullptr; n = 0; mapped = false;
-    }
-    ~Blob() { release(); }
-    bool alloc(size_t bytes) {
-        release();
-        if (bytes >= ((size_t)8 << 20)) {  // gigabytes touched for the first time by all workers at once: 2 MB pages, 512 x fewer faults
-            void* q = nullptr;
-            if (posix_memalign(&q, (size_t)2 << 20, (bytes + (((size_t)2 << 20) - 1)) & ~(((size_t)2 << 20) - 1)) == 0) {
-                (void)madvise(q, bytes, MADV_HUGEPAGE);
-                p = (uint8_t*)q; n = bytes;
-                return true;
-            }
-        }
-        p = (uint8_t*)malloc(bytes ? bytes : 1); n = p ? bytes : 0; return p != nullptr;
-    }
-    // the file's pages straight from the page cache (no copy; the inflate workers fault them in side by side)
-    bool map_file(const char* path) {
-        release();
-        const int fd = open(path, O_RDONLY);
-        if (fd < 0) return false;
-        struct stat st;
-        if (fstat(fd, &st) != 0 || st.st_size <= 0) { close(fd); return false; }
-        void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-        close(fd);
-        if (m == MAP_FAILED) return false;
-        (void)madvise(m, (size_t)st.st_size, MADV_WILLNEED);
-        p = (uint8_t*)m; n = (size_t)st.st_size; mapped = true;
-        return true;
-    }
-    const uint8_t* data() const { return p; }
-    size_t size() const { return n; }
-    uint8_t operator[](size_t i) const { return p[i]; }
-};
-
-bool read_whole_file(const char* path, Blob& out, std::string& err) {
-    if (out.map_file(path)) return true;
-    FILE* f = fopen(path, "rb");
-    if (!f) { err = std::string("cannot open ") + path; return false; }
-    fseek(f, 0, SEEK_END);
-    const long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    if (!out.alloc((size_t)std::max(0L, n))) { fclose(f); err = "out of memory"; return false; }
-    const size_t got = n > 0 ? fread(out.p, 1, (size_t)n, f) : 0;
-    fclose(f);
-    if (got != (size_t)std::max(0L, n)) { err = std::string("short read on ") + path; return false; }
-    return true;
-}
-
-struct BgzfBlock { size_t off, clen; uint32_t isize; size_t out_off; uint32_t crc; };   // crc: CRC32 of the inflated bytes (member trailer)
-
-// all gzip members carry the BGZF extra field `BC` with their total size: index them without inflating
-bool bgzf_index(const Blob& raw, std::vector<BgzfBlock>& blocks) {
-    size_t p = 0;
-    size_t total = 0;
-    while (p < raw.size()) {
-        if (p + 18 > raw.size() || raw[p] != 0x1f || raw[p + 1] != 0x8b || raw[p + 2] != 8 || !(raw[p + 3] & 4)) return false;
-        const unsigned xlen = raw[p + 10] | (raw[p + 11] << 8);
-        size_t q = p + 12;
-        const size_t xend = q + xlen;
-        if (xend > raw.size()) return false;
-        long bsize = -1;
-        while (q + 4 <= xend) {
-            const unsigned slen = raw[q + 2] | (raw[q + 3] << 8);
-            if (raw[q] == 'B' && raw[q + 1] == 'C' && slen == 2 && q + 6 <= xend) bsize = (raw[q + 4] | (raw[q + 5] << 8)) + 1;
-            q += 4 + slen;
-        }
-        if (bsize < 0 || p + (size_t)bsize > raw.size() || (size_t)bsize < xlen + 20) return false;
-        const size_t cdata = xend, cend = p + (size_t)bsize - 8;
-        const uint32_t isize = raw[cend + 4] | (raw[cend + 5] << 8) | (raw[cend + 6] << 16) | ((uint32_t)raw[cend + 7] << 24);
-        const uint32_t crc = raw[cend] | (raw[cend + 1] << 8) | (raw[cend + 2] << 16) | ((uint32_t)raw[cend + 3] << 24);
-        blocks.push_back({cdata, cend - cdata, isize, total, crc});
-        total += isize;
-        p += (size_t)bsize;
-    }
-    return true;
-}
-
-// libdeflate (a system library next to zlib, about twice zlib's inflate rate) is taken through dlopen when it is installed — the
-// image carries the runtime library without its header; its C API (v1.x) is declared here.  zlib is the fallback.
-struct LibDeflate {
-    void* (*alloc_d)() = nullptr;
-    int (*decompress)(void*, const void*, size_t, void*, size_t, size_t*) = nullptr;
-    void (*free_d)(void*) = nullptr;
-    void* (*alloc_c)(int) = nullptr;
-    size_t (*compress)(void*, const void*, size_t, void*, size_t) = nullptr;
-    size_t (*bound)(void*, size_t) = nullptr;
-    void (*free_c)(void*) = nullptr;
-    uint32_t (*crc32)(uint32_t, const void*, size_t) = nullptr;
-    bool ok = false;
-    LibDeflate() {
-        if (getenv("VLR_NO_LIBDEFLATE")) return;
-        void* h = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
-        if (!h) return;
-        alloc_d = (void* (*)())dlsym(h, "libdeflate_alloc_decompressor");
-        decompress = (int (*)(void*, const void*, size_t, void*, size_t, size_t*))dlsym(h, "libdeflate_deflate_decompress");
-        free_d = (void (*)(void*))dlsym(h, "libdeflate_free_decompressor");
-        alloc_c = (void* (*)(int))dlsym(h, "libdeflate_alloc_compressor");
-        compress = (size_t (*)(void*, const void*, size_t, void*, size_t))dlsym(h, "libdeflate_deflate_compress");
-        bound = (size_t (*)(void*, size_t))dlsym(h, "libdeflate_deflate_compress_bound");
-        free_c = (void (*)(void*))dlsym(h, "libdeflate_free_compressor");
-        crc32 = (uint32_t (*)(uint32_t, const void*, size_t))dlsym(h, "libdeflate_crc32");
-        ok = alloc_d && decompress && free_d && alloc_c && compress && bound && free_c && crc32;
-    }
-};
-const LibDeflate& libdeflate() { static LibDeflate L; return L; }
-
-// CRC32 of an inflated member against the value in its trailer (RFC 1952; htslib's bgzf.c checks it for every block it reads)
-bool member_crc_ok(const uint8_t* data, size_t n, uint32_t want) {
-    const LibDeflate& ld = libdeflate();
-    const uint32_t got = ld.ok ? ld.crc32(0, data, n) : (uint32_t)crc32(crc32(0L, Z_NULL, 0), data, (uInt)n);
-    return got == want;
-}
-// one BGZF member: raw DEFLATE -> dlen bytes whose CRC32 is `crc`
-bool inflate_raw(const uint8_t* src, size_t clen, uint8_t* dst, size_t dlen, uint32_t crc) {
-    const LibDeflate& ld = libdeflate();
-    if (ld.ok) {
-        thread_local void* d = ld.alloc_d();
-        size_t got = 0;
-        if (d && ld.decompress(d, src, clen, dst, dlen, &got) == 0 && got == dlen) return member_crc_ok(dst, dlen, crc);
-        // fall through to zlib on any doubt
-    }
-    z_stream zs;
-    memset(&zs, 0, sizeof zs);
-    if (inflateInit2(&zs, -15) != Z_OK) return false;
-    zs.next_in = const_cast<Bytef*>(src); zs.avail_in = (uInt)clen;
-    zs.next_out = dst; zs.avail_out = (uInt)dlen;
-    const int rc = inflate(&zs, Z_FINISH);
-    const bool ok = (rc == Z_STREAM_END) && zs.total_out == dlen;
-    inflateEnd(&zs);
-    return ok && member_crc_ok(dst, dlen, crc);
-}
-
-// file contents, decompressed: BGZF (parallel), plain gzip (sequential), or as is
-bool load_inflated(const char* path, Blob& out_blob, int n_threads, std::string& err) {
-    Blob raw;
-    const double t0 = now_s();
-    if (!read_whole_file(path, raw, err)) return false;
-    g_ingest_t[0] += now_s() - t0;
-    std::vector<uint8_t> out;
-    auto finish = [&](std::vector<uint8_t>& v) { if (!out_blob.alloc(v.size())) { err = "out of memory"; return false; } memcpy(out_blob.p, v.data(), v.size()); return true; };
-    if (raw.size() < 2 || raw[0] != 0x1f || raw[1] != 0x8b) { std::swap(out_blob.p, raw.p); std::swap(out_blob.n, raw.n); std::swap(out_blob.mapped, raw.mapped); return true; }
-    std::vector<BgzfBlock> blocks;
-    if (bgzf_index(raw, blocks)) {
-        size_t total = 0;
-        for (auto& b : blocks) total += b.isize;
-        if (!out_blob.alloc(total)) { err = "out of memory"; return false; }
-        std::atomic<bool> bad{false};
-        const double t1 = now_s();
-        parallel_items((int64_t)blocks.size(), n_threads, [&](int64_t i, int) {
-            const BgzfBlock& b = blocks[(size_t)i];
-            if (b.isize == 0) return;
-            if (!inflate_raw(raw.data() + b.off, b.clen, out_blob.p + b.out_off, b.isize, b.crc)) bad = true;
-        });
-        g_ingest_t[1] += now_s() - t1;
-        if (bad) { err = std::string("corrupt BGZF block in ") + path; return false; }
-        return true;
-    }
-    // generic (multi-member) gzip
-    z_stream zs;
-    memset(&zs, 0, sizeof zs);
-    if (inflateInit2(&zs, 15 + 32) != Z_OK) { err = "zlib init failed"; return false; }
-    zs.next_in = raw.p; zs.avail_in = 0;
-    const uint8_t* const raw_end = raw.p + raw.size();
-    out.resize(std::max<size_t>(raw.size() * 4, 1 << 16));
-    size_t have = 0;
-    for (;;) {
-        if (have == out.size()) out.resize(out.size() * 2);
-        // zlib counts in 32 bits: hand the input over in pieces (a plain-gzip file above 2 GiB used to end at the first piece)
-        if (zs.avail_in == 0 && zs.next_in < raw_end) zs.avail_in = (uInt)std::min<size_t>((size_t)(raw_end - zs.next_in), 0x40000000);
-        zs.next_out = out.data() + have; zs.avail_out = (uInt)std::min<size_t>(out.size() - have, 0x7fffffff);
-        const int rc = inflate(&zs, Z_NO_FLUSH);
-        have = (size_t)(zs.next_out - out.data());
-        if (rc == Z_STREAM_END) {
-            if (zs.avail_in == 0 && zs.next_in >= raw_end) break;
-            if (inflateReset(&zs) != Z_OK) { inflateEnd(&zs); err = "zlib reset failed"; return false; }
-            continue;
-        }
-        if (rc != Z_OK) { inflateEnd(&zs); err = std::string("corrupt gzip stream in ") + path; return false; }
-    }
-    inflateEnd(&zs);
-    out.resize(have);
-    return finish(out);
-}
-
-// one BGZF member holding `n` bytes (n <= 0xff00)
-void bgzf_deflate_block(const uint8_t* data, size_t n, int level, std::vector<uint8_t>& out) {
-    uLong bound = compressBound((uLong)n) + 64;
-    const size_t at = out.size();
-    size_t clen = 0;
-    const LibDeflate& ld = libdeflate();
-    if (ld.ok) {
-        thread_local int c_level = -1;
-        thread_local void* c = nullptr;
-        if (c_level != level) { if (c) ld.free_c(c); c = ld.alloc_c(level); c_level = level; }
-        if (c) {
-            bound = (uLong)ld.bound(c, n) + 64;
-            out.resize(at + 18 + bound + 8);
-            clen = ld.compress(c, data, n, out.data() + at + 18, bound);
-        }
-    }
-    if (clen == 0 || clen + 26 > 0xffff) {
-        bound = compressBound((uLong)n) + 64;
-        out.resize(at + 18 + bound + 8);
-        z_stream zs;
-        memset(&zs, 0, sizeof zs);
-        deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY);
-        zs.next_in = const_cast<Bytef*>(data); zs.avail_in = (uInt)n;
-        zs.next_out = out.data() + at + 18; zs.avail_out = (uInt)bound;
-        deflate(&zs, Z_FINISH);
-        clen = zs.total_out;
-        deflateEnd(&zs);
-    }
-    static const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-    memcpy(out.data() + at, head, 16);
-    const unsigned bsize = (unsigned)(clen + 25);
-    out[at + 16] = (uint8_t)(bsize & 0xff); out[at + 17] = (uint8_t)(bsize >> 8);
-    const uint32_t crc = ld.ok ? ld.crc32(0, data, n) : (uint32_t)crc32(crc32(0L, Z_NULL, 0), data, (uInt)n), isz = (uint32_t)n;
-    uint8_t* t = out.data() + at + 18 + clen;
-    for (int i = 0; i < 4; ++i) { t[i] = (uint8_t)(crc >> (8 * i)); t[4 + i] = (uint8_t)(isz >> (8 * i)); }
-    out.resize(at + 18 + clen + 8);
-}
-const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-// compress `data` into BGZF members of 0xff00 bytes in parallel and write the file
-// File output behind the streaming calls writer: the compressed members of a chunk are handed to one I/O thread, so that copying
-// them into the page cache (tens of milliseconds per hundred megabytes, serial) runs beside the encoding of the next chunk.
-struct AsyncSink {
-    FILE* f = nullptr;
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::vector<std::vector<uint8_t>>> q;
-    bool closing = false, failed = false;
-    explicit AsyncSink(FILE* file) : f(file) {
-        th = std::thread([this] {
-            for (;;) {
-                std::vector<std::vector<uint8_t>> job;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [this] { return closing || !q.empty(); });
-                    if (q.empty()) return;
-                    job = std::move(q.front());
-                    q.pop_front();
-                }
-                bool ok = true;
-                for (auto& c : job) ok = ok && fwrite(c.data(), 1, c.size(), f) == c.size();
-                if (!ok) { std::lock_guard<std::mutex> g(mu); failed = true; }
-                cv.notify_all();
-            }
-        });
-    }
-    void push(std::vector<std::vector<uint8_t>>&& job) {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [this] { return q.size() < 3; });   // (bounded: at most three chunks of compressed members in memory)
-        q.push_back(std::move(job));
-        cv.notify_all();
-    }
-    bool finish() {   // everything handed over is in the file (or failed)
-        { std::lock_guard<std::mutex> g(mu); closing = true; }
-        cv.notify_all();
-        if (th.joinable()) th.join();
-        return !failed;
-    }
-    ~AsyncSink() { (void)finish(); }
-};
-bool write_bgzf_stream(FILE* f, const std::vector<const std::vector<uint8_t>*>& parts, int n_threads, int level, bool with_eof, std::string& err, AsyncSink* sink = nullptr);
-bool write_bgzf_file(const char* path, const std::vector<const std::vector<uint8_t>*>& parts, int n_threads, int level, std::string& err) {
-    FILE* f = fopen(path, "wb");
-    if (!f) { err = std::string("cannot create ") + path; return false; }
-    bool ok = write_bgzf_stream(f, parts, n_threads, level, true, err);
-    ok = (fclose(f) == 0) && ok;
-    if (!ok && err.empty()) err = std::string("write failed on ") + path;
-    return ok;
-}
-// the parts, logically concatenated, as BGZF members appended to an open file (a short last member is legal BGZF)
-bool write_bgzf_stream(FILE* f, const std::vector<const std::vector<uint8_t>*>& parts, int n_threads, int level, bool with_eof, std::string& err, AsyncSink* sink) {
-    // the parts are logically concatenated; cut into blocks without copying more than one block at a time
-    size_t total = 0;
-    std::vector<size_t> start;
-    for (auto* p : parts) { start.push_back(total); total += p->size(); }
-    const size_t B = 0xff00;
-    const int64_t nb = (int64_t)((total + B - 1) / B);
-    std::vector<std::vector<uint8_t>> comp((size_t)nb);
-    parallel_items(nb, n_threads, [&](int64_t bi, int) {
-        const size_t b0 = (size_t)bi * B, b1 = std::min(total, b0 + B);
-        std::vector<uint8_t> tmp;
-        tmp.reserve(b1 - b0);
-        size_t k = (size_t)(std::upper_bound(start.begin(), start.end(), b0) - start.begin()) - 1;
-        size_t pos = b0;
-        while (pos < b1) {
-            const std::vector<uint8_t>& P = *parts[k];
-            const size_t o = pos - start[k], n = std::min(P.size() - o, b1 - pos);
-            tmp.insert(tmp.end(), P.begin() + (long)o, P.begin() + (long)(o + n));
-            pos += n;
-            ++k;
-        }
-        bgzf_deflate_block(tmp.data(), tmp.size(), level, comp[(size_t)bi]);
-    });
-    if (sink) {   // (the streaming writer: the end-of-file member is written by its close, after the sink has drained)
-        sink->push(std::move(comp));
-        return true;
-    }
-    bool ok = true;
-    for (auto& c : comp) ok = ok && fwrite(c.data(), 1, c.size(), f) == c.size();
-    if (with_eof) ok = ok && fwrite(kBgzfEof, 1, 28, f) == 28;
-    if (!ok) err = "write failed";
-    return ok;
-}
 
 // ------------------------------------------------------------------------------------------------ f16
 float half_to_float(uint16_t h) {
@@ -492,13 +69,15 @@ uint16_t float_to_half(float f) {  // round to nearest even (half::f16::from_f64
     return (uint16_t)out;
 }
 
+}  // namespace
+
+namespace vlr_hostio VLR_HIDDEN {
+
+// stage timings of the last vlr_obs_read / vlr_calls_write of this process (vlr_ingest_last_timings): measurement aid
+double g_ingest_t[16] = {0};
+double g_ingest_total[16] = {0};  // the same stages summed over every call since the last reset (streaming reader / writer)
+
 // ------------------------------------------------------------------------------------------------ header
-struct Header {
-    std::string text;
-    std::vector<std::string> dict;     // FILTER/INFO/FORMAT ids by dictionary index
-    std::vector<std::string> contigs;  // by index
-    bool version_ok = false;
-};
 std::string attr(const std::string& body, const char* key) {
     const std::string k = std::string(key) + "=";
     size_t p = 0;
@@ -527,6 +106,7 @@ void parse_header(const std::string& text, Header& h) {
         if (line == "##varlociraptor_observation_format_version=15") h.version_ok = true;  // preprocessing/mod.rs:810, calling.rs:324-339
         const bool dictline = line.compare(0, 9, "##FILTER=") == 0 || line.compare(0, 7, "##INFO=") == 0 || line.compare(0, 9, "##FORMAT=") == 0;
         if (dictline) {
+            if (line.find('<') == std::string::npos) continue;   // (a line cut short: substr would throw through the C ABI)
             const std::string body = line.substr(line.find('<'));
             const std::string id = attr(body, "ID"), idx = attr(body, "IDX");
             if (id.empty() || seen.count(id)) continue;
@@ -535,7 +115,7 @@ void parse_header(const std::string& text, Header& h) {
             if ((int)h.dict.size() <= i) h.dict.resize((size_t)i + 1);
             h.dict[(size_t)i] = id;
             next = std::max(next, i + 1);
-        } else if (line.compare(0, 9, "##contig=") == 0) {
+        } else if (line.compare(0, 9, "##contig=") == 0 && line.find('<') != std::string::npos) {
             const std::string body = line.substr(line.find('<'));
             const std::string id = attr(body, "ID"), idx = attr(body, "IDX");
             const int i = idx.empty() ? cnext : atoi(idx.c_str());
@@ -546,6 +126,25 @@ void parse_header(const std::string& text, Header& h) {
     }
 }
 
+BcfHead bcf_head(const uint8_t* d, size_t n, size_t& need, Header& h) {
+    if (n < 9) return BCF_SHORT;
+    if (memcmp(d, "BCF\2\2", 5) != 0) return BCF_NOT;
+    uint32_t l_text;
+    memcpy(&l_text, d + 5, 4);
+    need = 9 + (size_t)l_text;
+    if (need > n) return BCF_PARTIAL;
+    std::string text((const char*)d + 9, l_text);
+    while (!text.empty() && text.back() == '\0') text.pop_back();
+    parse_header(text, h);
+    return BCF_OK;
+}
+
+}  // namespace vlr_hostio
+
+using namespace vlr_hostio;
+
+namespace {
+
 // ------------------------------------------------------------------------------------------------ observation records
 // (enum VlrObsField: vlr_gpuio.h — the device decoder indexes the same table)
 const char* const kFieldName[FD_N] = {
@@ -553,6 +152,14 @@ const char* const kFieldName[FD_N] = {
     "STRAND", "READ_ORIENTATION", "READ_POSITION", "ALT_LOCUS", "SOFTCLIPPED", "PAIRED", "IS_MAX_MAPQ",
     "PROB_HOMOPOLYMER_ARTIFACT_OBSERVABLE", "PROB_HOMOPOLYMER_VARIANT_OBSERVABLE", "HOMOPOLYMER_INDEL_LEN", "THIRD_ALLELE_EVIDENCE",
     "IMPRECISE", "EVENT", "MATEID", "HETEROZYGOSITY", "SOMATIC_EFFECTIVE_MUTATION_RATE"};
+// dictionary index of a header -> VlrObsField (-1: not a field of the observation format)
+std::vector<int8_t> obs_field_of_key(const Header& h) {
+    std::vector<int8_t> field_of_key(h.dict.size(), -1);
+    for (size_t i = 0; i < h.dict.size(); ++i)
+        for (int f = 0; f < FD_N; ++f)
+            if (h.dict[i] == kFieldName[f]) field_of_key[i] = (int8_t)f;
+    return field_of_key;
+}
 
 // one decoded record of one sample file, before it is placed into the batch
 struct RecView {
@@ -902,86 +509,46 @@ bool decode_into(const RecView& r, Chunk& c, std::string& err) {
     return push_cold(r, c, (uint32_t)n, is_hp, err);
 }
 
-// ---- BCF2 typed values
-struct Typed { int type; uint32_t n; const uint8_t* data; };
-bool bcf_typed(const uint8_t*& p, const uint8_t* e, Typed& t) {
-    if (p >= e) return false;
-    const uint8_t b = *p++;
-    t.type = b & 0xf;
-    t.n = b >> 4;
-    if (t.n == 15) {
-        Typed l;
-        if (!bcf_typed(p, e, l) || l.n != 1) return false;
-        if (l.type == 1) t.n = (uint32_t)(int8_t)l.data[0];
-        else if (l.type == 2) { int16_t v; memcpy(&v, l.data, 2); t.n = (uint32_t)v; }
-        else if (l.type == 3) { int32_t v; memcpy(&v, l.data, 4); t.n = (uint32_t)v; }
-        else return false;
-    }
-    static const int size[16] = {0, 1, 2, 4, 0, 4, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0};
-    const size_t bytes = (size_t)t.n * size[t.type];
-    if ((size_t)(e - p) < bytes) return false;
-    t.data = p;
-    p += bytes;
-    return true;
-}
-int32_t typed_int(const Typed& t, uint32_t i) {
-    if (t.type == 1) return (int8_t)t.data[i];
-    if (t.type == 2) { int16_t v; memcpy(&v, t.data + 2 * i, 2); return v; }
-    int32_t v; memcpy(&v, t.data + 4 * (size_t)i, 4); return v;
-}
 double phred_to_ln(float x) { return x != x ? NAN : -(double)x * std::log(10.0) / 10.0; }  // calling.rs:470-494
 
+// one record of an observation file (or its cold copy): the shared block (bcf_walk_shared) into the fields of the v15 format
 bool parse_bcf_record(const uint8_t* rec, const uint8_t* end, const std::vector<int8_t>& field_of_key, RecView& r, std::string& err) {
-    if (end - rec < 32) { err = "truncated BCF record"; return false; }
-    uint32_t l_shared;
-    memcpy(&l_shared, rec, 4);
-    const uint8_t* p = rec + 8;
-    const uint8_t* se = p + l_shared;
-    if (se > end) { err = "truncated BCF record"; return false; }
-    int32_t chrom, pos;
-    uint32_t nai;
-    memcpy(&chrom, p, 4); memcpy(&pos, p + 4, 4); memcpy(&nai, p + 16, 4);
-    p += 24;
-    r.contig = chrom; r.pos = (int64_t)pos + 1;
-    const uint32_t n_allele = nai >> 16, n_info = nai & 0xffff;
-    Typed t;
-    if (!bcf_typed(p, se, t)) { err = "bad ID"; return false; }
-    r.id.assign((const char*)t.data, t.type == 7 ? t.n : 0);
-    for (uint32_t a = 0; a < n_allele; ++a) {
-        if (!bcf_typed(p, se, t) || (t.type != 7 && t.n != 0)) { err = "bad allele"; return false; }
-        if (a == 0) r.ref.assign((const char*)t.data, t.n);
-        else { if (a > 1) r.alt.push_back(','); r.alt.append((const char*)t.data, t.n); }
-    }
-    if (n_allele < 2) r.alt = ".";
-    if (!bcf_typed(p, se, t)) { err = "bad FILTER"; return false; }
-    for (uint32_t k = 0; k < n_info; ++k) {
-        Typed key, val;
-        if (!bcf_typed(p, se, key) || key.n != 1 || key.type < 1 || key.type > 3 || !bcf_typed(p, se, val)) { err = "bad INFO"; return false; }
-        const int32_t ki = typed_int(key, 0);
-        const int f = (ki >= 0 && (size_t)ki < field_of_key.size()) ? field_of_key[(size_t)ki] : -1;
-        if (f < 0) continue;
-        if (f < FD_N_VEC) {
-            if (val.type < 1 || val.type > 3) continue;  // read_values: info(tag).integer()
-            if (hot_field(f)) { r.wsrc[f] = val.data; r.wn[f] = val.n; r.wstride[f] = val.type == 3 ? 4 : val.type; r.present[f] = true; continue; }
-            auto& out = r.vec[f];
-            out.resize((size_t)val.n * 2);
-            // i32 -> u16 -> 2 bytes LE (mod.rs:836-842); vector-end padding cannot occur inside an INFO vector
-            if (val.type == 3) for (uint32_t i = 0; i < val.n; ++i) { out[2 * i] = val.data[4 * (size_t)i]; out[2 * i + 1] = val.data[4 * (size_t)i + 1]; }
-            else if (val.type == 2) memcpy(out.data(), val.data, (size_t)val.n * 2);
-            else for (uint32_t i = 0; i < val.n; ++i) { const int v = (int8_t)val.data[i]; out[2 * i] = (uint8_t)(v & 0xff); out[2 * i + 1] = (uint8_t)((v >> 8) & 0xff); }
-            r.present[f] = true;
-        } else if (f == FD_IMPRECISE) r.imprecise = true;
-        else if (f == FD_EVENT && val.type == 7) r.event.assign((const char*)val.data, val.n);
-        else if (f == FD_MATEID && val.type == 7) r.mateid.assign((const char*)val.data, val.n);
-        else if ((f == FD_HET || f == FD_SOM) && val.type == 5 && val.n >= 1) {
-            uint32_t bits;
-            memcpy(&bits, val.data, 4);
-            float x;
-            memcpy(&x, &bits, 4);
-            const bool missing = bits == 0x7F800001u || bits == 0x7F800002u;
-            (f == FD_HET ? r.het_ln : r.som_ln) = missing ? NAN : phred_to_ln(x);
-        }
-    }
+    static const char* const kWalkText[] = {"", "truncated BCF record", "bad ID", "bad allele", "bad FILTER", "bad INFO"};
+    BcfSite s;
+    const BcfWalk w = bcf_walk_shared(rec, end, s,
+        [&](const Typed& t) { r.id.assign((const char*)t.data, t.type == 7 ? t.n : 0); },
+        [&](uint32_t a, const Typed& t) {
+            if (a == 0) r.ref.assign((const char*)t.data, t.n);
+            else { if (a > 1) r.alt.push_back(','); r.alt.append((const char*)t.data, t.n); }
+        },
+        [&](int32_t ki, const Typed& val) {
+            const int f = (ki >= 0 && (size_t)ki < field_of_key.size()) ? field_of_key[(size_t)ki] : -1;
+            if (f < 0) return;
+            if (f < FD_N_VEC) {
+                if (val.type < 1 || val.type > 3) return;  // read_values: info(tag).integer()
+                if (hot_field(f)) { r.wsrc[f] = val.data; r.wn[f] = val.n; r.wstride[f] = val.type == 3 ? 4 : val.type; r.present[f] = true; return; }
+                auto& out = r.vec[f];
+                out.resize((size_t)val.n * 2);
+                // i32 -> u16 -> 2 bytes LE (mod.rs:836-842); vector-end padding cannot occur inside an INFO vector
+                if (val.type == 3) for (uint32_t i = 0; i < val.n; ++i) { out[2 * i] = val.data[4 * (size_t)i]; out[2 * i + 1] = val.data[4 * (size_t)i + 1]; }
+                else if (val.type == 2) memcpy(out.data(), val.data, (size_t)val.n * 2);
+                else for (uint32_t i = 0; i < val.n; ++i) { const int v = (int8_t)val.data[i]; out[2 * i] = (uint8_t)(v & 0xff); out[2 * i + 1] = (uint8_t)((v >> 8) & 0xff); }
+                r.present[f] = true;
+            } else if (f == FD_IMPRECISE) r.imprecise = true;
+            else if (f == FD_EVENT && val.type == 7) r.event.assign((const char*)val.data, val.n);
+            else if (f == FD_MATEID && val.type == 7) r.mateid.assign((const char*)val.data, val.n);
+            else if ((f == FD_HET || f == FD_SOM) && val.type == 5 && val.n >= 1) {
+                uint32_t bits;
+                memcpy(&bits, val.data, 4);
+                float x;
+                memcpy(&x, &bits, 4);
+                const bool missing = bcf_float_missing(bits) || bcf_float_end_of_vector(bits);
+                (f == FD_HET ? r.het_ln : r.som_ln) = missing ? NAN : phred_to_ln(x);
+            }
+        });
+    if (w != BCF_WALK_OK) { err = kWalkText[w]; return false; }
+    r.contig = s.contig; r.pos = (int64_t)s.pos0 + 1;
+    if (s.n_allele < 2) r.alt = ".";
     while (!r.event.empty() && r.event.back() == '\0') r.event.pop_back();
     while (!r.mateid.empty() && r.mateid.back() == '\0') r.mateid.pop_back();
     return true;
@@ -1066,23 +633,15 @@ bool read_sample_file(const char* path, int n_threads, SampleFile& sf, std::stri
     Blob data;
     if (!load_inflated(path, data, n_threads, err)) return false;
     const double t_parse0 = now_s();
-    const bool is_bcf = data.size() >= 9 && memcmp(data.data(), "BCF\2\2", 5) == 0;
     Header h;
+    size_t header_bytes = 0;
+    const BcfHead head = bcf_head(data.data(), data.size(), header_bytes, h);
+    if (head == BCF_PARTIAL) { err = std::string("truncated BCF header in ") + path; return false; }
+    const bool is_bcf = head == BCF_OK;   // (anything else is read as text VCF)
     std::vector<size_t> starts;  // record starts (+ end sentinel)
     if (is_bcf) {
-        uint32_t l_text;
-        memcpy(&l_text, data.data() + 5, 4);
-        if (9 + (size_t)l_text > data.size()) { err = std::string("truncated BCF header in ") + path; return false; }
-        std::string text((const char*)data.data() + 9, l_text);
-        while (!text.empty() && text.back() == '\0') text.pop_back();
-        parse_header(text, h);
-        size_t p = 9 + (size_t)l_text;
-        while (p + 8 <= data.size()) {
-            uint32_t ls, li;
-            memcpy(&ls, data.data() + p, 4); memcpy(&li, data.data() + p + 4, 4);
-            starts.push_back(p);
-            p += 8 + (size_t)ls + li;
-        }
+        size_t p = header_bytes, e;
+        while (bcf_frame(data.data(), data.size(), p, e)) { starts.push_back(p); p = e; }
         if (p != data.size()) { err = std::string("truncated BCF record in ") + path; return false; }
         starts.push_back(p);
         sf.contig_names = h.contigs;
@@ -1100,10 +659,7 @@ bool read_sample_file(const char* path, int n_threads, SampleFile& sf, std::stri
         parse_header(text, h);
     }
     if (!h.version_ok) { err = std::string("invalid observation format in ") + path + " (calling.rs:324-339: varlociraptor_observation_format_version=15 expected)"; return false; }
-    std::vector<int8_t> field_of_key(h.dict.size(), -1);
-    for (size_t i = 0; i < h.dict.size(); ++i)
-        for (int f = 0; f < FD_N; ++f)
-            if (h.dict[i] == kFieldName[f]) field_of_key[i] = (int8_t)f;
+    const std::vector<int8_t> field_of_key = obs_field_of_key(h);
     std::unordered_map<std::string, int> contig_ids;
     std::mutex contig_mu;
     if (!decode_records(data.data(), data.size(), starts, is_bcf, field_of_key, contig_ids, contig_mu, path, 0, n_threads, sf, err)) return false;
@@ -1617,16 +1173,10 @@ bool stream_header(FileStream& f, int n_threads, std::string& err) {
     for (;;) {
         const uint8_t* d = f.base();
         const size_t n = f.avail();
-        if (n >= 9 && memcmp(d, "BCF\2\2", 5) == 0) {
-            uint32_t l_text;
-            memcpy(&l_text, d + 5, 4);
-            if (9 + (size_t)l_text <= n) {
-                std::string text((const char*)d + 9, l_text);
-                while (!text.empty() && text.back() == '\0') text.pop_back();
-                parse_header(text, f.h);
-                f.is_bcf = true; f.pos = 9 + (size_t)l_text; f.contig_names = f.h.contigs;
-                break;
-            }
+        size_t header_bytes = 0;
+        const BcfHead head = bcf_head(d, n, header_bytes, f.h);
+        if (head == BCF_OK) { f.is_bcf = true; f.pos = header_bytes; f.contig_names = f.h.contigs; break; }
+        if (head == BCF_PARTIAL) {   // (the rest of the header is in the next members, or the file ends inside it)
         } else if (n > 0 && d[0] == '#') {
             // all header lines must be in the window: the first line that does not start with '#' ends it
             size_t p = 0;
@@ -1646,10 +1196,7 @@ bool stream_header(FileStream& f, int n_threads, std::string& err) {
         if (!stream_fill(f, 64, n_threads, err)) return false;
     }
     if (!f.h.version_ok) { err = std::string("invalid observation format in ") + f.path + " (calling.rs:324-339: varlociraptor_observation_format_version=15 expected)"; return false; }
-    f.field_of_key.assign(f.h.dict.size(), -1);
-    for (size_t i = 0; i < f.h.dict.size(); ++i)
-        for (int k = 0; k < FD_N; ++k)
-            if (f.h.dict[i] == kFieldName[k]) f.field_of_key[i] = (int8_t)k;
+    f.field_of_key = obs_field_of_key(f.h);
     f.header_done = true;
     return true;
 }
@@ -1662,14 +1209,8 @@ bool stream_next(FileStream& f, int64_t max_records, int n_threads, SampleFile& 
         const uint8_t* d = f.base();
         const size_t n = f.avail();
         if (f.is_bcf) {
-            while ((int64_t)starts.size() < max_records && scan + 8 <= n) {
-                uint32_t ls, li;
-                memcpy(&ls, d + scan, 4); memcpy(&li, d + scan + 4, 4);
-                const size_t e = scan + 8 + (size_t)ls + li;
-                if (e > n) break;
-                starts.push_back(scan);
-                scan = e;
-            }
+            size_t e;
+            while ((int64_t)starts.size() < max_records && bcf_frame(d, n, scan, e)) { starts.push_back(scan); scan = e; }
         } else {
             while ((int64_t)starts.size() < max_records && scan < n) {
                 const uint8_t* nl = (const uint8_t*)memchr(d + scan, '\n', n - scan);
@@ -2033,7 +1574,7 @@ int count_header_samples(const std::string& text) {
     return tabs >= 9 ? tabs - 8 : 0;  // CHROM POS ID REF ALT QUAL FILTER INFO [FORMAT sample...]
 }
 
-int dev_stream_header(DevFileStream& f, const char* path, const std::vector<uint8_t>& head, size_t need, int device);
+int dev_stream_header(DevFileStream& f, const char* path, size_t need, int device);
 
 // Descriptor mode (plain readers of files above 32 MB, VLR_INGEST_STAGE=0: off): the file is opened, its first megabyte read for the BCF
 // header, and everything else — bytes into the page-locked ring, member chain — is the stager's work beside the reader.  Returns
@@ -2053,6 +1594,7 @@ int dev_stream_open_fd(DevFileStream& f, const char* path, int device) {
     // the members of the first megabyte, inflated until the header is complete
     std::vector<uint8_t> head;
     size_t need = 9, p = 0;
+    BcfHead hs = BCF_SHORT;
     bool ok = true;
     while (head.size() < need && ok) {
         if (p + 18 > got || first[p] != 0x1f || first[p + 1] != 0x8b || first[p + 2] != 8 || !(first[p + 3] & 4)) { ok = false; break; }
@@ -2073,17 +1615,13 @@ int dev_stream_open_fd(DevFileStream& f, const char* path, int device) {
         const size_t old = head.size();
         head.resize(old + isize);
         if (isize && !inflate_raw(first.data() + xend, cend - xend, head.data() + old, isize, crc)) { close(fd); return ifail(VLR_ERR_INVALID_ARGUMENT, "corrupt BGZF block in %s", path); }
-        if (head.size() >= 9 && need == 9) {
-            if (memcmp(head.data(), "BCF\2\2", 5) != 0) { close(fd); return ifail(VLR_ERR_UNSUPPORTED, "device reader: %s is not a BCF2 file (use vlr_obs_reader_open)", path); }
-            uint32_t l_text;
-            memcpy(&l_text, head.data() + 5, 4);
-            need = 9 + (size_t)l_text;
-        }
+        hs = bcf_head(head.data(), head.size(), need, f.h);
+        if (hs == BCF_NOT) { close(fd); return ifail(VLR_ERR_UNSUPPORTED, "device reader: %s is not a BCF2 file (use vlr_obs_reader_open)", path); }
         p += (size_t)bsize;
     }
-    if (!ok || head.size() < need || need == 9) { close(fd); return VLR_ERR_UNSUPPORTED; }   // (not BGZF, or a header beyond the first megabyte: the mapped path decides)
+    if (!ok || hs != BCF_OK || need == 9) { close(fd); return VLR_ERR_UNSUPPORTED; }   // (not BGZF, or a header beyond the first megabyte: the mapped path decides)
     f.path = path;
-    const int rc = dev_stream_header(f, path, head, need, device);
+    const int rc = dev_stream_header(f, path, need, device);
     if (rc != VLR_OK) { close(fd); return rc; }
     f.fd = fd;
     f.stage.reset(new StageRing());
@@ -2106,34 +1644,25 @@ int dev_stream_open(DevFileStream& f, const char* path, int device) {
     std::vector<uint8_t> head;
     size_t b = 0;
     size_t need = 9;
+    BcfHead hs = BCF_SHORT;
     while (head.size() < need && b < f.blocks.size()) {
         const BgzfBlock& k = f.blocks[b++];
         const size_t old = head.size();
         head.resize(old + k.isize);
         if (k.isize && !inflate_raw(f.raw.p + k.off, k.clen, head.data() + old, k.isize, k.crc)) return ifail(VLR_ERR_INVALID_ARGUMENT, "corrupt BGZF block in %s", path);
-        if (head.size() >= 9 && need == 9) {
-            if (memcmp(head.data(), "BCF\2\2", 5) != 0) return ifail(VLR_ERR_UNSUPPORTED, "device reader: %s is not a BCF2 file (use vlr_obs_reader_open)", path);
-            uint32_t l_text;
-            memcpy(&l_text, head.data() + 5, 4);
-            need = 9 + (size_t)l_text;
-        }
+        hs = bcf_head(head.data(), head.size(), need, f.h);
+        if (hs == BCF_NOT) return ifail(VLR_ERR_UNSUPPORTED, "device reader: %s is not a BCF2 file (use vlr_obs_reader_open)", path);
     }
-    if (head.size() < need || need == 9) return ifail(VLR_ERR_INVALID_ARGUMENT, "truncated header in %s", path);
-    return dev_stream_header(f, path, head, need, device);
+    if (hs != BCF_OK || need == 9) return ifail(VLR_ERR_INVALID_ARGUMENT, "truncated header in %s", path);
+    return dev_stream_header(f, path, need, device);
 }
 
-// the parsed header, the field table and the device side of a file whose inflated header bytes are `head`
-int dev_stream_header(DevFileStream& f, const char* path, const std::vector<uint8_t>& head, size_t need, int device) {
-    std::string text((const char*)head.data() + 9, need - 9);
-    while (!text.empty() && text.back() == '\0') text.pop_back();
-    parse_header(text, f.h);
+// the field table and the device side of a file whose header (`need` inflated bytes) bcf_head has parsed into f.h
+int dev_stream_header(DevFileStream& f, const char* path, size_t need, int device) {
     if (!f.h.version_ok) return ifail(VLR_ERR_INVALID_ARGUMENT, "invalid observation format in %s (calling.rs:324-339: varlociraptor_observation_format_version=15 expected)", path);
     f.header_bytes = need;
-    f.n_hdr_samples = count_header_samples(text);
-    f.field_of_key.assign(f.h.dict.size(), -1);
-    for (size_t i = 0; i < f.h.dict.size(); ++i)
-        for (int k = 0; k < FD_N; ++k)
-            if (f.h.dict[i] == kFieldName[k]) f.field_of_key[i] = (int8_t)k;
+    f.n_hdr_samples = count_header_samples(f.h.text);
+    f.field_of_key = obs_field_of_key(f.h);
     return vlr_dev_file_create(device, &f.dev);
 }
 
@@ -2897,10 +2426,11 @@ void build_out_header(const std::string& header_text, OutHeader& h) {
     for (auto& l : meta) {
         const bool d = l.compare(0, 9, "##FILTER=") == 0 || l.compare(0, 7, "##INFO=") == 0 || l.compare(0, 9, "##FORMAT=") == 0;
         if (d) {
+            if (l.find('<') == std::string::npos) continue;   // (as parse_header: a line without its body is no dictionary entry)
             const std::string body = l.substr(l.find('<'));
             const std::string id = attr(body, "ID"), idx = attr(body, "IDX");
             if (!h.dict.count(id)) { const int i = idx.empty() ? next : atoi(idx.c_str()); h.dict[id] = i; next = std::max(next, i + 1); }
-        } else if (l.compare(0, 9, "##contig=") == 0) {
+        } else if (l.compare(0, 9, "##contig=") == 0 && l.find('<') != std::string::npos) {
             const std::string body = l.substr(l.find('<'));
             const std::string id = attr(body, "ID"), idx = attr(body, "IDX");
             if (!h.contigs.count(id)) { const int i = idx.empty() ? cnext : atoi(idx.c_str()); h.contigs[id] = i; cnext = std::max(cnext, i + 1); }
@@ -2918,12 +2448,6 @@ std::string fmt_g(float x) {
     char b[48];
     snprintf(b, sizeof b, "%g", (double)x);
     return b;
-}
-bool relative_eq(double a, double b) {
-    if (a == b) return true;
-    if (std::isinf(a) || std::isinf(b)) return false;  // (approx::RelativeEq: infinities are equal only to themselves)
-    const double d = std::fabs(a - b), eps = std::numeric_limits<double>::epsilon();
-    return d <= eps || d <= std::max(std::fabs(a), std::fabs(b)) * eps;
 }
 char kr_letter(double bf) {  // utils/mod.rs:158-167 over bio's Kass-Raftery scale
     if (bf <= 1.0) return relative_eq(bf, 1.0) ? 'E' : 'N';
@@ -3244,8 +2768,7 @@ int vlr_calls_concat_parts(const char* path, const char* const* parts, int n_par
         ok = ok && !ferror(in);
         fclose(in);
     }
-    static const uint8_t kEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    ok = ok && fwrite(kEof, 1, sizeof kEof, o) == sizeof kEof;
+    ok = ok && fwrite(kBgzfEof, 1, sizeof kBgzfEof, o) == sizeof kBgzfEof;
     ok = (fclose(o) == 0) && ok;
     if (!ok) return ifail(VLR_ERR_INVALID_ARGUMENT, "assembling %s from its parts failed", path);
     for (int k = 0; k < n_parts; ++k) (void)remove(parts[k]);
@@ -3410,7 +2933,7 @@ static int calls_write_impl(FILE* out_file, bool bcf, bool with_header, bool wit
                 const int i = order[(size_t)k];
                 put_typed_int_scalar(shared, tag_key[(size_t)i]);
                 shared.push_back(0x15);
-                uint32_t bits = 0x7F800001u;  // missing
+                uint32_t bits = kBcfFloatMissing;
                 if (!missing && lp[i] == lp[i]) { const float v = (float)std::fabs(-10.0 * lp[i] / LN10); memcpy(&bits, &v, 4); }
                 put_u32(shared, bits);
             }
@@ -3440,7 +2963,7 @@ static int calls_write_impl(FILE* out_file, bool bcf, bool with_header, bool wit
             put_typed_int_scalar(indiv, fmt_key[1]);
             put_desc(indiv, 1, 5);
             for (int s = 0; s < S; ++s) {
-                uint32_t bits = 0x7F800001u;
+                uint32_t bits = kBcfFloatMissing;
                 if (!missing && sf[(size_t)s].af == sf[(size_t)s].af) memcpy(&bits, &sf[(size_t)s].af, 4);
                 put_u32(indiv, bits);
             }
@@ -3457,7 +2980,7 @@ static int calls_write_impl(FILE* out_file, bool bcf, bool with_header, bool wit
             put_u32(out, (uint32_t)contig_idx[(size_t)ci]);
             put_u32(out, (uint32_t)(t->pos[(size_t)l] - 1));
             put_u32(out, (uint32_t)strlen(ref));
-            put_u32(out, 0x7F800001u);  // QUAL missing
+            put_u32(out, kBcfFloatMissing);  // QUAL
             put_u32(out, (n_allele << 16) | (uint32_t)n_out);
             put_u32(out, (13u << 24) | (uint32_t)S);
             out.insert(out.end(), shared.begin(), shared.end());
@@ -3629,7 +3152,7 @@ int vlr_obs_write(const char* path, const vlr_batch* in, int sample, const vlr_o
             }
             put_u32(out, 24 + (uint32_t)shared.size()); put_u32(out, 0);
             put_u32(out, (uint32_t)contig); put_u32(out, (uint32_t)(pos - 1)); put_u32(out, (uint32_t)ref.size());
-            put_u32(out, 0x7F800001u);
+            put_u32(out, kBcfFloatMissing);  // QUAL
             put_u32(out, (n_allele << 16) | n_info);
             put_u32(out, 0);
             out.insert(out.end(), shared.begin(), shared.end());
@@ -3647,605 +3170,3 @@ int vlr_obs_write(const char* path, const vlr_batch* in, int sample, const vlr_o
 }
 
 }  // extern "C"
-
-// ================================================================================================ filter-calls control-fdr
-// The whole of `varlociraptor filter-calls control-fdr` behind the ABI (reference src/filtration/fdr.rs:36-158,
-// src/utils/mod.rs:169-374, record typing src/utils/collect_variants.rs:44-304): calls BCF in -> kept records out, the threshold
-// search on the device (vlr_fdr_threshold).  The Python restatement the tests compare with: varlociraptor_amd/fdr.py.
-extern "C" int vlr_fdr_threshold(int device, const double* ln_prob, int64_t n, int smart, double alpha_ln, double* threshold, int* status);
-namespace {
-constexpr double kNumericalEpsilon = 1e-3;  // utils/mod.rs:40
-struct CallRec {
-    const uint8_t* raw = nullptr;
-    size_t raw_len = 0;
-    int64_t pos0 = 0;
-    std::string ref, event, svtype;
-    std::vector<std::string> alts;
-    bool has_event = false, has_svlen = false, has_end = false;
-    std::vector<int64_t> svlen;      // |SVLEN| per entry, -1 = missing
-    int64_t end0 = 0;                // END - 1
-    std::vector<std::vector<double>> prob;  // per wanted tag: PHRED values per ALT (NaN = missing), empty = tag absent
-    // estimate mutational-burden only (read_call_records(.., with_ann_af = true))
-    int32_t contig = -1;
-    bool has_ann = false, has_af = false;
-    std::string ann;                       // INFO/ANN, entries separated by ','
-    std::vector<std::vector<float>> af;    // FORMAT/AF per sample of the file (missing value = NaN, end-of-vector trimmed)
-};
-struct VarType { int kind = -1; int64_t len = 0; };  // kind < 0: skipped by collect_variants
-enum { VK_SNV, VK_MNV, VK_INS, VK_DEL, VK_BND, VK_INV, VK_DUP, VK_REP, VK_REF, VK_METH };
-int vk_of(const std::string& s) {
-    static const char* const n[] = {"SNV", "MNV", "INS", "DEL", "BND", "INV", "DUP", "REP", "REF", "METH"};
-    for (int i = 0; i < 10; ++i) if (s == n[i]) return i;
-    return -1;
-}
-bool valid_del(const std::string& r, const std::string& a) { return a == "<DEL>" || (r.size() > a.size() && r.compare(0, a.size(), a) == 0 && a.size() == 1); }
-bool valid_ins(const std::string& r, const std::string& a) { return a == "<INS>" || (r.size() < a.size() && a.compare(0, r.size(), r) == 0 && r.size() == 1); }
-// (type, length) per ALT allele as collect_variants types it (collect_variants.rs:44-304)
-bool variant_types(const CallRec& r, std::vector<VarType>& out, std::string& err) {
-    out.clear();
-    if (!r.svtype.empty()) {
-        const std::string& sv = r.svtype;
-        if (sv == "INV" || sv == "DUP") {
-            VarType v;
-            if (r.alts.size() == 1 && r.has_end) { v.kind = sv == "INV" ? VK_INV : VK_DUP; v.len = r.end0 + 1 - r.pos0; }
-            out.push_back(v);
-        } else if (sv == "BND") {
-            for (size_t i = 0; i < r.alts.size(); ++i) out.push_back(VarType{VK_BND, 0});
-        } else if (sv == "INS") {
-            VarType v;
-            if (!r.alts.empty() && r.alts[0] != "<INS>" && valid_ins(r.ref, r.alts[0])) { v.kind = VK_INS; v.len = (int64_t)r.alts[0].size() - (int64_t)r.ref.size(); }
-            out.push_back(v);
-        } else if (sv == "DEL") {
-            int64_t svlen;
-            if (r.has_svlen && !r.svlen.empty() && r.svlen[0] >= 0) svlen = r.svlen[0];
-            else if (!r.has_svlen && r.has_end) svlen = r.end0 - (r.pos0 + 1);  // collect_variants.rs:196-199
-            else { err = "missing SVLEN or END"; return false; }
-            VarType v;
-            if (!r.alts.empty() && valid_del(r.ref, r.alts[0])) { v.kind = VK_DEL; v.len = svlen; }
-            out.push_back(v);
-        }
-        return true;
-    }
-    for (size_t i = 0; i < r.alts.size(); ++i) {
-        const std::string& a = r.alts[i];
-        VarType v;
-        if (a == "<*>") v = VarType{VK_REF, 0};
-        else if (a == "<DEL>") { if (r.has_svlen && i < r.svlen.size() && r.svlen[i] >= 0) v = VarType{VK_DEL, r.svlen[i]}; }
-        else if (a == "<METH>") v = VarType{VK_METH, 0};
-        else if (!a.empty() && a[0] == '<') {}
-        else if (a.size() == 1 && r.ref.size() == 1) v = VarType{VK_SNV, 1};
-        else if (a.size() == r.ref.size()) v = VarType{VK_MNV, (int64_t)a.size()};
-        else if (valid_del(r.ref, a)) v = VarType{VK_DEL, (int64_t)r.ref.size() - (int64_t)a.size()};
-        else if (valid_ins(r.ref, a)) v = VarType{VK_INS, (int64_t)a.size() - (int64_t)r.ref.size()};
-        else v = VarType{VK_REP, 0};
-        out.push_back(v);
-    }
-    return true;
-}
-struct TypeFilter { int kind = -1; bool has_range = false; int64_t lo = 0, hi = 0; };
-bool is_type(const VarType& v, const TypeFilter& f) {  // Variant::is_type (variants/model/mod.rs)
-    if (v.kind < 0) return false;
-    if (f.kind < 0) return true;
-    if (v.kind != f.kind) return false;
-    return !f.has_range || (f.lo <= v.len && v.len < f.hi);
-}
-double lse(const std::vector<double>& v) {  // bio LogProb::ln_sum_exp: the maximum apart, ln_1p of the others
-    if (v.empty()) return -INFINITY;
-    size_t im = 0;
-    for (size_t i = 1; i < v.size(); ++i)
-        if (v[i] > v[im]) im = i;
-    const double m = v[im];
-    if (m == -INFINITY) return m;
-    double s = 0.0;
-    for (size_t i = 0; i < v.size(); ++i)
-        if (i != im && v[i] != -INFINITY) s += std::exp(v[i] - m);
-    return m + std::log1p(s);
-}
-// utils/mod.rs:177-212: ln-sum over the given PROB_* tags per (typed) variant; NaN = None
-void tags_prob_sum(const CallRec& r, const std::vector<VarType>& types, const std::vector<int>& tags, const TypeFilter& tf, std::vector<double>& out) {
-    std::vector<const VarType*> variants;
-    for (auto& v : types) if (v.kind >= 0) variants.push_back(&v);
-    std::vector<std::vector<double>> acc(variants.size());
-    for (int t : tags) {
-        const std::vector<double>& vals = r.prob[(size_t)t];
-        for (size_t i = 0; i < variants.size() && i < vals.size(); ++i) {
-            const double p = vals[i];
-            if (p != p || !is_type(*variants[i], tf)) continue;
-            acc[i].push_back(-p * std::log(10.0) / 10.0);
-        }
-    }
-    out.clear();
-    for (auto& probs : acc) {
-        if (probs.empty()) { out.push_back(NAN); continue; }
-        double s = lse(probs);
-        if (0.0 < s && s <= kNumericalEpsilon) s = 0.0;  // cap_numerical_overshoot
-        out.push_back(s);
-    }
-}
-double ln_one_minus_exp(double p) { return p < 0.0 ? (p < -0.693 ? std::log1p(-std::exp(p)) : std::log(-std::expm1(p))) : -INFINITY; }
-
-// a calls BCF in memory: header, sample names, records (views into `data`)
-struct CallsFile {
-    Blob data;
-    uint32_t l_text = 0;
-    Header h;
-    std::vector<std::string> samples;  // the columns of the #CHROM line behind FORMAT
-    std::vector<CallRec> recs;
-};
-int open_calls(const char* in_path, int n_threads, CallsFile& f) {
-    std::string err;
-    if (!load_inflated(in_path, f.data, n_threads, err)) return ifail(VLR_ERR_INVALID_ARGUMENT, "%s", err.c_str());
-    if (f.data.size() < 9 || memcmp(f.data.data(), "BCF\2\2", 5) != 0) return ifail(VLR_ERR_INVALID_ARGUMENT, "%s is not a BCF file", in_path);
-    memcpy(&f.l_text, f.data.data() + 5, 4);
-    if (9 + (size_t)f.l_text > f.data.size()) return ifail(VLR_ERR_INVALID_ARGUMENT, "truncated BCF header in %s", in_path);
-    std::string text((const char*)f.data.data() + 9, f.l_text);
-    while (!text.empty() && text.back() == '\0') text.pop_back();
-    parse_header(text, f.h);
-    const size_t c = text.find("#CHROM");
-    if (c != std::string::npos && (c == 0 || text[c - 1] == '\n')) {
-        size_t e = text.find('\n', c);
-        if (e == std::string::npos) e = text.size();
-        int col = 0;
-        for (size_t q = c; q <= e;) {
-            size_t t = text.find('\t', q);
-            if (t == std::string::npos || t > e) t = e;
-            if (col >= 9) f.samples.push_back(text.substr(q, t - q));
-            ++col;
-            q = t + 1;
-        }
-    }
-    return VLR_OK;
-}
-// the records of an opened calls file: alleles, the float INFO tags `tag_names` (CallRec::prob in that order), EVENT, SVTYPE, SVLEN,
-// END; with_ann_af: INFO/ANN and FORMAT/AF as well
-int read_call_records(const char* in_path, CallsFile& f, const std::vector<std::string>& tag_names, bool with_ann_af) {
-    const Header& h = f.h;
-    std::vector<int> key_tag(h.dict.size(), -1);  // dictionary index -> 0.. wanted tag, -2 EVENT, -3 SVTYPE, -4 SVLEN, -5 END, -6 ANN, -7 AF
-    for (size_t k = 0; k < h.dict.size(); ++k) {
-        for (size_t t = 0; t < tag_names.size(); ++t) if (h.dict[k] == tag_names[t]) key_tag[k] = (int)t;
-        if (h.dict[k] == "EVENT") key_tag[k] = -2;
-        else if (h.dict[k] == "SVTYPE") key_tag[k] = -3;
-        else if (h.dict[k] == "SVLEN") key_tag[k] = -4;
-        else if (h.dict[k] == "END") key_tag[k] = -5;
-        else if (with_ann_af && h.dict[k] == "ANN") key_tag[k] = -6;
-        else if (with_ann_af && h.dict[k] == "AF") key_tag[k] = -7;
-    }
-    std::vector<CallRec>& recs = f.recs;
-    const Blob& data = f.data;
-    const uint32_t l_text = f.l_text;
-    const uint8_t* p = data.data() + 9 + l_text;
-    const uint8_t* const e = data.data() + data.size();
-    while (p + 8 <= e) {
-        uint32_t ls, li;
-        memcpy(&ls, p, 4); memcpy(&li, p + 4, 4);
-        const size_t len = 8 + (size_t)ls + li;
-        if ((size_t)(e - p) < len || ls < 24) return ifail(VLR_ERR_INVALID_ARGUMENT, "truncated BCF record in %s", in_path);
-        CallRec r;
-        r.raw = p; r.raw_len = len;
-        r.prob.resize(tag_names.size());
-        const uint8_t* q = p + 8;
-        const uint8_t* se = q + ls;
-        int32_t pos;
-        uint32_t nai, nfs;
-        memcpy(&r.contig, q, 4); memcpy(&pos, q + 4, 4); memcpy(&nai, q + 16, 4); memcpy(&nfs, q + 20, 4);
-        q += 24;
-        r.pos0 = pos;
-        const uint32_t n_allele = nai >> 16, n_info = nai & 0xffff;
-        Typed t;
-        if (!bcf_typed(q, se, t)) return ifail(VLR_ERR_INVALID_ARGUMENT, "bad ID field in %s", in_path);
-        for (uint32_t a = 0; a < n_allele; ++a) {
-            if (!bcf_typed(q, se, t) || (t.type != 7 && t.n != 0)) return ifail(VLR_ERR_INVALID_ARGUMENT, "bad allele in %s", in_path);
-            std::string s((const char*)t.data, t.n);
-            if (a == 0) r.ref = s; else r.alts.push_back(s);
-        }
-        if (!bcf_typed(q, se, t)) return ifail(VLR_ERR_INVALID_ARGUMENT, "bad FILTER field in %s", in_path);
-        for (uint32_t k = 0; k < n_info; ++k) {
-            Typed key, val;
-            if (!bcf_typed(q, se, key) || key.n != 1 || key.type < 1 || key.type > 3 || !bcf_typed(q, se, val)) return ifail(VLR_ERR_INVALID_ARGUMENT, "bad INFO field in %s", in_path);
-            const int32_t ki = typed_int(key, 0);
-            const int kt = (ki >= 0 && (size_t)ki < key_tag.size()) ? key_tag[(size_t)ki] : -1;
-            if (kt >= 0 && val.type == 5) {
-                auto& v = r.prob[(size_t)kt];
-                for (uint32_t i = 0; i < val.n; ++i) {
-                    uint32_t bits;
-                    memcpy(&bits, val.data + 4 * (size_t)i, 4);
-                    if (bits == 0x7F800002u) break;  // end of vector
-                    float x;
-                    memcpy(&x, &bits, 4);
-                    v.push_back(bits == 0x7F800001u ? NAN : (double)x);
-                }
-                if (v.empty()) v.push_back(NAN);  // (a present tag is a list: keeps "tag absent" apart)
-            } else if (kt == -2 && val.type == 7) {
-                r.event.assign((const char*)val.data, val.n);
-                while (!r.event.empty() && r.event.back() == '\0') r.event.pop_back();
-                r.has_event = true;
-            } else if (kt == -3 && val.type == 7) {
-                r.svtype.assign((const char*)val.data, val.n);
-                while (!r.svtype.empty() && r.svtype.back() == '\0') r.svtype.pop_back();
-            } else if (kt == -6 && val.type == 7) {
-                r.ann.assign((const char*)val.data, val.n);
-                while (!r.ann.empty() && r.ann.back() == '\0') r.ann.pop_back();
-                r.has_ann = true;
-            } else if ((kt == -4 || kt == -5) && val.type >= 1 && val.type <= 3) {
-                static const int32_t miss[4] = {0, -128, -32768, (int32_t)0x80000000}, eov[4] = {0, -127, -32767, (int32_t)0x80000001};
-                std::vector<int64_t> vals;
-                for (uint32_t i = 0; i < val.n; ++i) {
-                    const int32_t x = typed_int(val, i);
-                    if (x == eov[val.type]) continue;
-                    vals.push_back(x == miss[val.type] ? -1 : (kt == -4 ? std::llabs((long long)x) : (int64_t)x));
-                }
-                if (kt == -4) { r.has_svlen = true; r.svlen = vals; }
-                else if (!vals.empty()) { r.has_end = true; r.end0 = vals[0] - 1; }
-            }
-        }
-        if (with_ann_af) {  // FORMAT blocks: key, type descriptor, n_sample vectors
-            const uint32_t n_fmt = nfs >> 24, n_sample = nfs & 0xffffff;
-            const uint8_t* fq = se;
-            const uint8_t* const fe = p + len;
-            static const int size[16] = {0, 1, 2, 4, 0, 4, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0};
-            for (uint32_t k = 0; k < n_fmt; ++k) {
-                Typed key;
-                if (!bcf_typed(fq, fe, key) || key.n != 1 || key.type < 1 || key.type > 3 || fq >= fe) return ifail(VLR_ERR_INVALID_ARGUMENT, "bad FORMAT field in %s", in_path);
-                const uint8_t b = *fq++;
-                const int type = b & 0xf;
-                uint32_t n = b >> 4;
-                if (n == 15) {
-                    Typed l;
-                    if (!bcf_typed(fq, fe, l) || l.n != 1 || l.type < 1 || l.type > 3 || typed_int(l, 0) < 0) return ifail(VLR_ERR_INVALID_ARGUMENT, "bad FORMAT field in %s", in_path);
-                    n = (uint32_t)typed_int(l, 0);
-                }
-                const size_t bytes = (size_t)n * size[type] * n_sample;
-                if ((size_t)(fe - fq) < bytes) return ifail(VLR_ERR_INVALID_ARGUMENT, "truncated FORMAT field in %s", in_path);
-                const int32_t ki = typed_int(key, 0);
-                if (ki >= 0 && (size_t)ki < key_tag.size() && key_tag[(size_t)ki] == -7 && type == 5) {
-                    r.has_af = true;
-                    r.af.assign(n_sample, std::vector<float>());
-                    for (uint32_t sidx = 0; sidx < n_sample; ++sidx)
-                        for (uint32_t i = 0; i < n; ++i) {
-                            uint32_t bits;
-                            memcpy(&bits, fq + 4 * ((size_t)sidx * n + i), 4);
-                            if (bits == 0x7F800002u) break;
-                            float x;
-                            memcpy(&x, &bits, 4);
-                            r.af[sidx].push_back(bits == 0x7F800001u ? NAN : x);
-                        }
-                }
-                fq += bytes;
-            }
-        }
-        recs.push_back(std::move(r));
-        p += len;
-    }
-    return VLR_OK;
-}
-}  // namespace
-
-extern "C" int vlr_calls_filter_fdr(const char* in_path, const char* out_path, int n_events, const char* const* events, double alpha, uint32_t mode,
-                                    const char* vartype, int64_t minlen, int64_t maxlen, int device, int n_threads, int64_t* n_kept, int64_t* n_total) {
-    if (!in_path || !out_path || n_events <= 0 || !events) return ifail(VLR_ERR_INVALID_ARGUMENT, "null argument");
-    if (!(alpha > 0.0)) return ifail(VLR_ERR_INVALID_ARGUMENT, "alpha must be positive");
-    const bool local = (mode & VLR_FDR_MODE_LOCAL) != 0, smart = (mode & VLR_FDR_MODE_SMART) != 0, retain = (mode & VLR_FDR_MODE_RETAIN_ARTIFACTS) != 0;
-    n_threads = pick_threads(n_threads);
-    TypeFilter tf;
-    if (vartype && *vartype) {
-        tf.kind = vk_of(vartype);
-        if (tf.kind < 0) return ifail(VLR_ERR_INVALID_ARGUMENT, "unknown variant type %s", vartype);
-        if (minlen >= 0 || maxlen >= 0) { tf.has_range = true; tf.lo = minlen >= 0 ? minlen : 0; tf.hi = maxlen >= 0 ? maxlen : ((int64_t)1 << 62); }
-    }
-    std::string err;
-    CallsFile cf;
-    if (int rc = open_calls(in_path, n_threads, cf)) return rc;
-    const Header& h = cf.h;
-    const Blob& data = cf.data;
-    const uint32_t l_text = cf.l_text;
-    // wanted INFO tags: the events' PROB_* (those the header declares, fdr.rs:46-60), PROB_ABSENT, PROB_ARTIFACT
-    std::vector<std::string> tag_names;
-    auto tag_id = [&](const std::string& name) {
-        for (size_t i = 0; i < tag_names.size(); ++i) if (tag_names[i] == name) return (int)i;
-        tag_names.push_back(name);
-        return (int)tag_names.size() - 1;
-    };
-    auto declared = [&](const std::string& name) { return std::find(h.dict.begin(), h.dict.end(), name) != h.dict.end() && h.text.find("##INFO=<ID=" + name + ",") != std::string::npos; };
-    std::vector<int> ev_tags;
-    for (int i = 0; i < n_events; ++i) {
-        std::string t = "PROB_";
-        for (const char* q = events[i]; *q; ++q) t.push_back((char)toupper((unsigned char)*q));
-        if (declared(t)) ev_tags.push_back(tag_id(t));
-    }
-    if (ev_tags.empty()) return ifail(VLR_ERR_INVALID_ARGUMENT, "invalid FDR control events");  // errors::Error::InvalidFDRControlEvents
-    const int t_absent = tag_id("PROB_ABSENT"), t_artifact = tag_id("PROB_ARTIFACT");
-    if (int rc = read_call_records(in_path, cf, tag_names, false)) return rc;
-    const std::vector<CallRec>& recs = cf.recs;
-    const int64_t N = (int64_t)recs.size();
-    std::vector<std::vector<VarType>> types((size_t)N);
-    for (int64_t i = 0; i < N; ++i)
-        if (!variant_types(recs[(size_t)i], types[(size_t)i], err)) return ifail(VLR_ERR_INVALID_ARGUMENT, "%s (record %lld of %s)", err.c_str(), (long long)i, in_path);
-    // threshold (fdr.rs:62-141)
-    const double alpha_ln = std::log(alpha);
-    bool have_thr = false;
-    double thr = 0.0;
-    if (local) { have_thr = true; thr = alpha < 1.0 ? std::log1p(-alpha) : -INFINITY; }
-    else if (alpha != 1.0) {
-        std::vector<int> dist_tags;
-        if (smart) { dist_tags.push_back(t_absent); if (!retain) dist_tags.push_back(t_artifact); }
-        else dist_tags = ev_tags;
-        std::vector<double> dist, sums;
-        std::unordered_set<std::string> seen;
-        for (int64_t i = 0; i < N; ++i) {  // utils/mod.rs:236-270: one entry per breakend event
-            const CallRec& r = recs[(size_t)i];
-            if (r.has_event) { if (seen.count(r.event)) continue; seen.insert(r.event); }
-            tags_prob_sum(r, types[(size_t)i], dist_tags, tf, sums);
-            for (double s : sums) if (s == s) dist.push_back(s);
-        }
-        int status = 0;
-        const int rc = vlr_fdr_threshold(device, dist.data(), (int64_t)dist.size(), smart ? 1 : 0, alpha_ln, &thr, &status);
-        if (rc != 0) return rc;
-        if (status == VLR_FDR_VALUE) have_thr = true;
-        else if (status == VLR_FDR_LN_ONE) { have_thr = true; thr = 0.0; }
-    }
-    // filter_by_threshold (utils/mod.rs:288-374)
-    std::vector<int> ftags = ev_tags, absent_tags{t_absent};
-    if (smart && retain) ftags.push_back(t_artifact); else absent_tags.push_back(t_artifact);
-    std::unordered_map<std::string, bool> decisions;
-    std::vector<uint8_t> header_bytes(data.data(), data.data() + 9 + l_text);
-    std::vector<uint8_t> body;
-    int64_t kept = 0;
-    std::vector<double> pe, pa;
-    for (int64_t i = 0; i < N; ++i) {
-        const CallRec& r = recs[(size_t)i];
-        tags_prob_sum(r, types[(size_t)i], ftags, tf, pe);
-        if (smart) tags_prob_sum(r, types[(size_t)i], absent_tags, tf, pa);
-        bool keep_any = false;
-        for (size_t v = 0; v < pe.size(); ++v) {
-            bool keep;
-            auto it = r.has_event ? decisions.find(r.event) : decisions.end();
-            if (r.has_event && it != decisions.end()) keep = it->second;
-            else {
-                const double prob_events = pe[v];
-                double p = prob_events;
-                if (smart) { const double a = v < pa.size() ? pa[v] : NAN; p = (a == a) ? ln_one_minus_exp(a) : NAN; }
-                if (p == p && have_thr) keep = p > thr || relative_eq(p, thr);
-                else if (p == p) keep = true;
-                else keep = false;
-                if (smart) keep = keep && (prob_events == prob_events && prob_events > std::log(0.5));
-                if (r.has_event) decisions[r.event] = keep;
-            }
-            keep_any = keep_any || keep;
-        }
-        if (keep_any) {
-            // The reference removes the alleles that did not pass (filter_calls, utils/mod.rs:382-417: record.remove_alleles) and
-            // asserts one filter decision per ALT.  This entry writes kept records byte for byte, which is the same thing for the
-            // single-ALT records `call variants` emits; anything else is refused rather than emitted untrimmed.
-            if (r.alts.size() > 1 || pe.size() != r.alts.size())
-                return ifail(VLR_ERR_UNSUPPORTED, "record %lld of %s has %zu ALT alleles (%zu typed variants): multi-allelic calls files are not supported by control-fdr here",
-                             (long long)i, in_path, r.alts.size(), pe.size());
-            body.insert(body.end(), r.raw, r.raw + r.raw_len); ++kept;
-        }
-    }
-    if (!write_bgzf_file(out_path, {&header_bytes, &body}, n_threads, 6, err)) return ifail(VLR_ERR_INVALID_ARGUMENT, "%s", err.c_str());
-    if (n_kept) *n_kept = kept;
-    if (n_total) *n_total = N;
-    return VLR_OK;
-}
-
-// ================================================================================================ filter-calls posterior-odds
-// The whole of `varlociraptor filter-calls posterior-odds` behind the ABI (reference src/filtration/posterior_odds.rs:19-82,
-// utils/mod.rs:177-226, 382-446): calls BCF in -> kept records out; both ln-sums per typed variant are formed here, the
-// Kass-Raftery decisions are made on the device (vlr_posterior_odds_keep, csrc/vlr_callstats.hip).  Deviation: the reference trims
-// the removed alleles of a kept record (filter_calls: record.remove_alleles); like control-fdr above this writes kept records byte
-// for byte, untrimmed — the same thing for the single-ALT records `call variants` emits.  The Python restatement the tests compare
-// with: varlociraptor_amd/odds.py.
-namespace {
-// (ID, Description) of every PROB_* INFO line in header order (utils::get_event_tags, utils/mod.rs:429-446)
-std::vector<std::pair<std::string, std::string>> event_tags_of(const std::string& text) {
-    std::vector<std::pair<std::string, std::string>> out;
-    size_t p = 0;
-    while (p < text.size()) {
-        size_t e = text.find('\n', p);
-        if (e == std::string::npos) e = text.size();
-        const std::string line = text.substr(p, e - p);
-        p = e + 1;
-        if (line.compare(0, 8, "##INFO=<") != 0) continue;
-        const std::string id = attr(line.substr(7), "ID");
-        if (id.compare(0, 5, "PROB_") != 0) continue;
-        std::string desc;
-        const size_t d = line.find("Description=");
-        if (d != std::string::npos) {
-            size_t b = d + 12, q = line.rfind('>');
-            if (q == std::string::npos || q < b) q = line.size();
-            desc = line.substr(b, q - b);
-            if (!desc.empty() && desc[0] == '"') {  // quoted: up to the closing quote
-                const size_t c = desc.find('"', 1);
-                desc = desc.substr(1, c == std::string::npos ? std::string::npos : c - 1);
-            } else {
-                const size_t c = desc.find(',');
-                if (c != std::string::npos) desc.resize(c);
-            }
-        }
-        out.emplace_back(id, desc);
-    }
-    return out;
-}
-bool ends_with(const std::string& s, const char* suffix) {
-    const size_t n = strlen(suffix);
-    return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
-}
-std::string event_tag(const char* event) {  // Event::tag_name("PROB") (lib.rs:52-54)
-    std::string t = "PROB_";
-    for (const char* q = event; *q; ++q) t.push_back((char)toupper((unsigned char)*q));
-    return t;
-}
-}  // namespace
-
-extern "C" int vlr_calls_filter_odds(const char* in_path, const char* out_path, int n_events, const char* const* events, int min_level, int device, int n_threads,
-                                     int64_t* n_kept, int64_t* n_total) {
-    if (!in_path || !out_path || n_events <= 0 || !events) return ifail(VLR_ERR_INVALID_ARGUMENT, "null argument");
-    if (min_level < VLR_ODDS_NONE || min_level > VLR_ODDS_VERY_STRONG) return ifail(VLR_ERR_INVALID_ARGUMENT, "min_level %d outside [0, 4]", min_level);
-    n_threads = pick_threads(n_threads);
-    CallsFile cf;
-    if (int rc = open_calls(in_path, n_threads, cf)) return rc;
-    const auto etags = event_tags_of(cf.h.text);
-    for (auto& t : etags)  // is_phred_scaled (a missing closing parenthesis passes, for backward compatibility)
-        if (!(ends_with(t.second, "(PHRED)") || !ends_with(t.second, ")")))
-            return ifail(VLR_ERR_INVALID_ARGUMENT, "Event probabilities are not PHRED scaled, aborting (%s: %s)", t.first.c_str(), t.second.c_str());
-    std::vector<std::string> tag_names;
-    auto tag_id = [&](const std::string& name) {
-        for (size_t i = 0; i < tag_names.size(); ++i) if (tag_names[i] == name) return (int)i;
-        tag_names.push_back(name);
-        return (int)tag_names.size() - 1;
-    };
-    std::vector<int> target_tags, other_tags;
-    for (int i = 0; i < n_events; ++i) target_tags.push_back(tag_id(event_tag(events[i])));
-    for (auto& t : etags) {
-        bool is_event = false;
-        for (int i = 0; i < n_events; ++i) is_event = is_event || t.first.compare(5, std::string::npos, events[i]) == 0;  // the name as given
-        if (!is_event) other_tags.push_back(tag_id(t.first));
-    }
-    if (int rc = read_call_records(in_path, cf, tag_names, false)) return rc;
-    const std::vector<CallRec>& recs = cf.recs;
-    const int64_t N = (int64_t)recs.size();
-    const TypeFilter all;
-    std::string err;
-    std::vector<VarType> types;
-    std::vector<double> lt, lo, st, so;
-    std::vector<uint8_t> valid;
-    std::vector<int64_t> first((size_t)N + 1, 0);
-    for (int64_t i = 0; i < N; ++i) {
-        if (!variant_types(recs[(size_t)i], types, err)) return ifail(VLR_ERR_INVALID_ARGUMENT, "%s (record %lld of %s)", err.c_str(), (long long)i, in_path);
-        tags_prob_sum(recs[(size_t)i], types, target_tags, all, st);
-        tags_prob_sum(recs[(size_t)i], types, other_tags, all, so);
-        for (size_t v = 0; v < st.size(); ++v) {
-            const bool vt = st[v] == st[v], vo = so[v] == so[v];
-            lt.push_back(vt ? st[v] : 0.0);
-            lo.push_back(vo ? so[v] : 0.0);
-            valid.push_back((uint8_t)((vt ? 1 : 0) | (vo ? 2 : 0)));
-        }
-        first[(size_t)i + 1] = (int64_t)lt.size();
-    }
-    std::vector<uint8_t> keep(lt.size(), 0);
-    if (int rc = vlr_posterior_odds_keep(device, (int64_t)lt.size(), lt.data(), lo.data(), valid.data(), min_level, keep.data())) return rc;
-    std::vector<uint8_t> header_bytes(cf.data.data(), cf.data.data() + 9 + cf.l_text);
-    std::vector<uint8_t> body;
-    int64_t kept = 0;
-    for (int64_t i = 0; i < N; ++i) {
-        bool any = false;
-        for (int64_t v = first[(size_t)i]; v < first[(size_t)i + 1]; ++v) any = any || keep[(size_t)v];
-        if (any) { body.insert(body.end(), recs[(size_t)i].raw, recs[(size_t)i].raw + recs[(size_t)i].raw_len); ++kept; }
-    }
-    if (!write_bgzf_file(out_path, {&header_bytes, &body}, n_threads, 6, err)) return ifail(VLR_ERR_INVALID_ARGUMENT, "%s", err.c_str());
-    if (n_kept) *n_kept = kept;
-    if (n_total) *n_total = N;
-    return VLR_OK;
-}
-
-// ================================================================================================ estimate mutational-burden
-// The record pass of `varlociraptor estimate mutational-burden` (reference src/estimation/mutational_burden.rs:18-43, 93-184,
-// 482-515) and its reduction on the device (vlr_range_group_lse, csrc/vlr_callstats.hip).  Scaling and output:
-// varlociraptor_amd/burden.py, which also holds the numpy restatement the tests compare with.
-namespace {
-constexpr int kNSignatures = 14;      // DEL METH INS INV DUP BND MNV Complex C>A C>G C>T T>A T>C T>G
-constexpr int64_t kUploadPiece = 1 << 16;  // entries per host-to-device copy
-bool is_coding(const std::string& ann) {  // is_valid_variant over the ','-separated ANN entries
-    size_t p = 0;
-    while (p <= ann.size()) {
-        size_t e = ann.find(',', p);
-        if (e == std::string::npos) e = ann.size();
-        bool coding = false;
-        int i = 0;
-        for (size_t q = p; q <= e; ++i) {
-            size_t b = ann.find('|', q);
-            if (b == std::string::npos || b > e) b = e;
-            if (i == 7) coding = ann.compare(q, b - q, "protein_coding") == 0;
-            if (i == 13) coding = coding && b > q;
-            q = b + 1;
-        }
-        if (coding) return true;
-        p = e + 1;
-    }
-    return false;
-}
-int signature_of(const std::string& ref, const std::string& alt) {  // signatures(); -1: an SNV that is no ACGT substitution
-    if (alt == "<DEL>") return 0;
-    if (alt == "<INV>") return 3;
-    if (alt == "<DUP>") return 4;
-    if (alt == "<BND>") return 5;
-    if (alt == "<METH>") return 1;
-    if (ref.size() == 1 && alt.size() == 1) {
-        static const char* const cls[6][2] = {{"CA", "GT"}, {"CG", "GC"}, {"CT", "GA"}, {"TA", "AT"}, {"TC", "AG"}, {"TG", "AC"}};
-        for (int c = 0; c < 6; ++c)
-            for (int k = 0; k < 2; ++k)
-                if (ref[0] == cls[c][k][0] && alt[0] == cls[c][k][1]) return 8 + c;
-        return -1;
-    }
-    if (ref.size() > 1 && alt.size() == 1) return 0;
-    if (ref.size() == 1 && alt.size() > 1) return 2;
-    if (ref.size() == alt.size() && ref.size() > 1) return 6;
-    return 7;
-}
-double ln_add_exp(double a, double b) {  // bio LogProb::ln_add_exp; NaN in, NaN out
-    if (a != a || b != b) return NAN;
-    if (b > a) std::swap(a, b);
-    if (a == -INFINITY) return a;
-    return a + std::log1p(std::exp(b - a));
-}
-}  // namespace
-
-extern "C" int vlr_calls_mutational_burden(const char* in_path, int n_events, const char* const* events, int n_samples, const char* const* samples, int by_sample,
-                                           int n_ranges, const double* lo, const double* hi, int device, int n_threads, double* out_cells, int64_t* n_entries) {
-    if (!in_path || n_events <= 0 || !events || n_samples <= 0 || !samples || !lo || !hi || !out_cells) return ifail(VLR_ERR_INVALID_ARGUMENT, "null argument");
-    if (n_samples > VLR_MAX_SAMPLES) return ifail(VLR_ERR_INVALID_ARGUMENT, "%d samples: at most %d", n_samples, VLR_MAX_SAMPLES);
-    n_threads = pick_threads(n_threads);
-    CallsFile cf;
-    if (int rc = open_calls(in_path, n_threads, cf)) return rc;
-    std::vector<int> sample_col;
-    for (int s = 0; s < n_samples; ++s) {
-        const auto it = std::find(cf.samples.begin(), cf.samples.end(), std::string(samples[s]));
-        if (it == cf.samples.end()) return ifail(VLR_ERR_INVALID_ARGUMENT, "Sample %s not found", samples[s]);
-        sample_col.push_back((int)(it - cf.samples.begin()));
-    }
-    std::vector<int> by_name((size_t)n_samples);  // the reference pushes a record's entries in sample-name order (a BTreeMap's keys, :103-111, :160)
-    for (int s = 0; s < n_samples; ++s) by_name[(size_t)s] = s;
-    std::stable_sort(by_name.begin(), by_name.end(), [&](int a, int b) { return strcmp(samples[a], samples[b]) < 0; });
-    std::vector<std::string> tag_names;
-    for (int i = 0; i < n_events; ++i) tag_names.push_back(event_tag(events[i]));
-    if (int rc = read_call_records(in_path, cf, tag_names, true)) return rc;
-    std::vector<double> vaf, lnp, probs;
-    std::vector<int32_t> grp;
-    std::vector<int> sig;
-    for (size_t i = 0; i < cf.recs.size(); ++i) {
-        const CallRec& r = cf.recs[i];
-        const std::string contig = (r.contig >= 0 && (size_t)r.contig < cf.h.contigs.size()) ? cf.h.contigs[(size_t)r.contig] : std::string("?");
-        if (!r.has_af) return ifail(VLR_ERR_INVALID_ARGUMENT, "record %s:%lld of %s has no FORMAT/AF", contig.c_str(), (long long)r.pos0 + 1, in_path);
-        if (!r.has_ann || !is_coding(r.ann)) continue;
-        const size_t n_alt = r.alts.size();
-        probs.assign(n_alt, -INFINITY);
-        bool skip = false;
-        for (size_t t = 0; t < tag_names.size() && !skip; ++t) {
-            const std::vector<double>& v = r.prob[t];
-            if (v.empty()) { skip = true; break; }
-            if (v.size() < n_alt) return ifail(VLR_ERR_INVALID_ARGUMENT, "record %s:%lld of %s: %s has %zu values for %zu ALT alleles", contig.c_str(), (long long)r.pos0 + 1,
-                                               in_path, tag_names[t].c_str(), v.size(), n_alt);
-            for (size_t a = 0; a < n_alt; ++a) probs[a] = ln_add_exp(probs[a], v[a] != v[a] ? NAN : -v[a] * std::log(10.0) / 10.0);
-        }
-        if (skip) continue;
-        sig.resize(n_alt);
-        for (size_t a = 0; a < n_alt; ++a) {
-            sig[a] = signature_of(r.ref, r.alts[a]);
-            if (sig[a] < 0) return ifail(VLR_ERR_INVALID_ARGUMENT, "record %s:%lld of %s: %s>%s is not a substitution between A, C, G and T", contig.c_str(),
-                                         (long long)r.pos0 + 1, in_path, r.ref.c_str(), r.alts[a].c_str());
-        }
-        for (int s : by_name) {
-            const std::vector<float>& af = r.af[(size_t)sample_col[(size_t)s]];
-            for (size_t a = 0; a < n_alt && a < af.size(); ++a) {
-                if (af[a] != af[a]) continue;
-                vaf.push_back((double)af[a]);
-                lnp.push_back(probs[a]);
-                grp.push_back((by_sample ? s * kNSignatures : 0) + sig[a]);
-            }
-        }
-    }
-    if (n_entries) *n_entries = (int64_t)vaf.size();
-    if (vaf.empty()) return ifail(VLR_ERR_INVALID_ARGUMENT, "unable to estimate TMB because no valid records were found in the given BCF/VCF");  // errors::Error::NoRecordsFound
-    return vlr_launch_range_group_lse(device, (int64_t)vaf.size(), vaf.data(), lnp.data(), grp.data(), n_ranges, lo, hi, (by_sample ? n_samples : 1) * kNSignatures,
-                                      kUploadPiece, out_cells);
-}

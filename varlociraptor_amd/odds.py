@@ -4,7 +4,7 @@ An allele is kept while the evidence AGAINST the chosen events — the Bayes fac
 chosen ones, on the Kass-Raftery scale — stays below `--odds`.  Both probabilities are ln-sums over
 PROB_* INFO tags as utils::tags_prob_sum forms them (restated in fdr.py).  The per-allele decision has a HIP kernel behind the C
 ABI (`vlr_posterior_odds_keep`, csrc/vlr_callstats.hip) and the whole command runs in the engine (`vlr_calls_filter_odds`,
-csrc/vlr_ingest.cpp); next to them is the host restatement (`device="cpu"`) that the CPU suite and the comparisons use.
+csrc/vlr_callsfile.cpp); next to them is the host restatement (`device="cpu"`) that the CPU suite and the comparisons use.
 
 Deviation: the reference trims the removed alleles of a kept record; here a kept record passes through untrimmed, which is the
 same thing for the single-ALT records `call variants` writes.  Not checkable here: the reference's spelling of the `--odds`
