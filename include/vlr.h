@@ -48,7 +48,8 @@ extern "C" {
                              * 13: vlr_fragpileup_* (fragment observations of SNV / MNV candidates from BAM records);
                              * 14: vlr_fragpileup_open_realign / _realign_result / _read_realigned (indel-bearing reads over SNV / MNV
                              *     candidates realigned inside the fragment session); still 14, purely additive: vlr_fragpileup_open_indel /
-                             *     _read_indel (fragments of deletion / insertion candidates in the fragment session) */
+                             *     _read_indel (fragments of deletion / insertion candidates in the fragment session) and
+                             *     vlr_fragpileup_open_methylation / vlr_methylation_tables (fragments of <METH> candidates) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -853,6 +854,22 @@ int  vlr_fragpileup_open_indel(int device, int64_t n_loci, const int32_t* ref_id
                                int realign_window, int mode, const double gap[4], const double* hop, int64_t evidence_capacity,
                                int64_t pair_byte_limit, int has_insert_size, vlr_fragpileup** out);
 int  vlr_fragpileup_read_indel(vlr_fragpileup* s, vlr_fragpileup_indel_obs* extra_obs, int64_t n_obs, vlr_fragpileup_indel_locus* extra_loci, int64_t n_loci);
+/* Methylation candidates (ALT <METH>) in the fragment session (variants/types/methylation.rs; the rule is stated once, at the head of
+ *   csrc/vlr_methylation.h).  vlr_fragpileup_open_methylation takes the arguments of vlr_fragpileup_open with the loci as (ref_id, start)
+ *   only — the locus is [start, start + 1), the C of a CpG — and readtype: VLR_METH_CONVERTED (bisulfite / EM-seq reads: C / T forward,
+ *   G / A reverse, scored with the tables of the SNV arm) or VLR_METH_ANNOTATED (reads with MM / ML tags: the 5mC map of the record, scored
+ *   with vlr_methylation_tables).  A record of reverse orientation (unpaired: the reverse flag; paired: (reverse && first) || (!reverse &&
+ *   !first)) is read at start + 1 and encloses the locus when pos <= start + 1 && end_pos >= start + 1; only records whose FLAG is one of
+ *   0, 16, 83, 99, 147, 163 give support.  The read position of an observation is the position in SEQ, without a leading hard clip;
+ *   third_allele is 0.  vlr_fragpileup_add_bam, _result, _read and _close work on such a session as on any other; the overflow statuses and
+ *   the guard words are those of every session.  A record of any length is one thread's work (csrc/vlr_methylation.h says what it costs).
+ *   NOT mirrored: max_depth subsampling, report_fragment_ids.
+ * vlr_methylation_tables: ln((ml + 0.5) / 256) and ln(1 - exp of it) for ml = 0 .. 255, as the session scores with them. */
+enum { VLR_METH_CONVERTED = 0, VLR_METH_ANNOTATED = 1 };
+int  vlr_fragpileup_open_methylation(int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, int readtype, int64_t window, int max_mapq,
+                                     int max_read_len, int64_t member_capacity, int64_t name_capacity, int64_t key_capacity, int64_t window_bytes,
+                                     vlr_fragpileup** out);
+int  vlr_methylation_tables(double ln_meth[256], double ln_unmeth[256]);
 
 /* The whole of `varlociraptor filter-calls control-fdr` (/root/reference/src/filtration/fdr.rs:36-158, record typing
  * src/utils/collect_variants.rs:44-304, probability sums and the filtering pass src/utils/mod.rs:169-374): read the calls BCF

@@ -242,6 +242,8 @@ FRAGPILEUP_INDEL_NONPOSITIVE_ISIZE = 1
 FRAGPILEUP_INDEL_OBS_DTYPE = np.dtype([("insert_size", "<i8"), ("len_left", "<u4"), ("len_right", "<u4"), ("flags", "<u4"), ("pad", "<u4")])
 FRAGPILEUP_INDEL_LOCUS_DTYPE = np.dtype([("max_del", "<u4"), ("max_ins", "<u4"), ("max_clip", "<u4"), ("max_clip_l_seq", "<u4")])
 assert FRAGPILEUP_INDEL_OBS_DTYPE.itemsize == 24 and FRAGPILEUP_INDEL_LOCUS_DTYPE.itemsize == 16
+# vlr_fragpileup_open_methylation (<METH> candidates in the fragment session; additive, ABI stays 14)
+METH_CONVERTED, METH_ANNOTATED = 0, 1
 
 
 class RealignDesc(C.Structure):
@@ -346,6 +348,9 @@ SIGNATURES = {
     "vlr_fragpileup_open_indel": (C.c_int, [C.c_int, C.c_int64] + [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_char_p, C.c_int,
                                             C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "vlr_fragpileup_read_indel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "vlr_fragpileup_open_methylation": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                  C.POINTER(C.c_void_p)]),
+    "vlr_methylation_tables": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # ---- consumers of a calls file: filter-calls control-fdr / posterior-odds, estimate mutational-burden
     "vlr_calls_filter_fdr": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_double, C.c_uint32, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

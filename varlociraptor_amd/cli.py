@@ -182,6 +182,9 @@ def main(argv=None):
     pv.add_argument("--indel-candidates", action="store_true",
                     help="build deletion and insertion candidates too, one observation per fragment with the insert-size support of a deletion "
                     "(without it such a candidate is an error)")
+    pv.add_argument("--methylation-read-type", choices=["converted", "annotated"],
+                    help="build methylation candidates (ALT <METH>) too: 'converted' for bisulfite / EM-seq reads, 'annotated' for reads with "
+                    "MM / ML tags (cli.rs:367-371; without it such a candidate is an error)")
     pv.add_argument("--indel-window", type=int, default=64, help="bases of a read realigned on either side of the candidate (at most 64, cli.rs:877)")
     pv.add_argument("--pairhmm-mode", choices=["exact", "fast", "homopolymer"], default="exact")
     pv.add_argument("--device", default="0", help="HIP device index, or 'cpu' for the Python restatement")
@@ -199,7 +202,8 @@ def main(argv=None):
                                               a.atomic_candidate_variants, a.omit_mapq_adjustment, a.max_depth, a.score_indel_reads_from_alignment,
                                               warn=lambda m: print(f"[WARN] {m}", file=sys.stderr),
                                               realign=fragments.RealignSpec(a.indel_window, a.pairhmm_mode) if a.realign_indel_reads else None,
-                                              indel_candidates=fragments.RealignSpec(a.indel_window, a.pairhmm_mode) if a.indel_candidates else None)
+                                              indel_candidates=fragments.RealignSpec(a.indel_window, a.pairhmm_mode) if a.indel_candidates else None,
+                                              methylation_readtype=a.methylation_read_type)
         except (fragments.PreprocessError, fragments.FragPileupError, fragments.InvalidReadOrientationInfo, fragments.EngineError) as e:
             print(f"error: {e}", file=sys.stderr)
             sys.exit(1)

@@ -54,7 +54,10 @@
 //                            NOT mirrored: the read-inferred third allele, alt_variants, homopolymer_indel_len and the two
 //                            prob_observable_at_homopolymer_* fields (the Myers traceback of the bio crate), max_depth subsampling,
 //                            report_fragment_ids, replacements, SVs, breakends, deletions with more than one fetch.
-// varlociraptor_amd/fragments.py is the same in Python.
+//   methylation candidates   (a methylation session, vlr_fragpileup_open_methylation) variants/types/methylation.rs: vlr_methylation.h, included at
+//                            the end of this file, has the rule, what of it is not mirrored, and its own member pass (record_members_meth);
+//                            the fragment pass below runs on its members as it is.
+// varlociraptor_amd/fragments.py is the same in Python (methylation.py for the methylation rule).
 //
 // Bounds: `features` runs only on a record vlr_bp::decode accepted, so the fixed head, the name (l_read_name bytes behind the head) and
 // every aux field lie inside [p, p + size); it walks the aux fields again with the same length checks and reads RO and XA values byte
@@ -719,5 +722,7 @@ VLR_BP_HD inline uint32_t major_of_sorted(const uint32_t* v, uint32_t n, bool* f
 }
 
 }  // namespace vlr_fp
+
+#include "vlr_methylation.h"   // methylation candidates (a methylation session, vlr_fragpileup_open_methylation): the rule and its member pass
 
 #endif

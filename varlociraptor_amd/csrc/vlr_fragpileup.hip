@@ -45,6 +45,11 @@
 // rule of the locus's kind (vlr_fp::make_obs_indel) and carry a vlr_fragpileup_indel_obs beside each observation.  The arrays are
 // allocated by such a session alone; the other kernels keep the signatures every session had before (the bodies are shared templates).
 //
+// A methylation session (vlr_fragpileup_open_methylation; the rule: vlr_methylation.h) has a count and a fill kernel of its own
+// (frag_count_meth_kernel, frag_fill_meth_kernel) over vlr_fp::record_members_meth: one record per thread whatever its length, the same
+// three count arrays, the same places; nothing of it is compiled into the kernels of the other sessions.  Its members go through the
+// fragment pass above unchanged (frag_locus_kernel, frag_gather_kernel): no new LDS, no atomic that decides a place.
+//
 // LDS of frag_locus_kernel: 4 B index + 2 B rank per member + 2 KiB of scan cells = 26 KiB at VLR_FRAGPILEUP_MAX_MEMBERS = 4096, six
 // workgroups per CU by LDS.
 // Bounds: a record is read only after vlr_bp::decode checked it; members[k] is written for k < member capacity, names[k] for
@@ -272,6 +277,47 @@ __global__ __launch_bounds__(kThreads) void frag_fill_indel_kernel(const uint8_t
                                                                    IndelFill in) {
     frag_fill_body<true, true>(base, starts, n, rec0, t, L, realign, window, coeff, cnt, nbytes, off, noff, xoff, member0, member_cap, name0, name_cap, key0, key_cap,
                                members, names, keys, locus_cnt, ev, in);
+}
+
+// The member pass of a methylation session: the count and the fill of frag_count_body / frag_fill_body without evidences, over
+// record_members_meth.  The same bounds: members[k] for k < member_cap, names below name_cap, keys below key_cap.
+__global__ __launch_bounds__(kThreads) void frag_count_meth_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
+                                                                   vlr_bp::Tables t, vlr_bp::Loci L, Meth me, int64_t window, uint64_t coeff, uint32_t* __restrict__ cnt,
+                                                                   uint32_t* __restrict__ nbytes, uint32_t* __restrict__ nxa, unsigned long long* __restrict__ counters) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t o = starts[i], end = starts[i + 1];
+    const RecMembers r = record_members_meth(t, L, me, base + o, end - o, rec0 + (uint64_t)i, window, coeff, nullptr, 0, 0, nullptr, 0, nullptr, 0);
+    cnt[i] = r.n_members;
+    nbytes[i] = r.name_bytes;
+    nxa[i] = r.n_xa;
+    if (r.cls == vlr_bp::REC_REJECTED) atomicAdd(&counters[C_REJECTED], 1ull);
+    if (r.cls == vlr_bp::REC_BAD) { atomicAdd(&counters[C_BAD], 1ull); atomicMin(&counters[C_FIRST_BAD], (unsigned long long)(rec0 + (uint64_t)i)); }
+}
+
+__global__ __launch_bounds__(kThreads) void frag_fill_meth_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
+                                                                  vlr_bp::Tables t, vlr_bp::Loci L, Meth me, int64_t window, uint64_t coeff, const uint32_t* __restrict__ cnt,
+                                                                  const uint32_t* __restrict__ nbytes, const uint64_t* __restrict__ off, const uint64_t* __restrict__ noff,
+                                                                  const uint64_t* __restrict__ xoff, uint64_t member0, uint64_t member_cap, uint64_t name0, uint64_t name_cap,
+                                                                  uint64_t key0, uint64_t key_cap, Member* __restrict__ members, uint8_t* __restrict__ names,
+                                                                  AltKey* __restrict__ keys, uint32_t* __restrict__ locus_cnt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || cnt[i] == 0) return;
+    const uint64_t first = member0 + off[i];
+    if (first >= member_cap) return;
+    const uint64_t room = member_cap - first;
+    const uint64_t name_at = name0 + noff[i];
+    uint8_t* name_dst = name_at + (uint64_t)nbytes[i] <= name_cap ? names + name_at : nullptr;
+    const uint64_t key_at = key0 + xoff[i];
+    const uint64_t key_room = key_at < key_cap ? key_cap - key_at : 0;
+    const uint64_t o = starts[i], end = starts[i + 1];
+    const RecMembers r = record_members_meth(t, L, me, base + o, end - o, rec0 + (uint64_t)i, window, coeff, members + first, room, name_at, name_dst, key_at,
+                                             key_room ? keys + key_at : nullptr, key_room);
+    const uint64_t written = std::min<uint64_t>(r.n_members, room);
+    for (uint64_t k = 0; k < written; ++k) {
+        const uint32_t li = members[first + k].locus;
+        if ((int64_t)li < L.n) atomicAdd(&locus_cnt[li], 1u);
+    }
 }
 
 __global__ __launch_bounds__(kThreads) void frag_scatter_kernel(const Member* __restrict__ members, uint64_t n_members, int64_t n_loci, const uint64_t* __restrict__ locus_off,
@@ -558,6 +604,10 @@ struct vlr_fragpileup : vlr_bam::Session {
     uint32_t *d_max_del = nullptr, *d_max_ins = nullptr; unsigned long long* d_max_clip = nullptr;   // [n_loci]
     std::vector<vlr_fragpileup_indel_obs> obsx;      // parallel to obs
     std::vector<vlr_fragpileup_indel_locus> locusx;  // [n_loci]
+    // a methylation session (vlr_fragpileup_open_methylation)
+    bool meth = false;
+    vlr_fp::Meth me{0, {nullptr, nullptr}};
+    double* d_meth_tables = nullptr;                 // ln_meth[256], ln_unmeth[256]
     vlr_fp::IndelFill indel_fill() const { return vlr_fp::IndelFill{indel, max_locus_len, member_cap, d_sides, d_max_del, d_max_ins, d_max_clip}; }
 };
 
@@ -587,7 +637,10 @@ int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
     const uint64_t rec0 = s->n_records;
     const size_t stride = s->rec_cap;
     uint32_t *d_cnt = (uint32_t*)s->d_cnt, *d_nbytes = d_cnt + K_NAME * stride, *d_nxa = d_cnt + K_XA * stride;
-    if (s->indel)
+    if (s->meth)
+        hipLaunchKernelGGL(frag_count_meth_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->me, s->win, s->coeff, d_cnt, d_nbytes,
+                           d_nxa, s->d_counters);
+    else if (s->indel)
         hipLaunchKernelGGL(frag_count_indel_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff,
                            d_cnt, d_nbytes, d_nxa, s->d_counters, s->ra(), d_cnt + K_EV * stride, d_cnt + K_X * stride, d_cnt + K_Y * stride, s->max_locus_len);
     else if (s->realigning)
@@ -613,7 +666,11 @@ int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
         ev.hits = s->d_ev; ev.member = s->d_evm; ev.gx = s->d_gx; ev.gy = s->d_gy; ev.src = s->d_src;
     }
     if (total[K_MEMBERS] && fits && s->n_members < s->member_cap) {
-        if (s->indel)
+        if (s->meth)
+            hipLaunchKernelGGL(frag_fill_meth_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->me, s->win, s->coeff, d_cnt, d_nbytes,
+                               s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys, s->key_cap,
+                               s->d_members, s->d_names, s->d_keys, s->d_lcnt);
+        else if (s->indel)
             hipLaunchKernelGGL(frag_fill_indel_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt,
                                d_nbytes, s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys,
                                s->key_cap, s->d_members, s->d_names, s->d_keys, s->d_lcnt, ev, s->indel_fill());
@@ -835,7 +892,7 @@ int check_indel_loci(const char* api, int64_t n_loci, const int32_t* ref_id, con
 
 int open_impl(const char* api, int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, const int32_t* len, const uint8_t* kind, const uint8_t* ref_bases,
               const uint8_t* alt_bases, int realign_indel_reads, int64_t window, int max_mapq, int max_read_len, int64_t member_capacity, int64_t name_capacity,
-              int64_t key_capacity, int64_t window_bytes, const RealignOpen* ro, vlr_fragpileup** out, const IndelOpen* io = nullptr) {
+              int64_t key_capacity, int64_t window_bytes, const RealignOpen* ro, vlr_fragpileup** out, const IndelOpen* io = nullptr, int meth_readtype = -1) {
     if (!out || n_loci < 0 || n_loci > 0x7fffffff || member_capacity < 0 || member_capacity > 0x7fffffff || name_capacity < 0 || key_capacity < 0 || key_capacity > 0x7fffffff ||
         window_bytes < 0 || window < 0 ||
         window > ((int64_t)1 << 40) || max_mapq < 0 || max_mapq > 255 || (n_loci > 0 && (!ref_id || !start || !len || !kind || !ref_bases || !alt_bases)))
@@ -905,6 +962,15 @@ int open_impl(const char* api, int device, int64_t n_loci, const int32_t* ref_id
     step(buf.guarded(s->d_members, (size_t)s->member_cap));
     step(buf.guarded(s->d_names, (size_t)s->name_cap));
     step(buf.guarded(s->d_keys, (size_t)s->key_cap));
+    if (meth_readtype >= 0) {   // a methylation session: the two tables of annotated reads, filled here with libm
+        s->meth = true;
+        std::vector<double> tab(512);
+        fill_meth_tables(tab.data(), tab.data() + 256);
+        step(buf.guarded(s->d_meth_tables, 512));
+        if (rc == VLR_OK && hipMemcpy(s->d_meth_tables, tab.data(), 512 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+            rc = bfail(VLR_ERR_HIP, "%s: hipMemcpy of the methylation tables failed", api);
+        s->me = Meth{meth_readtype == VLR_METH_ANNOTATED ? 1 : 0, MethTables{s->d_meth_tables, s->d_meth_tables + 256}};
+    }
     if (rc != VLR_OK) { vlr_fragpileup_close(s); return rc; }
     *out = s;
     return VLR_OK;
@@ -1052,6 +1118,26 @@ int vlr_fragpileup_read_indel(vlr_fragpileup* s, vlr_fragpileup_indel_obs* extra
         return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_read_indel: sizes differ from vlr_fragpileup_result and the loci given at open");
     if (n_obs) memcpy(extra_obs, s->obsx.data(), (size_t)n_obs * sizeof(vlr_fragpileup_indel_obs));
     if (n_loci) memcpy(extra_loci, s->locusx.data(), (size_t)n_loci * sizeof(vlr_fragpileup_indel_locus));
+    return VLR_OK;
+}
+
+int vlr_fragpileup_open_methylation(int device, int64_t n_loci, const int32_t* ref_id, const int64_t* start, int readtype, int64_t window, int max_mapq,
+                                    int max_read_len, int64_t member_capacity, int64_t name_capacity, int64_t key_capacity, int64_t window_bytes,
+                                    vlr_fragpileup** out) {
+    using namespace vlr_fp;
+    if (n_loci < 0 || n_loci > 0x7fffffff || (n_loci > 0 && (!ref_id || !start)) || (readtype != VLR_METH_CONVERTED && readtype != VLR_METH_ANNOTATED))
+        return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_open_methylation: bad argument (readtype: VLR_METH_CONVERTED or VLR_METH_ANNOTATED)");
+    // the loci as the session's tables hold them: one base each; kind and the allele bytes are never read by the methylation kernels
+    const size_t nl = (size_t)n_loci;
+    const std::vector<int32_t> len(nl, 1);
+    const std::vector<uint8_t> kind(nl, (uint8_t)VLR_BASEPILEUP_SNV), bases(nl ? nl : 1, (uint8_t)'N');
+    return open_impl("vlr_fragpileup_open_methylation", device, n_loci, ref_id, start, len.data(), kind.data(), bases.data(), bases.data(), 0, window, max_mapq, max_read_len,
+                     member_capacity, name_capacity, key_capacity, window_bytes, nullptr, out, nullptr, readtype);
+}
+
+int vlr_methylation_tables(double ln_meth[256], double ln_unmeth[256]) {
+    if (!ln_meth || !ln_unmeth) return vlr_bam::bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_methylation_tables: null");
+    vlr_fp::fill_meth_tables(ln_meth, ln_unmeth);
     return VLR_OK;
 }
 

@@ -1,8 +1,10 @@
 // vlr_fragpileup_host.cpp — the text of vlr_fragpileup.h compiled for the CPU: what the kernels of vlr_fragpileup.hip run, as a small program
 // that tests/test_fragpileup_host.py, tests/test_fragrealign_host_program.py and tests/test_fragment_indel_host.py build with
 // -fsanitize=address,undefined and run over hand cases, fixtures and truncated and corrupted records.  Not part of libvlr.so.  The magic
-// of <input> tells the session: "VFPH" SNV / MNV candidates, "VFIH" deletions / insertions.  Both run the same passes below; the indel
-// arms (vlr_fp::Indel, vlr_fp::run_obs_indel, the Side records, the per-locus CIGAR maxima) are the points where they differ.
+// of <input> tells the session: "VFPH" SNV / MNV candidates, "VFIH" deletions / insertions, "VFMH" methylation candidates
+// (tests/test_methylation_host.py).  All run the same passes below; the indel arms (vlr_fp::Indel, vlr_fp::run_obs_indel, the Side
+// records, the per-locus CIGAR maxima) and the member pass of a methylation session (vlr_fp::record_members_meth) are the points where
+// they differ.
 //
 //   vlr_fragpileup_host <input> <output>
 // input  (little endian): "VFPH", i32 realign_indel_reads, i64 window, i32 max_mapq, i32 max_read_len, i64 n_loci, i32 ref_id[n], i64 start[n], i32 len[n],
@@ -28,6 +30,12 @@
 //        i64 n_scores, f64 (ln_ref, ln_alt)[n_scores], the records one behind the other
 // output: i64 n_obs, vlr_fragpileup_obs[n_obs] locus-major, vlr_fragpileup_indel_obs[n_obs], vlr_fragpileup_locus[n_loci],
 //        vlr_fragpileup_indel_locus[n_loci], then what the realign output holds
+//
+//   vlr_fragpileup_host <input> <output>
+// the methylation session (vlr_fragpileup_open_methylation): the member pass of vlr_methylation.h, the fragment pass of every session.
+// input:  "VFMH", i32 readtype (VLR_METH_*), i64 window, i32 max_mapq, i32 max_read_len, i64 n_loci, i32 ref_id[n], i64 start[n], i64 n_records,
+//        u64 starts[n_records + 1], the records one behind the other
+// output: f64 call[256], f64 miscall[256], f64 ln_meth[256], f64 ln_unmeth[256], then as for "VFPH" from n_obs on
 //
 // Every record, every contig, the members, the Side records, the name pool, the alt-locus key pool, the evidences and every gathered
 // window lie in heap blocks of exactly their size, so that a read or write past one is a sanitizer report.  The members of a locus are
@@ -87,6 +95,9 @@ template <class T> T* exact(size_t n) { return (T*)malloc(n ? n * sizeof(T) : 1)
 // a session's input and what its passes build
 struct Run {
     bool indel = false;                     // "VFIH"
+    bool meth = false;                      // "VFMH"
+    vlr_fp::Meth me{0, {nullptr, nullptr}};
+    std::vector<double> mtab = std::vector<double>(2 * 256);
     bool realigning = false;                // the count and the fill pass get `ra`; an indel session always
     bool realign = true, has_isize = false; // realign_indel_reads, has_insert_size
     int64_t window = 0, max_locus_len = 1, n_loci = 0, n_rec = 0;
@@ -185,6 +196,35 @@ int read_snv(In& in, const uint8_t* magic, const char* realign_path, Run& r) {
     return read_starts(in, r) ? 0 : 2;
 }
 
+int read_meth(In& in, Run& r) {
+    r.meth = true;
+    r.realign = false;
+    const int32_t readtype = in.one<int32_t>();
+    r.window = in.one<int64_t>();
+    r.max_mapq = in.one<int32_t>();
+    r.max_read_len = in.one<int32_t>();
+    r.n_loci = in.one<int64_t>();
+    if (!in.ok || (readtype != VLR_METH_CONVERTED && readtype != VLR_METH_ANNOTATED) || r.n_loci < 0 || r.n_loci > (1 << 24) || r.window < 0 || r.max_read_len <= 0) return 2;
+    const size_t nl = (size_t)r.n_loci;
+    r.ref_id = in.arr<int32_t>(nl);
+    r.start = in.arr<int64_t>(nl);
+    if (!in.ok) return 2;
+    for (size_t k = 0; k < nl; ++k) {   // (what vlr_fragpileup_open_methylation checks)
+        if (r.ref_id[k] < 0 || r.start[k] < 0) return 2;
+        if (k > 0 && (r.ref_id[k] < r.ref_id[k - 1] || (r.ref_id[k] == r.ref_id[k - 1] && r.start[k] < r.start[k - 1]))) return 2;
+    }
+    // the loci as the session's tables hold them: one base each; kind and the allele bytes are never read
+    r.len.assign(nl, 1);
+    r.kind.assign(nl, (uint8_t)VLR_BASEPILEUP_SNV);
+    r.base_off.resize(nl + 1);
+    for (size_t k = 0; k <= nl; ++k) r.base_off[k] = k;
+    r.refb.assign(nl, (uint8_t)'N');
+    r.altb.assign(nl, (uint8_t)'N');
+    vlr_fp::fill_meth_tables(r.mtab.data(), r.mtab.data() + 256);
+    r.me = vlr_fp::Meth{readtype == VLR_METH_ANNOTATED ? 1 : 0, vlr_fp::MethTables{r.mtab.data(), r.mtab.data() + 256}};
+    return read_starts(in, r) ? 0 : 2;
+}
+
 int read_indel(In& in, Run& r) {
     r.indel = true;
     r.window = in.one<int64_t>();
@@ -241,6 +281,14 @@ void gather_windows(Run& r, const vlr_bp::Loci& L, const vlr_indelpileup_hit& h,
     free(xr); free(xa); free(yb_); free(yq);
 }
 
+// the members of one record: the member pass of the session's kind
+vlr_fp::RecMembers members_of(const Run& r, const vlr_bp::Tables& T, const vlr_bp::Loci& L, const uint8_t* rec, size_t size, uint64_t ordinal, uint64_t coeff,
+                              vlr_fp::Member* out, uint64_t room, uint64_t name_off, uint8_t* name_dst, uint64_t xa_off, vlr_fp::AltKey* xa_dst, uint64_t xa_room,
+                              const vlr_fp::Realign* rap, vlr_indelpileup_hit* ev_out, uint64_t ev_room, const vlr_fp::Indel* arm) {
+    if (r.meth) return vlr_fp::record_members_meth(T, L, r.me, rec, size, ordinal, r.window, coeff, out, room, name_off, name_dst, xa_off, xa_dst, xa_room);
+    return vlr_fp::record_members(T, L, rec, size, ordinal, r.realign, r.window, coeff, out, room, name_off, name_dst, xa_off, xa_dst, xa_room, rap, ev_out, ev_room, arm);
+}
+
 // member pass: count, then fill into exactly what was counted; the evidences of the members scored and applied
 int member_pass(const In& in, size_t blob, Run& r, const vlr_bp::Tables& T, const vlr_bp::Loci& L) {
     const size_t n_rec = (size_t)r.n_rec;
@@ -257,8 +305,7 @@ int member_pass(const In& in, size_t blob, Run& r, const vlr_bp::Tables& T, cons
         sizes[i] = (size_t)(r.starts[i + 1] - r.starts[i]);
         recs[i] = exact<uint8_t>(sizes[i]);   // exactly the record
         if (sizes[i]) memcpy(recs[i], in.d.data() + blob + r.starts[i], sizes[i]);
-        cnt[i] = vlr_fp::record_members(T, L, recs[i], sizes[i], (uint64_t)i, r.realign, r.window, coeff, nullptr, 0, 0, nullptr, 0, nullptr, 0, rap, nullptr, 0,
-                                        r.indel ? &count_arm : nullptr);
+        cnt[i] = members_of(r, T, L, recs[i], sizes[i], (uint64_t)i, coeff, nullptr, 0, 0, nullptr, 0, nullptr, 0, rap, nullptr, 0, r.indel ? &count_arm : nullptr);
         r.cls[i] = (uint8_t)cnt[i].cls;
         r.n_ev += cnt[i].n_ev;
         r.n_members += cnt[i].n_members;
@@ -277,8 +324,8 @@ int member_pass(const In& in, size_t blob, Run& r, const vlr_bp::Tables& T, cons
         const vlr_fp::RecMembers c = cnt[i];
         if (c.n_members) {
             const vlr_fp::Indel arm{r.max_locus_len, r.indel ? r.sides + m_at : nullptr};
-            const vlr_fp::RecMembers w = vlr_fp::record_members(T, L, recs[i], sizes[i], (uint64_t)i, r.realign, r.window, coeff, r.members + m_at, c.n_members, (uint64_t)n_at,
-                                                                 r.names + n_at, (uint64_t)k_at, r.keys + k_at, c.n_xa, rap, r.ev + e_at, c.n_ev, r.indel ? &arm : nullptr);
+            const vlr_fp::RecMembers w = members_of(r, T, L, recs[i], sizes[i], (uint64_t)i, coeff, r.members + m_at, c.n_members, (uint64_t)n_at, r.names + n_at,
+                                                     (uint64_t)k_at, r.keys + k_at, c.n_xa, rap, r.ev + e_at, c.n_ev, r.indel ? &arm : nullptr);
             if (w.n_members != c.n_members || w.name_bytes != c.name_bytes || w.n_xa != c.n_xa || w.n_ev != c.n_ev || w.x_bytes != c.x_bytes || w.y_bytes != c.y_bytes ||
                 (r.indel && (w.n_ev != w.n_members || w.max_del != c.max_del || w.max_ins != c.max_ins || w.max_clip != c.max_clip))) {
                 fprintf(stderr, "count and fill pass differ at record %lld\n", (long long)i);
@@ -394,9 +441,9 @@ int main(int argc, char** argv) {
     const uint8_t* magic = in.take(4);
     Run r;
     int rc;
-    if (magic && memcmp(magic, "VFIH", 4) == 0) {
+    if (magic && (memcmp(magic, "VFIH", 4) == 0 || memcmp(magic, "VFMH", 4) == 0)) {
         if (argc != 3) { fprintf(stderr, "usage: %s <input> <output>\n", argv[0]); return 2; }
-        rc = read_indel(in, r);
+        rc = magic[2] == 'I' ? read_indel(in, r) : read_meth(in, r);
     } else {
         rc = read_snv(in, magic, argc == 5 ? argv[3] : nullptr, r);
     }
@@ -424,6 +471,7 @@ int main(int argc, char** argv) {
     if (!o) { perror(argv[2]); return 2; }
     const int64_t n_obs = (int64_t)r.obs.size();
     if (!r.indel) put(o, r.tab.data(), 512);
+    if (r.meth) put(o, r.mtab.data(), 512);
     put(o, &n_obs, 1);
     put(o, r.obs.data(), r.obs.size());
     put(o, r.obsx.data(), r.obsx.size());

@@ -38,9 +38,10 @@ with the record's ordinal: a CIGAR that begins with N (read_pos fails) and a rec
 
 NOT mirrored (callers must know): `alt_variants`; without a RealignSpec the realignment (with realign_indel_reads=True such
 observations come back flagged NEEDS_REALIGN and `observations` raises), `max_depth` subsampling (the `rand` crate's StdRng),
-`report_fragment_ids` (None), replacement / SV / breakend candidates, haplotype blocks, methylation.  Deletion and insertion candidates
+`report_fragment_ids` (None), replacement / SV / breakend candidates, haplotype blocks.  Deletion and insertion candidates
 are built on request (`indel_candidates`, --indel-candidates): the section "deletion and insertion candidates" below has their rule
-and what of it is not mirrored.
+and what of it is not mirrored.  Methylation candidates (ALT <METH>) are built on request too (`methylation_readtype`,
+--methylation-read-type): methylation.py has their rule and what of it is not mirrored (max_depth subsampling, report_fragment_ids).
 `preprocess_variants` is the command `python -m varlociraptor_amd preprocess variants`; it says what it does not do as errors.
 """
 from __future__ import annotations
@@ -286,18 +287,24 @@ def _support(rec: BamRecord, loc: Locus, li: int, ordinal: int, t: Tables, reali
 
 
 def fragment_observation(left: Tuple[int, BamRecord], right: Optional[Tuple[int, BamRecord]], loc: Locus, li: int, max_mapq: int, t: Tables,
-                         realign_indel_reads: bool = False, realigned: Optional[Dict] = None) -> Optional[FragObs]:
-    """mod.rs:352-384 and evidence_to_observation for one candidate"""
+                         realign_indel_reads: bool = False, realigned: Optional[Dict] = None, rule=None) -> Optional[FragObs]:
+    """mod.rs:352-384 and evidence_to_observation for one candidate.  `rule`: the enclosing test and the per-read support of another
+    candidate kind (methylation.Rule); None = an SNV / MNV"""
     lo, lr = left
+    enc = basecalls.enclosing if rule is None else rule.enclosing
     if right is not None:
         if lr.mapq == 0 or right[1].mapq == 0:
             return None
-        if not basecalls.enclosing(lr, loc) and not basecalls.enclosing(right[1], loc):
+        if not enc(lr, loc) and not enc(right[1], loc):
             return None
-    elif not basecalls.enclosing(lr, loc):
+    elif not enc(lr, loc):
         return None
-    hl = _support(lr, loc, li, lo, t, realign_indel_reads, realigned)
-    hr = _support(right[1], loc, li, right[0], t, realign_indel_reads, realigned) if right is not None else None
+    if rule is None:
+        hl = _support(lr, loc, li, lo, t, realign_indel_reads, realigned)
+        hr = _support(right[1], loc, li, right[0], t, realign_indel_reads, realigned) if right is not None else None
+    else:
+        hl = rule.support(lr, loc, li, lo, t)
+        hr = rule.support(right[1], loc, li, right[0], t) if right is not None else None
     if hl is None and hr is None:
         return None
     h = basecalls.merge(hl, hr) if hl is not None and hr is not None else (hl if hl is not None else hr)
@@ -324,7 +331,7 @@ def fragment_observation(left: Tuple[int, BamRecord], right: Optional[Tuple[int,
 
 
 def locus_observations(members: Sequence[Tuple[int, BamRecord]], loc: Locus, li: int, max_mapq: int, t: Tables = basecalls.TABLES,
-                       realign_indel_reads: bool = False, realigned: Optional[Dict] = None) -> List[FragObs]:
+                       realign_indel_reads: bool = False, realigned: Optional[Dict] = None, rule=None) -> List[FragObs]:
     """the observations of one locus from its members (ordinal, record) in file order, in the byte order of the names"""
     cand: Dict[bytes, List] = {}
     for o, rec in members:
@@ -339,7 +346,7 @@ def locus_observations(members: Sequence[Tuple[int, BamRecord]], loc: Locus, li:
         c[1] = (o, rec)
     out = []
     for name in sorted(cand):
-        ob = fragment_observation(cand[name][0], cand[name][1], loc, li, max_mapq, t, realign_indel_reads, realigned)
+        ob = fragment_observation(cand[name][0], cand[name][1], loc, li, max_mapq, t, realign_indel_reads, realigned, rule)
         if ob is not None:
             out.append(ob)
     return out
@@ -484,9 +491,10 @@ def realign_members(good: Sequence[Tuple[int, BamRecord]], loci: Sequence[Locus]
 
 def restate(records: Sequence[BamRecord], loci: Sequence[Locus], props: Props, t: Tables = basecalls.TABLES, realign_indel_reads: bool = False,
             first_ordinal: int = 0, only: Optional[Sequence[int]] = None, realign: Optional[RealignSpec] = None, ref_seqs: Optional[Dict[int, bytes]] = None,
-            device="cpu") -> Restated:
+            device="cpu", rule=None) -> Restated:
     """The observations of every locus (`only`: of these loci) from `records` in file order.  `realign`: indel-bearing reads are
-    realigned (realign_indel_reads is implied) against `ref_seqs` {ref_id: contig, upper case}, scored on `device`."""
+    realigned (realign_indel_reads is implied) against `ref_seqs` {ref_id: contig, upper case}, scored on `device`.  `rule`: the loci
+    are of another candidate kind (methylation.Rule with methylation.MethLocus)."""
     out = Restated([[] for _ in loci], [0] * len(loci), len(records), props.max_read_len)
     good = []
     for k, rec in enumerate(records):
@@ -507,7 +515,7 @@ def restate(records: Sequence[BamRecord], loci: Sequence[Locus], props: Props, t
         loc = loci[li]
         members = [(o, r) for o, r in good if is_member(r, loc, props.window)]
         out.n_members[li] = len(members)
-        out.per_locus[li] = locus_observations(members, loc, li, props.max_mapq, t, realign_indel_reads, realigned)
+        out.per_locus[li] = locus_observations(members, loc, li, props.max_mapq, t, realign_indel_reads, realigned, rule)
     return out
 
 
@@ -731,16 +739,39 @@ class _Inputs:
 
 def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, bytes]], props, device=0, omit_mapq_adjustment: bool = False,
                  realign_indel_reads: bool = False, window_bytes: int = 0, realign: Optional[RealignSpec] = None,
-                 indel_candidates: Optional[RealignSpec] = None, indel_props: Optional[IndelProps] = None, _inputs: Optional["_Inputs"] = None) -> List[ObsTable]:
+                 indel_candidates: Optional[RealignSpec] = None, indel_props: Optional[IndelProps] = None, _inputs: Optional["_Inputs"] = None,
+                 methylation_readtype: Optional[str] = None) -> List[ObsTable]:
     """Per candidate (contig, 0-based position, REF, ALT), in the order given, its processed pileup.  device="cpu": the restatement; a
     device number: the kernels, finished as the module header says.  `realign`: indel-bearing reads are realigned (module header);
     realign_indel_reads=True without it raises NeedsRealign for such a read.  `indel_candidates`: deletion / insertion candidates
     (REF and ALT of different lengths) are built, every member realigned with this spec, through the indel session (`indel_tables`;
     `indel_props`: what they need of the alignment properties, default: read from `props`); the SNV / MNV candidates of the same call
-    go the way they always went."""
+    go the way they always went.  `methylation_readtype` ("converted" / "annotated"): candidates with ALT <METH> are built through the
+    methylation session (methylation.tables); the other candidates of the same call go the way they always went."""
     bams = [bam] if isinstance(bam, str) else list(bam)
     inp = _inputs if _inputs is not None else _Inputs(bams, fasta)      # (read once, shared by the SNV / MNV and the indel part of a mixed call)
     seqs, tid = inp.seqs, inp.tid
+    meth = [k for k, c in enumerate(candidates) if bytes(c[3]) == b"<METH>"]
+    if meth:
+        from . import methylation
+        if methylation_readtype is None:
+            raise ValueError("candidate %s:%d is a methylation candidate (methylation_readtype builds them)" % (candidates[meth[0]][0], candidates[meth[0]][1] + 1))
+        meth_set = set(meth)
+        rest = [k for k in range(len(candidates)) if k not in meth_set]
+        out: List[Optional[ObsTable]] = [None] * len(candidates)
+        if rest:
+            for k, tab in zip(rest, observations(bam, fasta, [candidates[k] for k in rest], props, device, omit_mapq_adjustment, realign_indel_reads, window_bytes, realign,
+                                                 indel_candidates, indel_props, _inputs=inp)):
+                out[k] = tab
+        loci = []
+        for k in meth:
+            c, pos = candidates[k][0], int(candidates[k][1])
+            if c not in tid or c not in seqs:
+                raise ValueError("contig %s is not in the BAM header and the reference" % c)
+            loci.append(methylation.MethLocus(tid[c], pos))
+        for k, tab in zip(meth, methylation.tables(bams, loci, props_of(props), methylation_readtype, device, omit_mapq_adjustment, window_bytes, records=inp.records)):
+            out[k] = tab
+        return out
     ind = [k for k, c in enumerate(candidates) if len(c[2]) != len(c[3])]
     if ind:
         if indel_candidates is None:
@@ -832,7 +863,8 @@ def pileup(tables: Sequence[ObsTable], candidates: Sequence[Tuple[str, int, byte
         cols["flags"].append(abi.pack_flags(s.strand, pack_orientation(s.orientation), s.read_position_major, s.softclipped, s.paired, s.is_max_mapq, s.alt_locus))
         third.append(s.third_allele.astype(np.int32))
     cat = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in cols.items()}
-    indel = np.array([len(c[2]) != len(c[3]) for c in candidates], bool)
+    indel = np.array([len(c[2]) != len(c[3]) for c in candidates], bool)      # (a <METH> candidate too: the locus flags of a precise candidate that is no SNV / MNV)
+    meth = np.array([bytes(c[3]) == b"<METH>" for c in candidates], bool)
     snv = np.array([len(c[2]) == 1 for c in candidates], bool) & ~indel
     lf = lf_indel = 0
     for bit in (abi.BIAS_ORIENTATION, abi.BIAS_STRAND, abi.BIAS_POSITION, abi.BIAS_SOFTCLIP, abi.BIAS_ALTLOCUS):
@@ -843,7 +875,7 @@ def pileup(tables: Sequence[ObsTable], candidates: Sequence[Tuple[str, int, byte
     if not omit_bias_mask & abi.BIAS_ORIENTATION:
         lf |= abi.LOCUS_REMOVE_NONSTANDARD
     loc = {"locus_flags": (np.where(indel, lf_indel, lf).astype(np.uint8) | np.where(snv, abi.LOCUS_HAS_SNV, 0).astype(np.uint8)),
-           "variant_type": np.where(indel, abi.VT_INDEL, np.where(snv, abi.VT_SNV, abi.VT_MNV)).astype(np.uint8),
+           "variant_type": np.where(meth, abi.VT_OTHER, np.where(indel, abi.VT_INDEL, np.where(snv, abi.VT_SNV, abi.VT_MNV))).astype(np.uint8),
            "ref_base": np.array([bytes(c[2]).upper()[0] if len(c[2]) == 1 and len(c[3]) == 1 else 0 for c in candidates], np.uint8),
            "alt_base": np.array([bytes(c[3]).upper()[0] if len(c[2]) == 1 and len(c[3]) == 1 else 0 for c in candidates], np.uint8)}
     batch = PileupBatch(1, off.astype(np.uint32), {k: (np.asarray(v, np.float32) if k != "flags" else np.asarray(v, np.uint32)) for k, v in cat.items()}, loc)
@@ -1387,12 +1419,14 @@ def read_candidates(path: str) -> List[Tuple[str, int, str, str, str]]:
 def preprocess_variants(reference: str, candidates: str, bam: str, output: str, alignment_properties: Optional[str] = None, device=0,
                         atomic_candidate_variants: bool = False, omit_mapq_adjustment: bool = False, max_depth: int = 200,
                         score_indel_reads_from_alignment: bool = False, warn=None, realign: Optional[RealignSpec] = None,
-                        indel_candidates: Optional[RealignSpec] = None) -> int:
+                        indel_candidates: Optional[RealignSpec] = None, methylation_readtype: Optional[str] = None) -> int:
     """`preprocess variants` for SNV / MNV candidates of one sample: the observation BCF `output` (format v15) that `call variants`
     reads.  Returns the number of records written.  `realign` (--realign-indel-reads): indel-bearing reads over a candidate are
     realigned as the reference does by default; its gap / hop parameters default to those of the alignment properties.
     `indel_candidates` (--indel-candidates): deletion and insertion candidates are built too, one observation per fragment (the
-    section "deletion and insertion candidates" above); the file may mix them with SNVs / MNVs, records keep the candidate order."""
+    section "deletion and insertion candidates" above); the file may mix them with SNVs / MNVs, records keep the candidate order.
+    `methylation_readtype` (--methylation-read-type converted|annotated): candidates with ALT <METH> are built too (methylation.py);
+    without it such a candidate is refused as every symbolic allele is."""
     import json
     from . import ingest
     if not atomic_candidate_variants:
@@ -1400,7 +1434,14 @@ def preprocess_variants(reference: str, candidates: str, bam: str, output: str, 
                               "realignment against the other candidates at a locus (alt_variants) is not built")
     sites = read_candidates(candidates)
     cands = []
+    if methylation_readtype is not None:
+        from . import methylation
+        if methylation_readtype not in methylation.READTYPES:
+            raise PreprocessError("--methylation-read-type must be one of %s" % ", ".join(methylation.READTYPES))
     for chrom, pos, rid, ref, alt in sites:
+        if methylation_readtype is not None and alt == "<METH>" and ref:
+            cands.append((chrom, pos - 1, ref.encode(), alt.encode()))
+            continue
         sym = alt.startswith("<") or "[" in alt or "]" in alt or alt in ("*", ".")
         if indel_candidates is not None and (sym or not ref or not alt):
             raise PreprocessError("candidate %s:%d %s>%s is a symbolic or breakend allele: only SNVs, MNVs, deletions and insertions are built" % (chrom, pos, ref, alt))
@@ -1422,7 +1463,7 @@ def preprocess_variants(reference: str, candidates: str, bam: str, output: str, 
     try:
         tabs = observations(bam, reference, cands, props, device=device, omit_mapq_adjustment=omit_mapq_adjustment,
                             realign_indel_reads=not score_indel_reads_from_alignment, realign=realign, indel_candidates=indel_candidates,
-                            indel_props=indel_props_of(pj) if indel_candidates is not None else None)
+                            indel_props=indel_props_of(pj) if indel_candidates is not None else None, methylation_readtype=methylation_readtype)
     except NeedsRealign as e:
         raise PreprocessError(str(e) + "; --score-indel-reads-from-alignment scores such reads as they are aligned, --realign-indel-reads realigns them") from e
     deep = sum(1 for t in tabs if len(t) > max_depth)
