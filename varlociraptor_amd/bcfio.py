@@ -93,6 +93,8 @@ class BcfReader:
             rec_start = p
             p += 8
             end = p + l_shared + l_indiv
+            if end > len(buf):   # (bcf_frame of the native readers: a record whose lengths reach behind the stream is an error, not the last record)
+                raise ValueError("truncated BCF record")
             chrom, pos, rlen, qual, nai, nfs = struct.unpack_from("<iiifII", buf, p)
             q = p + 24
             n_allele, n_info = nai >> 16, nai & 0xFFFF

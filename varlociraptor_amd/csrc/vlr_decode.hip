@@ -6,7 +6,9 @@
 //   calling/variants/preprocessing/mod.rs:818-919    read_observations: INFO integer vectors -> u16 words -> bincode -> ReadObservation
 //   utils/mod.rs:449-474                             MiniLogProb {F16, F32}
 // and what vlr_ingest.cpp does for the same rows on the host (decode_into, parse_bcf_record): the two paths are compared column by
-// column and byte by byte in tests/test_gpu_ingest_device.py.
+// column and byte by byte in tests/test_gpu_ingest_device.py; the forms no writer at hand emits (every element kind x integer width x start
+// parity x form of the chain walk, all f16 patterns, bit-vector forms, scan forms, refusals, wrong anchor guesses) are hand-built in
+// tests/record_cases.py, proven on the host in tests/test_record_cases_host.py and given to the kernels in tests/test_gpu_record_cases.py.
 //
 // Stages per chunk of a sample file (all on one stream of the reader):
 //   1. compressed BGZF members  --H2D-->  vlr_inflate_kernel (vlr_inflate.hip)  -->  inflated stream in HBM
