@@ -961,6 +961,15 @@ int vlr_selftest_math(int device, int which, const double* a, const double* b, d
  * lane-contiguous 4-byte loads (4 n bytes per launch), mode 1 writes n f64 with lane-contiguous 8-byte stores (8 n bytes
  * per launch) — so that rocprofv3's FETCH_SIZE / WRITE_SIZE can be calibrated for them (tools/traffic_measure.sh). */
 int vlr_selftest_stream(int device, int mode, int64_t n, int reps);
+/* Diagnostics: vlr_fdr_threshold with its intermediate stages copied back (tests/test_gpu_fdr_stages.py).  Same inputs, same code
+ * path (cap of values above ln 1, padding, staging, kernels, read-back, decision with the host fallback), same *threshold and
+ * *status.  Host arrays, any of which may be NULL: sorted[n] = the keys after the descending sort; prob[n], pep_ln[n], cum[n] = the
+ * probabilities after the optional `smart` conversion, ln PEP and the per-1024-block inclusive prefix sums of the linear PEPs as
+ * the PEP kernel wrote them; block_offset[(n + 1023) / 1024] = the exclusive prefix sums of the block totals; best_raw[3] = the
+ * result words as the device left them, before any host fallback: boundary index + 1 (0 = none), the bits of the expected FDR
+ * of entry 0 (a double), the near-alpha flag.  n == 0: nothing but best_raw (zeros), *threshold and *status is written. */
+int vlr_selftest_fdr_stages(int device, const double* ln_prob, int64_t n, int smart, double alpha_ln, double* sorted, double* prob, double* pep_ln,
+                            double* cum, double* block_offset, int64_t* best_raw, double* threshold, int* status);
 
 /* ---------------------------------------------------------------- native ingest / emission
  * The process boundary of `call variants` without htslib: observation files in (calling.rs:306-339 bcf::Reader,

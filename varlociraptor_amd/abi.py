@@ -363,6 +363,7 @@ SIGNATURES = {
     # ---- diagnostics
     "vlr_selftest_math": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "vlr_selftest_stream": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "vlr_selftest_fdr_stages": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_double] + [C.c_void_p] * 6 + [C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     # ---- native ingest / emission
     "vlr_obs_read": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "vlr_obs_table_free": (None, [C.c_void_p]),

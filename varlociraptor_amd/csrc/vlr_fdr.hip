@@ -1,5 +1,5 @@
 // vlr_fdr.hip — gfx950 kernels of the Bayesian FDR threshold search:
-//   /root/reference/src/filtration/fdr.rs:107-141 (posterior distribution in descending order, posterior error probabilities,
+//   reference src/filtration/fdr.rs:107-141 (posterior distribution in descending order, posterior error probabilities,
 //   bio::stats::bayesian::expected_fdr = running mean of the PEPs, largest PEP whose expected FDR is <= alpha without
 //   letting equal PEPs cross the boundary).  The collection of the per-variant probabilities (utils/mod.rs:177-270) and the
 //   second, filtering pass (utils/mod.rs:288-374) are record I/O and stay on the host (varlociraptor_amd/fdr.py).
@@ -95,7 +95,10 @@ __global__ void __launch_bounds__(1024) fdr_pep_scan(const double* sorted, long 
     if (threadIdx.x == 1023) block_sum[blockIdx.x] = v;
 }
 
-// exclusive scan of the block totals (sequential over chunks of 1024: n / 1024 totals, a few thousand at most)
+// exclusive scan of the block totals, sequential over chunks of 1024 with a running carry: (n + 1023) / 1024 totals, one chunk up to
+// n = 2^20 and one more per further 2^20 entries (n is bounded by device memory alone; tests/test_gpu_fdr_stages.py runs n > 2^20).
+// Exclusive by taking the lane before's inclusive value, not by subtracting the own total again: the PEPs ascend, so a total can be
+// 2^53 times the sum before it, and `off + v - x` would then return 0 for that sum.
 __global__ void __launch_bounds__(1024) fdr_scan_blocks(double* block_sum, long long nb) {
     __shared__ double wsum[16];
     __shared__ double carry;
@@ -103,8 +106,7 @@ __global__ void __launch_bounds__(1024) fdr_scan_blocks(double* block_sum, long 
     __syncthreads();
     for (long long b0 = 0; b0 < nb; b0 += 1024) {
         const long long i = b0 + threadIdx.x;
-        const double x = (i < nb) ? block_sum[i] : 0.0;
-        double v = x;
+        double v = (i < nb) ? block_sum[i] : 0.0;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -112,10 +114,11 @@ __global__ void __launch_bounds__(1024) fdr_scan_blocks(double* block_sum, long 
             if (lane >= o) v += u;
         }
         if (lane == 63) wsum[wave] = v;
+        const double before = __shfl_up(v, 1);  // inclusive value of the lane before = exclusive value of this one inside the wave
         __syncthreads();
         double off = carry;
         for (int w = 0; w < wave; ++w) off += wsum[w];
-        if (i < nb) block_sum[i] = off + v - x;  // exclusive
+        if (i < nb) block_sum[i] = lane == 0 ? off : off + before;
         __syncthreads();
         if (threadIdx.x == 1023) carry = off + v;
         __syncthreads();

@@ -1974,10 +1974,22 @@ static void fdr_search_reference_order(const double* prob, int64_t n, double alp
     else { *status = VLR_FDR_VALUE; *threshold = prob[best]; }
 }
 
-int vlr_fdr_threshold(int device, const double* ln_prob, int64_t n, int smart, double alpha_ln, double* threshold, int* status) {
+// What vlr_selftest_fdr_stages copies back on the way (host arrays, any may be null); vlr_fdr_threshold passes none.
+struct FdrStages {
+    double* sorted = nullptr;        // [n] keys after the sort
+    double* prob = nullptr;          // [n] } as fdr_pep_scan wrote them
+    double* pep_ln = nullptr;        // [n] }
+    double* cum = nullptr;           // [n] }
+    double* block_offset = nullptr;  // [(n + 1023) / 1024] after fdr_scan_blocks
+    int64_t* best_raw = nullptr;     // [3] the result words before any host fallback
+};
+
+// The threshold search behind both entry points: cap of values above ln 1, padding, staging, kernels, read-back, decision.
+static int fdr_threshold_run(int device, const double* ln_prob, int64_t n, int smart, double alpha_ln, double* threshold, int* status, const FdrStages& out) {
     if (n < 0 || (n > 0 && !ln_prob) || !threshold || !status) return fail(VLR_ERR_INVALID_ARGUMENT, "null argument");
     *threshold = 0.0;
     *status = VLR_FDR_EMPTY;
+    if (out.best_raw) out.best_raw[0] = out.best_raw[1] = out.best_raw[2] = 0;
     if (n == 0) return VLR_OK;
     // LogProb sums of PHRED-rounded probabilities overshoot ln 1 by rounding: capped like cap_numerical_overshoot(NUMERICAL_EPSILON)
     // (utils/mod.rs:40, 207-209) instead of being refused; anything larger is not a log probability.
@@ -2016,6 +2028,15 @@ int vlr_fdr_threshold(int device, const double* ln_prob, int64_t n, int smart, d
         if (hipMemcpy(b, best, 24, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(VLR_ERR_HIP, "result copy failed"); break; }
         double f0;
         std::memcpy(&f0, &b[1], 8);
+        if (out.best_raw) { out.best_raw[0] = b[0]; out.best_raw[1] = b[1]; out.best_raw[2] = b[2]; }
+        const size_t nbytes = (size_t)n * 8;
+        if ((out.sorted && hipMemcpy(out.sorted, keys, nbytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (out.prob && hipMemcpy(out.prob, work, nbytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (out.pep_ln && hipMemcpy(out.pep_ln, work + n, nbytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (out.cum && hipMemcpy(out.cum, work + 2 * (size_t)n, nbytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (out.block_offset && hipMemcpy(out.block_offset, work + 3 * (size_t)n, (size_t)nb * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
+            rc = fail(VLR_ERR_HIP, "stage copy failed"); break;
+        }
         if (b[2] != 0) {
             // an expected FDR within rounding of alpha: decide with the reference's accumulation order (ties at alpha)
             std::vector<double> host((size_t)n);
@@ -2033,6 +2054,18 @@ int vlr_fdr_threshold(int device, const double* ln_prob, int64_t n, int smart, d
     } while (0);
     (void)hipFree(d);
     return rc;
+}
+
+int vlr_fdr_threshold(int device, const double* ln_prob, int64_t n, int smart, double alpha_ln, double* threshold, int* status) {
+    return fdr_threshold_run(device, ln_prob, n, smart, alpha_ln, threshold, status, FdrStages());
+}
+
+// diagnostics (tests/test_gpu_fdr_stages.py): the same run with its stages copied back
+int vlr_selftest_fdr_stages(int device, const double* ln_prob, int64_t n, int smart, double alpha_ln, double* sorted, double* prob, double* pep_ln,
+                            double* cum, double* block_offset, int64_t* best_raw, double* threshold, int* status) {
+    FdrStages out;
+    out.sorted = sorted; out.prob = prob; out.pep_ln = pep_ln; out.cum = cum; out.block_offset = block_offset; out.best_raw = best_raw;
+    return fdr_threshold_run(device, ln_prob, n, smart, alpha_ln, threshold, status, out);
 }
 
 // ---- diagnostics (tests/test_gpu_math.py)

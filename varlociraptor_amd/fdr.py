@@ -140,6 +140,26 @@ def fdr_threshold_device(prob_dist: Sequence[float], alpha_ln: float, smart: boo
     return {0: None, 1: thr.value, 2: 0.0, 3: None}[st.value]
 
 
+def fdr_stages_device(prob_dist: Sequence[float], alpha_ln: float, smart: bool = False, device: int = 0) -> dict:
+    """Diagnostics (vlr_selftest_fdr_stages): the run of fdr_threshold_device with its stages copied back — `sorted`, `prob`, `pep_ln`,
+    `cum` (n each), `block_offset` ((n + 1023) // 1024), the raw result words `boundary` (index + 1, 0 = none), `fdr0` and `near_alpha`
+    as the device left them, and the final `threshold` and raw `status` (VLR_FDR_*)."""
+    import ctypes as C
+    from . import engine
+    L = engine.lib()
+    a = np.ascontiguousarray(prob_dist, dtype=np.float64)
+    n = len(a)
+    out = {k: np.empty(n, dtype=np.float64) for k in ("sorted", "prob", "pep_ln", "cum")}
+    out["block_offset"] = np.empty((n + 1023) // 1024, dtype=np.float64)
+    raw = np.zeros(3, dtype=np.int64)
+    thr, st = C.c_double(), C.c_int()
+    engine.check(L.vlr_selftest_fdr_stages(device, a.ctypes.data, n, int(smart), float(alpha_ln), out["sorted"].ctypes.data, out["prob"].ctypes.data,
+                                           out["pep_ln"].ctypes.data, out["cum"].ctypes.data, out["block_offset"].ctypes.data, raw.ctypes.data,
+                                           C.byref(thr), C.byref(st)))
+    out.update(boundary=int(raw[0]), fdr0=float(raw[1:2].view(np.float64)[0]), near_alpha=int(raw[2]), threshold=thr.value, status=st.value)
+    return out
+
+
 def fdr_threshold(prob_dist_desc: Sequence[float], alpha_ln: float, device: str = "cpu") -> Optional[float]:
     """fdr.rs:118-141 + bio::stats::bayesian::expected_fdr: threshold = probability of the last entry whose
     expected FDR (running mean of 1 - p over the descending list) is <= alpha.  Host restatement (numpy/torch on the CPU);
