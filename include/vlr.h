@@ -49,7 +49,9 @@ extern "C" {
                              * 14: vlr_fragpileup_open_realign / _realign_result / _read_realigned (indel-bearing reads over SNV / MNV
                              *     candidates realigned inside the fragment session); still 14, purely additive: vlr_fragpileup_open_indel /
                              *     _read_indel (fragments of deletion / insertion candidates in the fragment session) and
-                             *     vlr_fragpileup_open_methylation / vlr_methylation_tables (fragments of <METH> candidates) */
+                             *     vlr_fragpileup_open_methylation / vlr_methylation_tables (fragments of <METH> candidates); added within 14 as
+                             *     well: vlr_fragpileup_set_alt_variants / _alt_result / _read_alt_variants (the other alleles of a locus on the
+                             *     reference side of a realigned evidence) */
 #define VLR_MAX_SAMPLES 16     /* samples per scenario supported by the device path   */
 #define VLR_N_BIAS      6      /* strand, orientation, position, softclip, homopolymer, alt-locus */
 
@@ -736,8 +738,8 @@ void vlr_indelpileup_close(vlr_indelpileup* s);
  *   record's when the supports differ, else none (mod.rs:409-413), no read position, no third-allele evidence.  The fragment pass
  *   behind it is the one of every session.  An evidence without overlap or with an empty read window gets ln 0.5 / ln 0.5.
  *   Refused, as a status of the observation: a CIGAR that begins with N (VLR_BASEPILEUP_HIT_LEADING_REFSKIP) and a record with an
- *   SI:Z tag (VLR_FRAGPILEUP_OBS_REALIGN_STRAND_INFO).  NOT mirrored: the read-inferred third allele (mod.rs:317-348), alt_variants,
- *   homopolymer_indel_len.  More evidences than evidence_capacity: VLR_FRAGPILEUP_EVIDENCE_OVERFLOW, nothing is written past a buffer,
+ *   SI:Z tag (VLR_FRAGPILEUP_OBS_REALIGN_STRAND_INFO).  NOT mirrored: the read-inferred third allele (mod.rs:317-348),
+ *   homopolymer_indel_len; the other alleles of a locus (alt_variants) only with vlr_fragpileup_set_alt_variants (below).  More evidences than evidence_capacity: VLR_FRAGPILEUP_EVIDENCE_OVERFLOW, nothing is written past a buffer,
  *   vlr_fragpileup_realign_result gives the exact need.  The observations do not depend on window_bytes, the split into files or
  *   pair_byte_limit, bit for bit.
  * vlr_fragpileup_realign_result (after vlr_fragpileup_result): the evidence counts; seconds [0] window gather kernels, [1]
@@ -832,7 +834,7 @@ int  vlr_fragpileup_read_realigned(vlr_fragpileup* s, vlr_indelpileup_hit* hits,
  *   with the validity rule of the kind and writes beside it a vlr_fragpileup_indel_obs.  The insert-size support, prob_sample_alt
  *   and the running maxima of the alignment properties need libm and stay with the caller (varlociraptor_amd/fragments.py).
  *   vlr_fragpileup_read, vlr_fragpileup_realign_result and vlr_fragpileup_read_realigned work on such a session as on a realigning one.
- *   NOT mirrored: the read-inferred third allele, alt_variants, homopolymer_indel_len and the prob_observable_at_homopolymer_*
+ *   NOT mirrored: the read-inferred third allele, homopolymer_indel_len and the prob_observable_at_homopolymer_*
  *   fields, max_depth subsampling, report_fragment_ids, replacements, SVs, breakends, deletions with more than one fetch.
  * vlr_fragpileup_read_indel (after vlr_fragpileup_result): n_obs side records parallel to the observations of vlr_fragpileup_read and
  *   n_loci records of maxima. */
@@ -854,6 +856,40 @@ int  vlr_fragpileup_open_indel(int device, int64_t n_loci, const int32_t* ref_id
                                int realign_window, int mode, const double gap[4], const double* hop, int64_t evidence_capacity,
                                int64_t pair_byte_limit, int has_insert_size, vlr_fragpileup** out);
 int  vlr_fragpileup_read_indel(vlr_fragpileup* s, vlr_fragpileup_indel_obs* extra_obs, int64_t n_obs, vlr_fragpileup_indel_locus* extra_loci, int64_t n_loci);
+/* The other alleles of a locus (`alt_variants`: utils/variant_buffer.rs:203-222, realignment/mod.rs:250-292, prob_allele 426-479; the rule
+ *   is stated once, at the head of csrc/vlr_altvariants.h).  vlr_fragpileup_set_alt_variants gives a session of vlr_fragpileup_open_realign
+ *   or vlr_fragpileup_open_indel, once and before its first vlr_fragpileup_add_bam, the competitors of its loci: those of locus l are
+ *   comp_offset[l] .. comp_offset[l + 1], at most VLR_FRAGPILEUP_MAX_ALT_VARIANTS each, the alt allele window of competitor c is
+ *   comp_bases[comp_base_offset[c] .. comp_base_offset[c + 1]) (upper case, as the caller builds the alt window of that candidate).
+ *   Refused with VLR_ERR_INVALID_ARGUMENT and a message that names the locus or competitor: a plain or methylation session, a second call,
+ *   a call after a BAM was added, more than VLR_FRAGPILEUP_MAX_ALT_VARIANTS competitors at a locus, descending offsets, an empty window or
+ *   one longer than the alt-window limit of the session (VLR_FRAGPILEUP_MAX_INDEL_LEN plus twice the ref window, int(1.5 * realign_window):
+ *   the limit of vlr_fragpileup_open_indel, in either session, since an indel may compete with an MNV).  A refusal launches nothing and
+ *   leaves the session as it was.
+ *   Such a session scores an evidence in 2 + K pairs — (ref, read), (alt, read), (competitor i, read) — through the edit-distance
+ *   kernel, selects per evidence the reference-side alleles at the minimum distance, compacts those pairs and the alt pair, runs the pair
+ *   HMM of the session's mode over the compacted pairs alone and takes as ln_ref the largest score (the lowest index on equal scores),
+ *   as dist_ref the minimum distance.  In a session of vlr_fragpileup_open_realign an MNV locus with a competitor realigns every
+ *   enclosing record, with or without an I / D operation (mnv.rs:83); an SNV locus does not (snv.rs:76).  A session that never calls
+ *   vlr_fragpileup_set_alt_variants launches the kernels it always launched.
+ * vlr_fragpileup_alt_result (after vlr_fragpileup_result): how many pairs went through the edit-distance kernel and the pair HMM.
+ * vlr_fragpileup_read_alt_variants: one record per evidence, parallel to vlr_fragpileup_read_realigned. */
+#define VLR_FRAGPILEUP_MAX_ALT_VARIANTS 15
+typedef struct {
+    uint8_t  winner;               /* the reference-side allele that gave ln_ref: 0 = the reference, i = competitor i (1-based)         */
+    uint8_t  n_tied;               /* reference-side alleles at the minimum edit distance (0: none had a hit)                          */
+    uint8_t  n_ref_side_hits;      /* reference-side alleles with a hit                                                                */
+    uint8_t  pad[5];
+} vlr_fragpileup_alt_hit;
+typedef struct {
+    int64_t  n_edit_pairs;         /* pairs that went through the edit-distance kernel: the sum of 2 + K over the evidences            */
+    int64_t  n_hmm_pairs;          /* pairs that went through the pair HMM: per evidence the tied set and the alt pair                 */
+    int64_t  n_competitors;        /* competitors of the table                                                                         */
+    int64_t  n_loci_with_competitors;
+} vlr_fragpileup_alt_counts;
+int  vlr_fragpileup_set_alt_variants(vlr_fragpileup* s, const uint64_t* comp_offset, const uint64_t* comp_base_offset, const uint8_t* comp_bases);
+int  vlr_fragpileup_alt_result(vlr_fragpileup* s, vlr_fragpileup_alt_counts* out);
+int  vlr_fragpileup_read_alt_variants(vlr_fragpileup* s, vlr_fragpileup_alt_hit* out, int64_t n_evidences);
 /* Methylation candidates (ALT <METH>) in the fragment session (variants/types/methylation.rs; the rule is stated once, at the head of
  *   csrc/vlr_methylation.h).  vlr_fragpileup_open_methylation takes the arguments of vlr_fragpileup_open with the loci as (ref_id, start)
  *   only — the locus is [start, start + 1), the C of a CpG — and readtype: VLR_METH_CONVERTED (bisulfite / EM-seq reads: C / T forward,

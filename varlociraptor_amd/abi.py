@@ -242,6 +242,17 @@ FRAGPILEUP_INDEL_NONPOSITIVE_ISIZE = 1
 FRAGPILEUP_INDEL_OBS_DTYPE = np.dtype([("insert_size", "<i8"), ("len_left", "<u4"), ("len_right", "<u4"), ("flags", "<u4"), ("pad", "<u4")])
 FRAGPILEUP_INDEL_LOCUS_DTYPE = np.dtype([("max_del", "<u4"), ("max_ins", "<u4"), ("max_clip", "<u4"), ("max_clip_l_seq", "<u4")])
 assert FRAGPILEUP_INDEL_OBS_DTYPE.itemsize == 24 and FRAGPILEUP_INDEL_LOCUS_DTYPE.itemsize == 16
+# vlr_fragpileup_set_alt_variants / _alt_result / _read_alt_variants (the other alleles of a locus; additive, ABI stays 14)
+FRAGPILEUP_MAX_ALT_VARIANTS = 15
+FRAGPILEUP_ALT_HIT_DTYPE = np.dtype([("winner", "u1"), ("n_tied", "u1"), ("n_ref_side_hits", "u1"), ("pad", "u1", (5,))])
+assert FRAGPILEUP_ALT_HIT_DTYPE.itemsize == 8
+
+
+class FragPileupAltCounts(C.Structure):
+    """vlr_fragpileup_alt_counts"""
+    _fields_ = [("n_edit_pairs", C.c_int64), ("n_hmm_pairs", C.c_int64), ("n_competitors", C.c_int64), ("n_loci_with_competitors", C.c_int64)]
+
+
 # vlr_fragpileup_open_methylation (<METH> candidates in the fragment session; additive, ABI stays 14)
 METH_CONVERTED, METH_ANNOTATED = 0, 1
 
@@ -348,6 +359,9 @@ SIGNATURES = {
     "vlr_fragpileup_open_indel": (C.c_int, [C.c_int, C.c_int64] + [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_char_p, C.c_int,
                                             C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "vlr_fragpileup_read_indel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "vlr_fragpileup_set_alt_variants": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vlr_fragpileup_alt_result": (C.c_int, [C.c_void_p, C.POINTER(FragPileupAltCounts)]),
+    "vlr_fragpileup_read_alt_variants": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "vlr_fragpileup_open_methylation": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                                   C.POINTER(C.c_void_p)]),
     "vlr_methylation_tables": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),

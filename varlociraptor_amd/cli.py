@@ -171,7 +171,7 @@ def main(argv=None):
     pv.add_argument("--candidates", required=True, help="candidate variants (VCF or BCF)")
     pv.add_argument("--bam", required=True)
     pv.add_argument("--alignment-properties", help="JSON of `estimate alignment-properties` (default: estimated from --bam on the device)")
-    pv.add_argument("--atomic-candidate-variants", action="store_true", help="required: every candidate on its own (no realignment against the others)")
+    pv.add_argument("--atomic-candidate-variants", action="store_true", help="required: SNV / MNV candidates are scored from the read's alignment unless a flag below realigns")
     pv.add_argument("--omit-mapq-adjustment", action="store_true")
     pv.add_argument("--max-depth", type=int, default=200, help="loci above it are counted in a warning and processed whole")
     pv.add_argument("--score-indel-reads-from-alignment", action="store_true",
@@ -185,6 +185,10 @@ def main(argv=None):
     pv.add_argument("--methylation-read-type", choices=["converted", "annotated"],
                     help="build methylation candidates (ALT <METH>) too: 'converted' for bisulfite / EM-seq reads, 'annotated' for reads with "
                     "MM / ML tags (cli.rs:367-371; without it such a candidate is an error)")
+    pv.add_argument("--alt-variants", action="store_true",
+                    help="score a realigned read against the other ALT alleles at the candidate's (CHROM, POS) too, as the reference does: a read "
+                    "that carries another allele of a multi-allelic site then counts against the candidate (without it every candidate is "
+                    "scored as if it were alone at its position)")
     pv.add_argument("--indel-window", type=int, default=64, help="bases of a read realigned on either side of the candidate (at most 64, cli.rs:877)")
     pv.add_argument("--pairhmm-mode", choices=["exact", "fast", "homopolymer"], default="exact")
     pv.add_argument("--device", default="0", help="HIP device index, or 'cpu' for the Python restatement")
@@ -203,7 +207,7 @@ def main(argv=None):
                                               warn=lambda m: print(f"[WARN] {m}", file=sys.stderr),
                                               realign=fragments.RealignSpec(a.indel_window, a.pairhmm_mode) if a.realign_indel_reads else None,
                                               indel_candidates=fragments.RealignSpec(a.indel_window, a.pairhmm_mode) if a.indel_candidates else None,
-                                              methylation_readtype=a.methylation_read_type)
+                                              methylation_readtype=a.methylation_read_type, alt_variants=a.alt_variants)
         except (fragments.PreprocessError, fragments.FragPileupError, fragments.InvalidReadOrientationInfo, fragments.EngineError) as e:
             print(f"error: {e}", file=sys.stderr)
             sys.exit(1)

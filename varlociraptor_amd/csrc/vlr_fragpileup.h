@@ -24,8 +24,9 @@
 //                            normalisation of mod.rs:358-376 (`normalize_support`).  The strand is the record's when the normalised
 //                            supports differ, else none (mod.rs:409-413); read position and third-allele evidence are none.
 //                            NOT mirrored: the read-inferred third allele (mod.rs:317-348 needs the Myers traceback of the bio crate,
-//                            which the reference does not vendor), alt_variants (candidates are atomic, so an MNV is realigned only
-//                            for an indel operation), homopolymer_indel_len.  Two inputs are refused, each with a status of its own: a
+//                            which the reference does not vendor), homopolymer_indel_len.  alt_variants (the other alleles of the
+//                            locus on the reference side, and mnv.rs:83's realignment of every enclosing record of an MNV that has
+//                            one) is vlr_altvariants.h's, in a session with vlr_fragpileup_set_alt_variants.  Two inputs are refused, each with a status of its own: a
 //                            CIGAR that begins with N (read_pos fails) and a record with an SI:Z tag (strand information over an
 //                            interval, mod.rs:381-387).  A region without overlap or with an empty read window gives ln 0.5 / ln 0.5
 //                            (mod.rs:186-199).
@@ -51,7 +52,8 @@
 //                            hard), inner distance + both spans; a value <= 0 is the reference's assertion and comes back flagged.
 //                            `cigar_maxima`: the longest D, the longest I and the largest soft clip of a record, which the reference
 //                            folds into the alignment properties while it reads (mod.rs:310, alignment_properties.rs:94-144).
-//                            NOT mirrored: the read-inferred third allele, alt_variants, homopolymer_indel_len and the two
+//                            The other alleles of the locus (alt_variants): vlr_altvariants.h, in a session with
+//                            vlr_fragpileup_set_alt_variants.  NOT mirrored: the read-inferred third allele, homopolymer_indel_len and the two
 //                            prob_observable_at_homopolymer_* fields (the Myers traceback of the bio crate), max_depth subsampling,
 //                            report_fragment_ids, replacements, SVs, breakends, deletions with more than one fetch.
 //   methylation candidates   (a methylation session, vlr_fragpileup_open_methylation) variants/types/methylation.rs: vlr_methylation.h, included at
@@ -370,7 +372,7 @@ VLR_BP_HD inline vlr_indelpileup_hit realign_evidence(const Realign& ra, const v
 VLR_BP_HD inline RecMembers record_members(const vlr_bp::Tables& t, const vlr_bp::Loci& L, const uint8_t* p, uint64_t size, uint64_t ordinal,
                                            bool realign_indel_reads, int64_t window, uint64_t coeff, Member* out, uint64_t room, uint64_t name_off, uint8_t* name_dst,
                                            uint64_t xa_off, AltKey* xa_dst, uint64_t xa_room, const Realign* ra = nullptr, vlr_indelpileup_hit* ev_out = nullptr,
-                                           uint64_t ev_room = 0, const Indel* ia = nullptr) {
+                                           uint64_t ev_room = 0, const Indel* ia = nullptr, const uint64_t* comp_off = nullptr) {
     RecMembers res = {0u, 0u, 0u, vlr_bp::REC_OK, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     Rec r;
     res.cls = vlr_bp::decode(p, size, r);
@@ -419,8 +421,12 @@ VLR_BP_HD inline RecMembers record_members(const vlr_bp::Tables& t, const vlr_bp
         }
         // SingleLocus::overlap(read, false, 0, 0) == Enclosing
         const bool enclosing = r.pos <= L.start[li] && r.end_pos >= L.start[li] + (int64_t)L.len[li];
+        // mnv.rs:83: an MNV whose locus has other alleles (comp_off: a session with vlr_fragpileup_set_alt_variants) realigns every
+        // enclosing record; snv.rs:76 asks for the I / D operation whatever the locus has
+        const bool by_competitor = comp_off != nullptr && ra != nullptr && realign_indel_reads && !r.has_indel && L.kind[li] == VLR_BASEPILEUP_MNV &&
+                                   comp_off[li + 1] > comp_off[li];
         // a realigning pass: the evidence of a record vlr_bp::score flags (the count pass and the fill pass see the same ones)
-        if (ra != nullptr && enclosing && realign_indel_reads && r.has_indel) {
+        if (ra != nullptr && enclosing && realign_indel_reads && (r.has_indel || by_competitor)) {
             uint32_t xb, yb;
             const vlr_indelpileup_hit h = realign_evidence(*ra, L, li, r, ordinal, &xb, &yb);
             if (ev_out != nullptr && (uint64_t)res.n_ev < ev_room) ev_out[res.n_ev] = h;
@@ -447,7 +453,8 @@ VLR_BP_HD inline RecMembers record_members(const vlr_bp::Tables& t, const vlr_bp
             if (enclosing) {
                 m.bits |= M_ENCLOSING;
                 vlr_basepileup_hit h;
-                if (vlr_bp::score(t, L, li, r, ordinal, realign_indel_reads, h)) {
+                if (by_competitor) { m.bits |= M_HAS_SUPPORT; m.status = VLR_BASEPILEUP_HIT_NEEDS_REALIGN; }   // (until apply_realigned)
+                else if (vlr_bp::score(t, L, li, r, ordinal, realign_indel_reads, h)) {
                     m.bits |= M_HAS_SUPPORT;
                     m.prob_ref = h.prob_ref; m.prob_alt = h.prob_alt;
                     m.read_position = h.read_position;

@@ -63,6 +63,7 @@
 #include "vlr_bamsession.h"
 #include "vlr_fragpileup.h"
 #include "vlr_pairscore.h"
+#include "vlr_altvariants.h"
 
 static_assert(sizeof(vlr_indelpileup_hit) == 64, "hit layout");
 static_assert(sizeof(vlr_fragpileup_obs) == 56, "observation layout");
@@ -72,6 +73,7 @@ static_assert(sizeof(vlr_fp::AltKey) == 16, "key layout");
 static_assert(sizeof(vlr_fp::Side) == 32, "side record layout");
 static_assert(sizeof(vlr_fragpileup_indel_obs) == 24, "indel side record layout");
 static_assert(sizeof(vlr_fragpileup_indel_locus) == 16, "indel locus record layout");
+static_assert(sizeof(vlr_fragpileup_alt_hit) == 8, "alt hit layout");
 
 namespace vlr_fp {
 
@@ -157,13 +159,14 @@ __device__ __forceinline__ void frag_count_body(const uint8_t* __restrict__ base
                                                               vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
                                                               uint32_t* __restrict__ cnt, uint32_t* __restrict__ nbytes, uint32_t* __restrict__ nxa,
                                                               unsigned long long* __restrict__ counters, Realign ra, uint32_t* __restrict__ nev,
-                                                              uint32_t* __restrict__ nxb, uint32_t* __restrict__ nyb, int64_t max_locus_len) {
+                                                              uint32_t* __restrict__ nxb, uint32_t* __restrict__ nyb, int64_t max_locus_len,
+                                                              const uint64_t* __restrict__ comp_off = nullptr) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t o = starts[i], end = starts[i + 1];
     const Indel ia{max_locus_len, nullptr};
     const RecMembers r = record_members(t, L, base + o, end - o, rec0 + (uint64_t)i, realign != 0, window, coeff, nullptr, 0, 0, nullptr, 0, nullptr, 0,
-                                        kRealign ? &ra : nullptr, nullptr, 0, kIndel ? &ia : nullptr);
+                                        kRealign ? &ra : nullptr, nullptr, 0, kIndel ? &ia : nullptr, comp_off);
     cnt[i] = r.n_members;
     nbytes[i] = r.name_bytes;
     nxa[i] = r.n_xa;
@@ -178,7 +181,8 @@ __device__ __forceinline__ void frag_fill_body(const uint8_t* __restrict__ base,
                                                              const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ nbytes, const uint64_t* __restrict__ off,
                                                              const uint64_t* __restrict__ noff, const uint64_t* __restrict__ xoff, uint64_t member0, uint64_t member_cap,
                                                              uint64_t name0, uint64_t name_cap, uint64_t key0, uint64_t key_cap, Member* __restrict__ members,
-                                                             uint8_t* __restrict__ names, AltKey* __restrict__ keys, uint32_t* __restrict__ locus_cnt, EvFill ev, IndelFill in) {
+                                                             uint8_t* __restrict__ names, AltKey* __restrict__ keys, uint32_t* __restrict__ locus_cnt, EvFill ev, IndelFill in,
+                                                             const uint64_t* __restrict__ comp_off = nullptr) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     // the end of the chunk's pairs, for the last evidence's windows (index 2 * (ev0 + n_ev) <= 2 * capacity: the arrays hold one more)
     if (kRealign && i == 0 && ev.on) { ev.gx[2 * (ev.ev0 + ev.n_ev)] = ev.x0 + ev.x_bytes; ev.gy[2 * (ev.ev0 + ev.n_ev)] = ev.y0 + ev.y_bytes; }
@@ -201,7 +205,7 @@ __device__ __forceinline__ void frag_fill_body(const uint8_t* __restrict__ base,
     if (kIndel && !(ev.on && in.on)) return;
     const RecMembers r = record_members(t, L, base + o, end - o, rec0 + (uint64_t)i, realign != 0, window, coeff, members + first, room, name_at, name_dst, key_at,
                                         key_room ? keys + key_at : nullptr, key_room, kRealign && ev.on ? &ev.ra : nullptr, e_room ? ev.hits + e_first : nullptr, e_room,
-                                        kIndel ? &ia : nullptr);
+                                        kIndel ? &ia : nullptr, comp_off);
     const uint64_t written = std::min<uint64_t>(r.n_members, room);
     if (kRealign && e_room) {   // the evidences of the record: their members, the offsets of their pairs, where their read windows come from
         uint64_t x = ev.x0 + ev.xoff[i], y = ev.y0 + ev.yoff[i], e = 0;
@@ -277,6 +281,90 @@ __global__ __launch_bounds__(kThreads) void frag_fill_indel_kernel(const uint8_t
                                                                    IndelFill in) {
     frag_fill_body<true, true>(base, starts, n, rec0, t, L, realign, window, coeff, cnt, nbytes, off, noff, xoff, member0, member_cap, name0, name_cap, key0, key_cap,
                                members, names, keys, locus_cnt, ev, in);
+}
+
+// The member pass of a realigning session with vlr_fragpileup_set_alt_variants: the realigning instances of the two bodies with the
+// loci's competitor offsets, so that an MNV with a competitor realigns every enclosing record (vlr_fp::record_members).  The x and y
+// bytes they count stay those of the evidence's own two pairs: the competitors' pairs exist only while a range is scored.
+__global__ __launch_bounds__(kThreads) void frag_count_alt_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
+                                                                  vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
+                                                                  uint32_t* __restrict__ cnt, uint32_t* __restrict__ nbytes, uint32_t* __restrict__ nxa,
+                                                                  unsigned long long* __restrict__ counters, Realign ra, uint32_t* __restrict__ nev,
+                                                                  uint32_t* __restrict__ nxb, uint32_t* __restrict__ nyb, const uint64_t* __restrict__ comp_off) {
+    frag_count_body<true, false>(base, starts, n, rec0, t, L, realign, window, coeff, cnt, nbytes, nxa, counters, ra, nev, nxb, nyb, 0, comp_off);
+}
+__global__ __launch_bounds__(kThreads) void frag_fill_alt_kernel(const uint8_t* __restrict__ base, const uint64_t* __restrict__ starts, int64_t n, uint64_t rec0,
+                                                                 vlr_bp::Tables t, vlr_bp::Loci L, int realign, int64_t window, uint64_t coeff,
+                                                                 const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ nbytes, const uint64_t* __restrict__ off,
+                                                                 const uint64_t* __restrict__ noff, const uint64_t* __restrict__ xoff, uint64_t member0, uint64_t member_cap,
+                                                                 uint64_t name0, uint64_t name_cap, uint64_t key0, uint64_t key_cap, Member* __restrict__ members,
+                                                                 uint8_t* __restrict__ names, AltKey* __restrict__ keys, uint32_t* __restrict__ locus_cnt, EvFill ev,
+                                                                 const uint64_t* __restrict__ comp_off) {
+    frag_fill_body<true, false>(base, starts, n, rec0, t, L, realign, window, coeff, cnt, nbytes, off, noff, xoff, member0, member_cap, name0, name_cap, key0, key_cap,
+                                members, names, keys, locus_cnt, ev, IndelFill{}, comp_off);
+}
+
+// The passes of a range of evidences in a session with competitors (vlr_altvariants.h has their text and their bounds).
+// One wave per evidence: its windows into its 2 + K pairs.  gx / gy: the session-wide offsets of the evidences' own two pairs
+// (at 2 * e), xb / yb / yq the session's pair arrays; pair_base[n_ev + 1], xoff / yoff [n_pairs + 1]: the range's, from the host.
+__global__ __launch_bounds__(vlr_ip::kThreads) void frag_alt_expand_kernel(uint64_t n_ev, const vlr_indelpileup_hit* __restrict__ hits, vlr_av::Table tab,
+                                                                           const uint64_t* __restrict__ gx, const uint64_t* __restrict__ gy, const uint8_t* __restrict__ xb,
+                                                                           const uint8_t* __restrict__ yb, const uint8_t* __restrict__ yq,
+                                                                           const uint32_t* __restrict__ pair_base, const uint32_t* __restrict__ xoff,
+                                                                           const uint32_t* __restrict__ yoff, uint8_t* __restrict__ x, uint8_t* __restrict__ y,
+                                                                           uint8_t* __restrict__ q) {
+    const uint64_t e = (uint64_t)blockIdx.x * (vlr_ip::kThreads / 64) + (threadIdx.x >> 6);
+    if (e >= n_ev) return;
+    const vlr_indelpileup_hit h = hits[e];
+    if (h.status || (int64_t)h.locus >= tab.n_loci) return;   // (an evidence with a status: its pairs are empty)
+    const uint32_t p0 = pair_base[e], k = pair_base[e + 1] - p0 - 2u;
+    const uint64_t x0 = gx[2 * e], x1 = gx[2 * e + 1], x2 = gx[2 * e + 2], y0 = gy[2 * e], y1 = gy[2 * e + 1];
+    vlr_av::expand_evidence(threadIdx.x & 63u, 64u, tab, h.locus, k, xb + x0, (uint32_t)(x1 - x0), (uint32_t)(x2 - x1), yb + y0, yq + y0, (uint32_t)(y1 - y0), xoff, yoff, p0,
+                            x, y, q);
+}
+
+// One evidence per thread: the tied set of its reference side.  keep / klx / kly [n_pairs]: the flag and the bytes of a kept pair
+// (0 otherwise), the three count arrays of the compaction's scan; band[n_pairs].
+__global__ __launch_bounds__(kThreads) void frag_alt_select_kernel(uint64_t n_ev, const uint32_t* __restrict__ pair_base, const int32_t* __restrict__ dist,
+                                                                   const uint32_t* __restrict__ xoff, const uint32_t* __restrict__ yoff, int fast, uint32_t* __restrict__ keep,
+                                                                   uint32_t* __restrict__ klx, uint32_t* __restrict__ kly, int32_t* __restrict__ band) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_ev) return;
+    const uint32_t p0 = pair_base[e], np = pair_base[e + 1] - p0;
+    if (np < 2u || np > (uint32_t)vlr_av::kMaxPairs) return;
+    const vlr_av::Selected s = vlr_av::select(dist + p0, np - 2u);
+    for (uint32_t j = 0; j < np; ++j) {
+        const uint32_t p = p0 + j, on = (s.keep >> j) & 1u;
+        keep[p] = on;
+        klx[p] = on ? xoff[p + 1] - xoff[p] : 0u;
+        kly[p] = on ? yoff[p + 1] - yoff[p] : 0u;
+        band[p] = vlr_av::band_of(dist[p], fast != 0);
+    }
+}
+
+// One wave per pair: a kept pair into the compacted batch, at the places the scans gave it (slot / cx_at / cy_at [n_pairs]).
+__global__ __launch_bounds__(vlr_ip::kThreads) void frag_alt_compact_kernel(uint64_t n_pairs, const uint32_t* __restrict__ keep, const uint64_t* __restrict__ slot,
+                                                                            const uint64_t* __restrict__ cx_at, const uint64_t* __restrict__ cy_at,
+                                                                            const uint32_t* __restrict__ xoff, const uint32_t* __restrict__ yoff, const uint8_t* __restrict__ x,
+                                                                            const uint8_t* __restrict__ y, const uint8_t* __restrict__ q, const int32_t* __restrict__ band,
+                                                                            uint64_t n_kept, uint64_t x_total, uint64_t y_total, uint32_t* __restrict__ cxoff,
+                                                                            uint32_t* __restrict__ cyoff, int32_t* __restrict__ cband, uint8_t* __restrict__ cx,
+                                                                            uint8_t* __restrict__ cy, uint8_t* __restrict__ cq) {
+    const uint64_t p = (uint64_t)blockIdx.x * (vlr_ip::kThreads / 64) + (threadIdx.x >> 6);
+    if (p >= n_pairs || !keep[p]) return;
+    vlr_av::compact_pair(threadIdx.x & 63u, 64u, xoff, yoff, x, y, q, (uint32_t)p, band[p], slot[p], cx_at[p], cy_at[p], n_kept, x_total, y_total, cxoff, cyoff, cband, cx, cy,
+                         cq);
+}
+
+// One evidence per thread: the winner of its tied set into the evidence (ln_ref, dist_ref, ln_alt, dist_alt) and its side record.
+__global__ __launch_bounds__(kThreads) void frag_alt_collect_kernel(uint64_t n_ev, uint64_t hit0, uint64_t capacity, const uint32_t* __restrict__ pair_base,
+                                                                    const int32_t* __restrict__ dist, const uint64_t* __restrict__ slot, const double* __restrict__ lnp,
+                                                                    uint64_t n_kept, vlr_indelpileup_hit* __restrict__ hits, vlr_fragpileup_alt_hit* __restrict__ alt) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_ev || hit0 + e >= capacity) return;
+    const uint32_t p0 = pair_base[e], np = pair_base[e + 1] - p0;
+    if (np < 2u || np > (uint32_t)vlr_av::kMaxPairs) return;
+    vlr_av::collect_evidence(dist + p0, np - 2u, slot + p0, lnp, n_kept, hits + hit0 + e, alt + hit0 + e);
 }
 
 // The member pass of a methylation session: the count and the fill of frag_count_body / frag_fill_body without evidences, over
@@ -608,6 +696,14 @@ struct vlr_fragpileup : vlr_bam::Session {
     bool meth = false;
     vlr_fp::Meth me{0, {nullptr, nullptr}};
     double* d_meth_tables = nullptr;                 // ln_meth[256], ln_unmeth[256]
+    // a session with vlr_fragpileup_set_alt_variants: the competitor table (host and device) and what the scoring says of it
+    bool alt_set = false, bam_added = false;
+    uint64_t alt_limit = 0;                          // the longest competitor window the session takes
+    std::vector<uint64_t> h_comp_off, h_comp_boff;
+    uint64_t *d_comp_off = nullptr, *d_comp_boff = nullptr; uint8_t* d_comp_bases = nullptr;
+    std::vector<vlr_fragpileup_alt_hit> alt_hits;    // parallel to ev
+    int64_t n_edit_pairs = 0, n_hmm_pairs = 0, n_loci_with_comp = 0;
+    vlr_av::Table alt_table() const { return vlr_av::Table{n_loci, d_comp_off, d_comp_boff, d_comp_bases}; }
     vlr_fp::IndelFill indel_fill() const { return vlr_fp::IndelFill{indel, max_locus_len, member_cap, d_sides, d_max_del, d_max_ins, d_max_clip}; }
 };
 
@@ -643,6 +739,9 @@ int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
     else if (s->indel)
         hipLaunchKernelGGL(frag_count_indel_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff,
                            d_cnt, d_nbytes, d_nxa, s->d_counters, s->ra(), d_cnt + K_EV * stride, d_cnt + K_X * stride, d_cnt + K_Y * stride, s->max_locus_len);
+    else if (s->realigning && s->alt_set)
+        hipLaunchKernelGGL(frag_count_alt_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt,
+                           d_nbytes, d_nxa, s->d_counters, s->ra(), d_cnt + K_EV * stride, d_cnt + K_X * stride, d_cnt + K_Y * stride, s->d_comp_off);
     else if (s->realigning)
         hipLaunchKernelGGL(frag_count_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt,
                            d_nbytes, d_nxa, s->d_counters, s->ra(), d_cnt + K_EV * stride, d_cnt + K_X * stride, d_cnt + K_Y * stride);
@@ -674,6 +773,10 @@ int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
             hipLaunchKernelGGL(frag_fill_indel_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt,
                                d_nbytes, s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys,
                                s->key_cap, s->d_members, s->d_names, s->d_keys, s->d_lcnt, ev, s->indel_fill());
+        else if (s->realigning && s->alt_set)
+            hipLaunchKernelGGL(frag_fill_alt_kernel, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt, d_nbytes,
+                               s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys, s->key_cap,
+                               s->d_members, s->d_names, s->d_keys, s->d_lcnt, ev, s->d_comp_off);
         else if (s->realigning)
             hipLaunchKernelGGL(frag_fill_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, d_base, d_starts, n, rec0, s->dl.tables, s->dl.loci, s->realign, s->win, s->coeff, d_cnt, d_nbytes,
                                s->d_off, s->d_off + K_NAME * stride, s->d_off + K_XA * stride, s->n_members, s->member_cap, s->n_name_bytes, s->name_cap, s->n_keys, s->key_cap,
@@ -707,6 +810,23 @@ int run_chunk(vlr_fragpileup* s, vlr_dev_file* df, int64_t n, hipStream_t st) {
 }
 
 
+// the normalised supports of the scored evidences (s->ev) into their members
+int apply_pass(vlr_fragpileup* s, vlr_bam::Buffers& scratch, hipStream_t st, double& t0) {
+    const size_t ne = s->ev.size();
+    double* d_norm = nullptr;
+    std::vector<double> norm(2 * ne);
+    for (size_t e = 0; e < ne; ++e) {
+        norm[2 * e] = s->ev[e].ln_ref; norm[2 * e + 1] = s->ev[e].ln_alt;
+        normalize_support(&norm[2 * e], &norm[2 * e + 1]);
+    }
+    int rc;
+    if ((rc = scratch.guarded(d_norm, 2 * ne)) != VLR_OK) return rc;
+    VLR_HIP_OK(hipMemcpy(d_norm, norm.data(), 2 * ne * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(frag_apply_kernel, dim3((unsigned)((ne + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, s->d_ev, s->d_evm, d_norm, (uint64_t)ne,
+                       std::min<uint64_t>(s->n_members, s->member_cap), s->d_members);
+    return vlr_ip::sync_stage(st, s->rt[3], t0);
+}
+
 // The realignment of the session's evidences: scored in ranges of evidences whose pair bytes fit pair_byte_limit, normalised on the
 // host, written into their members.
 int realign_pass(vlr_fragpileup* s) {
@@ -718,7 +838,7 @@ int realign_pass(vlr_fragpileup* s) {
     gx[2 * ne] = s->x_total; gy[2 * ne] = s->y_total;
     for (size_t p = 0; p < 2 * ne; ++p)
         if (gx[p] > gx[p + 1] || gy[p] > gy[p + 1] || gx[p + 1] > s->x_cap || gy[p + 1] > s->y_cap) return bfail(VLR_ERR_HIP, "vlr_fragpileup_result: the pair offsets of evidence %zu are not ascending", p / 2);
-    uint32_t *d_xoff = nullptr, *d_yoff = nullptr; int32_t *d_band = nullptr, *d_dist = nullptr; double *d_lnp = nullptr, *d_norm = nullptr;
+    uint32_t *d_xoff = nullptr, *d_yoff = nullptr; int32_t *d_band = nullptr, *d_dist = nullptr; double* d_lnp = nullptr;
     std::vector<uint32_t> xo, yo;
     vlr_bam::Buffers scratch;
     auto body = [&]() -> int {
@@ -752,16 +872,130 @@ int realign_pass(vlr_fragpileup* s) {
         double t0 = now_s();
         s->ev.resize(ne);
         VLR_HIP_OK(hipMemcpy(s->ev.data(), s->d_ev, ne * sizeof(vlr_indelpileup_hit), hipMemcpyDeviceToHost));
-        std::vector<double> norm(2 * ne);
-        for (size_t e = 0; e < ne; ++e) {
-            norm[2 * e] = s->ev[e].ln_ref; norm[2 * e + 1] = s->ev[e].ln_alt;
-            normalize_support(&norm[2 * e], &norm[2 * e + 1]);
+        if ((rc = apply_pass(s, scratch, st, t0)) != VLR_OK) return rc;
+        bool ok = true;
+        rc = scratch.guards_intact(&ok);
+        if (rc == VLR_OK && !ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
+        return rc;
+    };
+    const int rc = body();
+    scratch.free();
+    return rc;
+}
+
+// The realignment of a session with competitors (vlr_fragpileup_set_alt_variants): per range of evidences whose EXPANDED pair bytes fit
+// pair_byte_limit (an evidence whose own pairs exceed it is a range of its own) the windows are expanded into 2 + K pairs, all go
+// through the edit-distance kernel, the select kernel marks the tied set and the alt pair, three scans (kept pairs, their x bytes,
+// their y bytes) place them, the compact kernel copies them, the pair HMM of the mode runs over the compacted batch alone and the
+// collect kernel takes the winner.  seconds: [1] expand + edit distance + select, [2] compaction + pair HMM, [3] collect and apply.
+int realign_pass_alt(vlr_fragpileup* s) {
+    const size_t ne = (size_t)s->n_ev;
+    std::vector<uint64_t> gx(2 * ne + 1), gy(2 * ne + 1);
+    VLR_HIP_OK(hipMemcpy(gx.data(), s->d_gx, gx.size() * 8, hipMemcpyDeviceToHost));
+    VLR_HIP_OK(hipMemcpy(gy.data(), s->d_gy, gy.size() * 8, hipMemcpyDeviceToHost));
+    gx[2 * ne] = s->x_total; gy[2 * ne] = s->y_total;
+    for (size_t p = 0; p < 2 * ne; ++p)
+        if (gx[p] > gx[p + 1] || gy[p] > gy[p + 1] || gx[p + 1] > s->x_cap || gy[p + 1] > s->y_cap) return bfail(VLR_ERR_HIP, "vlr_fragpileup_result: the pair offsets of evidence %zu are not ascending", p / 2);
+    // the evidences as the fill pass wrote them: locus and status decide an evidence's pairs
+    std::vector<vlr_indelpileup_hit> hv(ne);
+    VLR_HIP_OK(hipMemcpy(hv.data(), s->d_ev, ne * sizeof(vlr_indelpileup_hit), hipMemcpyDeviceToHost));
+    const vlr_av::Table ht{s->n_loci, s->h_comp_off.data(), s->h_comp_boff.data(), nullptr};
+    // per evidence: its pairs and their bytes (vlr_av::layout_evidence), as running sums
+    std::vector<uint64_t> pb(ne + 1, 0), ex(ne + 1, 0), ey(ne + 1, 0);
+    uint32_t xl[vlr_av::kMaxPairs], yl[vlr_av::kMaxPairs];
+    for (size_t e = 0; e < ne; ++e) {
+        const vlr_indelpileup_hit& h = hv[e];
+        if ((int64_t)h.locus >= s->n_loci) return bfail(VLR_ERR_HIP, "vlr_fragpileup_result: evidence %zu names locus %u of %lld", e, h.locus, (long long)s->n_loci);
+        const uint64_t ref_len = gx[2 * e + 1] - gx[2 * e], alt_len = gx[2 * e + 2] - gx[2 * e + 1], read_len = gy[2 * e + 1] - gy[2 * e];
+        const uint32_t np = vlr_av::layout_evidence(ht, h.locus, h.status == 0, (uint32_t)ref_len, (uint32_t)alt_len, (uint32_t)read_len, xl, yl);
+        uint64_t sx = 0, sy = 0;
+        for (uint32_t j = 0; j < np; ++j) { sx += xl[j]; sy += yl[j]; }
+        pb[e + 1] = pb[e] + np; ex[e + 1] = ex[e] + sx; ey[e + 1] = ey[e] + sy;
+    }
+    // the ranges, and the largest of each quantity over them: the scratch is sized once
+    std::vector<size_t> cut{0};
+    size_t max_ev = 0; uint64_t max_np = 0, max_x = 0, max_y = 0;
+    for (size_t e0 = 0; e0 < ne;) {
+        size_t e1 = e0 + 1;
+        while (e1 < ne && ex[e1 + 1] - ex[e0] <= s->pair_byte_limit && ey[e1 + 1] - ey[e0] <= s->pair_byte_limit) ++e1;
+        if (ex[e1] - ex[e0] >= (1ull << 32) || ey[e1] - ey[e0] >= (1ull << 32) || pb[e1] - pb[e0] >= (1ull << 31))
+            return bfail(VLR_ERR_UNSUPPORTED, "evidence %zu: its windows take 4 GiB or more", e0);
+        max_ev = std::max(max_ev, e1 - e0); max_np = std::max(max_np, pb[e1] - pb[e0]); max_x = std::max(max_x, ex[e1] - ex[e0]); max_y = std::max(max_y, ey[e1] - ey[e0]);
+        cut.push_back(e1);
+        e0 = e1;
+    }
+    const size_t NP = (size_t)max_np;
+    uint32_t *d_pb = nullptr, *d_xoff = nullptr, *d_yoff = nullptr, *d_cxoff = nullptr, *d_cyoff = nullptr, *d_keep = nullptr;
+    int32_t *d_band = nullptr, *d_dist = nullptr, *d_cband = nullptr;
+    uint64_t *d_koff = nullptr, *d_ktotal = nullptr;
+    uint8_t *d_x = nullptr, *d_y = nullptr, *d_q = nullptr, *d_cx = nullptr, *d_cy = nullptr, *d_cq = nullptr;
+    double* d_lnp = nullptr;
+    vlr_fragpileup_alt_hit* d_alt = nullptr;
+    vlr_bam::Buffers scratch;
+    auto body = [&]() -> int {
+        int rc = VLR_OK;
+        hipStream_t st = 0;
+        auto step = [&](int r) { if (rc == VLR_OK) rc = r; };
+        step(scratch.guarded(d_pb, max_ev + 1)); step(scratch.guarded(d_xoff, NP + 1)); step(scratch.guarded(d_yoff, NP + 1));
+        step(scratch.guarded(d_cxoff, NP + 1)); step(scratch.guarded(d_cyoff, NP + 1));
+        step(scratch.guarded(d_keep, 3 * NP)); step(scratch.guarded(d_koff, 3 * NP)); step(scratch.guarded(d_ktotal, 3));
+        step(scratch.guarded(d_band, NP)); step(scratch.guarded(d_dist, NP)); step(scratch.guarded(d_cband, NP)); step(scratch.guarded(d_lnp, NP));
+        step(scratch.guarded(d_x, (size_t)max_x)); step(scratch.guarded(d_y, (size_t)max_y)); step(scratch.guarded(d_q, (size_t)max_y));
+        step(scratch.guarded(d_cx, (size_t)max_x)); step(scratch.guarded(d_cy, (size_t)max_y)); step(scratch.guarded(d_cq, (size_t)max_y));
+        step(scratch.guarded(d_alt, ne));
+        if (rc != VLR_OK) return rc;
+        VLR_HIP_OK(hipMemset(d_alt, 0, ne * sizeof(vlr_fragpileup_alt_hit)));
+        std::vector<uint32_t> hpb, xo, yo;
+        const unsigned wpb = vlr_ip::kThreads / 64;
+        for (size_t c = 0; c + 1 < cut.size(); ++c) {
+            const size_t e0 = cut[c], e1 = cut[c + 1], n = e1 - e0, np = (size_t)(pb[e1] - pb[e0]);
+            hpb.resize(n + 1); xo.assign(np + 1, 0); yo.assign(np + 1, 0);
+            for (size_t e = e0; e < e1; ++e) {
+                const vlr_indelpileup_hit& h = hv[e];
+                const uint32_t k = vlr_av::layout_evidence(ht, h.locus, h.status == 0, (uint32_t)(gx[2 * e + 1] - gx[2 * e]), (uint32_t)(gx[2 * e + 2] - gx[2 * e + 1]),
+                                                           (uint32_t)(gy[2 * e + 1] - gy[2 * e]), xl, yl);
+                const size_t p0 = (size_t)(pb[e] - pb[e0]);
+                hpb[e - e0] = (uint32_t)p0;
+                for (uint32_t j = 0; j < k; ++j) { xo[p0 + j + 1] = xo[p0 + j] + xl[j]; yo[p0 + j + 1] = yo[p0 + j] + yl[j]; }
+            }
+            hpb[n] = (uint32_t)np;
+            double t0 = now_s();
+            VLR_HIP_OK(hipMemcpy(d_pb, hpb.data(), (n + 1) * 4, hipMemcpyHostToDevice));
+            VLR_HIP_OK(hipMemcpy(d_xoff, xo.data(), (np + 1) * 4, hipMemcpyHostToDevice));
+            VLR_HIP_OK(hipMemcpy(d_yoff, yo.data(), (np + 1) * 4, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(frag_alt_expand_kernel, dim3((unsigned)((n + wpb - 1) / wpb)), dim3(vlr_ip::kThreads), 0, st, (uint64_t)n, s->d_ev + e0, s->alt_table(),
+                               s->d_gx + 2 * e0, s->d_gy + 2 * e0, s->d_xb, s->d_yb, s->d_yq, d_pb, d_xoff, d_yoff, d_x, d_y, d_q);
+            vlr_realign_batch_desc b;
+            b.n_pairs = (int64_t)np;
+            b.x_offset = d_xoff; b.x_bases = d_x; b.y_offset = d_yoff; b.y_bases = d_y; b.y_quals = d_q;
+            b.max_edit_dist = nullptr;
+            for (int k = 0; k < 4; ++k) b.gap[k] = s->score.gap[k];
+            hipError_t he = (hipError_t)vlr_launch_edit_kernel(&b, d_dist, nullptr, nullptr, (void*)st);
+            if (he != hipSuccess) return bfail(VLR_ERR_HIP, "edit-distance kernel launch: %s", hipGetErrorString(he));
+            hipLaunchKernelGGL(frag_alt_select_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, (uint64_t)n, d_pb, d_dist, d_xoff, d_yoff,
+                               s->score.mode == VLR_INDELPILEUP_FAST ? 1 : 0, d_keep, d_keep + NP, d_keep + 2 * NP, d_band);
+            hipLaunchKernelGGL(vlr_bam::scan_kernel<uint32_t>, dim3(3), dim3(kScanThreads), 0, st, d_keep, (int64_t)np, (int64_t)NP, d_koff, d_ktotal);
+            uint64_t tot[3] = {0, 0, 0};
+            VLR_HIP_OK(hipMemcpyAsync(tot, d_ktotal, sizeof(tot), hipMemcpyDeviceToHost, st));
+            if ((rc = vlr_ip::sync_stage(st, s->rt[1], t0)) != VLR_OK) return rc;
+            if (tot[0] > np || tot[1] > xo[np] || tot[2] > yo[np]) return bfail(VLR_ERR_HIP, "vlr_fragpileup_result: the compaction keeps more than the range holds");
+            hipLaunchKernelGGL(frag_alt_compact_kernel, dim3((unsigned)((np + wpb - 1) / wpb)), dim3(vlr_ip::kThreads), 0, st, (uint64_t)np, d_keep, d_koff, d_koff + NP,
+                               d_koff + 2 * NP, d_xoff, d_yoff, d_x, d_y, d_q, d_band, tot[0], tot[1], tot[2], d_cxoff, d_cyoff, d_cband, d_cx, d_cy, d_cq);
+            b.n_pairs = (int64_t)tot[0];
+            b.x_offset = d_cxoff; b.x_bases = d_cx; b.y_offset = d_cyoff; b.y_bases = d_cy; b.y_quals = d_cq;
+            b.max_edit_dist = d_cband;
+            if ((rc = vlr_ip::score_hmm(s->score, b, d_lnp, st)) != VLR_OK || (rc = vlr_ip::sync_stage(st, s->rt[2], t0)) != VLR_OK) return rc;
+            hipLaunchKernelGGL(frag_alt_collect_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, (uint64_t)n, (uint64_t)e0, (uint64_t)ne, d_pb,
+                               d_dist, d_koff, d_lnp, tot[0], s->d_ev, d_alt);
+            if ((rc = vlr_ip::sync_stage(st, s->rt[3], t0)) != VLR_OK) return rc;
+            s->n_edit_pairs += (int64_t)np; s->n_hmm_pairs += (int64_t)tot[0];
+            ++s->n_ranges;
         }
-        if ((rc = scratch.guarded(d_norm, 2 * ne)) != VLR_OK) return rc;
-        VLR_HIP_OK(hipMemcpy(d_norm, norm.data(), 2 * ne * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(frag_apply_kernel, dim3((unsigned)((ne + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, s->d_ev, s->d_evm, d_norm, (uint64_t)ne,
-                           std::min<uint64_t>(s->n_members, s->member_cap), s->d_members);
-        if ((rc = vlr_ip::sync_stage(st, s->rt[3], t0)) != VLR_OK) return rc;
+        double t0 = now_s();
+        s->ev.resize(ne); s->alt_hits.resize(ne);
+        VLR_HIP_OK(hipMemcpy(s->ev.data(), s->d_ev, ne * sizeof(vlr_indelpileup_hit), hipMemcpyDeviceToHost));
+        VLR_HIP_OK(hipMemcpy(s->alt_hits.data(), d_alt, ne * sizeof(vlr_fragpileup_alt_hit), hipMemcpyDeviceToHost));
+        if ((rc = apply_pass(s, scratch, st, t0)) != VLR_OK) return rc;
         bool ok = true;
         rc = scratch.guards_intact(&ok);
         if (rc == VLR_OK && !ok) s->status |= VLR_FRAGPILEUP_GUARD_DAMAGED;
@@ -1006,8 +1240,11 @@ int vlr_fragpileup_add_bam(vlr_fragpileup* s, const char* bam_path) {
     if (!s) return vlr_bam::bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_add_bam: null");
     std::function<int(const std::vector<std::string>&)> on_header;
     if (s->realigning) on_header = [s, bam_path](const std::vector<std::string>& names) { return vlr_fp::on_header(s, names, bam_path); };
-    return vlr_bam::add_bam(*s, bam_path, "vlr_fragpileup_add_bam", {&s->t[0], &s->t[1], &s->t[2], &s->t[6], &s->t[5]}, on_header,
-                            [s](vlr_dev_file* df, int64_t n, hipStream_t st) { return vlr_fp::run_chunk(s, df, n, st); });
+    const int rc = vlr_bam::add_bam(*s, bam_path, "vlr_fragpileup_add_bam", {&s->t[0], &s->t[1], &s->t[2], &s->t[6], &s->t[5]}, on_header,
+                                    [s](vlr_dev_file* df, int64_t n, hipStream_t st) { return vlr_fp::run_chunk(s, df, n, st); });
+    // (vlr_fragpileup_set_alt_variants: a file that could not be added and gave no record does not count as the first one)
+    if (rc == VLR_OK || s->n_records > 0) s->bam_added = true;
+    return rc;
 }
 
 int vlr_fragpileup_result(vlr_fragpileup* s, vlr_fragpileup_counts* r) {
@@ -1028,7 +1265,7 @@ int vlr_fragpileup_result(vlr_fragpileup* s, vlr_fragpileup_counts* r) {
         if (s->ev_overflow) s->status |= VLR_FRAGPILEUP_EVIDENCE_OVERFLOW;
         if (!(s->status & (VLR_FRAGPILEUP_MEMBER_OVERFLOW | VLR_FRAGPILEUP_NAME_OVERFLOW | VLR_FRAGPILEUP_KEY_OVERFLOW | VLR_FRAGPILEUP_EVIDENCE_OVERFLOW | VLR_FRAGPILEUP_GUARD_DAMAGED)) &&
             s->n_members && s->n_loci) {
-            if (s->realigning && s->n_ev && (rc = realign_pass(s)) != VLR_OK) return rc;
+            if (s->realigning && s->n_ev && (rc = s->alt_set ? realign_pass_alt(s) : realign_pass(s)) != VLR_OK) return rc;
             if (s->status & VLR_FRAGPILEUP_GUARD_DAMAGED) { s->collected = true; return vlr_fragpileup_result(s, r); }
             const double t0 = now_s();
             rc = fragment_pass(s);
@@ -1109,6 +1346,64 @@ int vlr_fragpileup_open_indel(int device, int64_t n_loci, const int32_t* ref_id,
     // stand in for them rather than a null pointer.  Nothing may read ref_bases of such a session.)
     return open_impl("vlr_fragpileup_open_indel", device, n_loci, ref_id, start, len.data(), kind, alt_bases, alt_bases, 1, window, max_mapq, max_read_len,
                      member_capacity, name_capacity, key_capacity, window_bytes, &ro, out, &io);
+}
+
+int vlr_fragpileup_set_alt_variants(vlr_fragpileup* s, const uint64_t* comp_offset, const uint64_t* comp_base_offset, const uint8_t* comp_bases) {
+    using namespace vlr_fp;
+    const char* api = "vlr_fragpileup_set_alt_variants";
+    if (!s || !comp_offset) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: null", api);
+    if (!s->realigning) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: the session was not opened with vlr_fragpileup_open_realign or vlr_fragpileup_open_indel", api);
+    if (s->alt_set) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: the session has its competitors already", api);
+    if (s->bam_added) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: called after vlr_fragpileup_add_bam", api);
+    // (the offsets are walked only as far as they proved ascending: check_table stops at the first entry that is not)
+    const uint64_t limit = (uint64_t)VLR_FRAGPILEUP_MAX_INDEL_LEN + 2ull * ((uint64_t)s->rl_window * 3 / 2);
+    if (comp_offset[0] != 0) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: comp_offset[0] is not 0", api);
+    for (int64_t l = 0; l < s->n_loci; ++l) {
+        if (comp_offset[l + 1] < comp_offset[l]) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: locus %lld: the competitor offsets descend", api, (long long)l);
+        if (comp_offset[l + 1] - comp_offset[l] > (uint64_t)VLR_FRAGPILEUP_MAX_ALT_VARIANTS)
+            return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: locus %lld has %llu competitors: a session takes at most %d", api, (long long)l,
+                         (unsigned long long)(comp_offset[l + 1] - comp_offset[l]), VLR_FRAGPILEUP_MAX_ALT_VARIANTS);
+    }
+    const uint64_t n_comp = comp_offset[s->n_loci];
+    if (n_comp > 0 && (!comp_base_offset || !comp_bases)) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: null", api);
+    int64_t where = 0;
+    const int bad = n_comp > 0 ? vlr_av::check_table(s->n_loci, comp_offset, comp_base_offset, limit, &where) : 0;
+    if (bad == 3)
+        return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: competitor %lld has a window of %llu bases: a session takes 1 .. %llu", api, (long long)where,
+                     (unsigned long long)(comp_base_offset[where + 1] - comp_base_offset[where]), (unsigned long long)limit);
+    if (bad) return bfail(VLR_ERR_INVALID_ARGUMENT, "%s: competitor %lld: the window offsets descend or do not start at 0", api, (long long)where);
+    VLR_HIP_OK(hipSetDevice(s->device));
+    std::vector<uint64_t> boff(1, 0);
+    if (n_comp) boff.assign(comp_base_offset, comp_base_offset + n_comp + 1);
+    const uint8_t none = 0;
+    int rc;
+    if ((rc = s->buf.upload(s->d_comp_off, comp_offset, (size_t)s->n_loci + 1)) != VLR_OK || (rc = s->buf.upload(s->d_comp_boff, boff.data(), boff.size())) != VLR_OK ||
+        (rc = s->buf.upload(s->d_comp_bases, n_comp ? comp_bases : &none, n_comp ? (size_t)boff[n_comp] : 1)) != VLR_OK)
+        return rc;
+    s->h_comp_off.assign(comp_offset, comp_offset + s->n_loci + 1);
+    s->h_comp_boff = boff;
+    s->alt_limit = limit;
+    for (int64_t l = 0; l < s->n_loci; ++l) if (comp_offset[l + 1] > comp_offset[l]) ++s->n_loci_with_comp;
+    s->alt_set = true;
+    return VLR_OK;
+}
+
+int vlr_fragpileup_alt_result(vlr_fragpileup* s, vlr_fragpileup_alt_counts* r) {
+    using namespace vlr_fp;
+    if (!s || !r || !s->collected || !s->alt_set) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_alt_result: call vlr_fragpileup_result on a session with vlr_fragpileup_set_alt_variants first");
+    r->n_edit_pairs = s->n_edit_pairs;
+    r->n_hmm_pairs = s->n_hmm_pairs;
+    r->n_competitors = (int64_t)s->h_comp_off[(size_t)s->n_loci];
+    r->n_loci_with_competitors = s->n_loci_with_comp;
+    return VLR_OK;
+}
+
+int vlr_fragpileup_read_alt_variants(vlr_fragpileup* s, vlr_fragpileup_alt_hit* out, int64_t n) {
+    using namespace vlr_fp;
+    if (!s || !s->collected || !s->alt_set) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_read_alt_variants: call vlr_fragpileup_result on a session with vlr_fragpileup_set_alt_variants first");
+    if (n != (int64_t)s->alt_hits.size() || (n > 0 && !out)) return bfail(VLR_ERR_INVALID_ARGUMENT, "vlr_fragpileup_read_alt_variants: size differs from vlr_fragpileup_realign_result");
+    if (n) memcpy(out, s->alt_hits.data(), (size_t)n * sizeof(vlr_fragpileup_alt_hit));
+    return VLR_OK;
 }
 
 int vlr_fragpileup_read_indel(vlr_fragpileup* s, vlr_fragpileup_indel_obs* extra_obs, int64_t n_obs, vlr_fragpileup_indel_locus* extra_loci, int64_t n_loci) {

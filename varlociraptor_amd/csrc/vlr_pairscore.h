@@ -183,4 +183,15 @@ inline int score_pairs(const ScoreParams& sp, size_t np, const uint32_t* d_xoff,
     return sync_stage(st, t_hmm, t0);
 }
 
+// The pair HMM of the mode alone, over a batch whose bands are already set (a session with competitors: the edit distances of all pairs
+// are taken first, and only the pairs its select pass keeps come here).  Not synchronised.
+inline int score_hmm(const ScoreParams& sp, const vlr_realign_batch_desc& b, double* d_lnp, hipStream_t st) {
+    hipError_t e;
+    if (sp.mode == VLR_INDELPILEUP_FAST) e = (hipError_t)vlr_launch_pathhmm_kernel(&b, d_lnp, (void*)st);
+    else if (sp.mode == VLR_INDELPILEUP_HOMOPOLYMER) e = (hipError_t)vlr_launch_homopoly_kernel(&b, sp.hop, d_lnp, (void*)st);
+    else e = (hipError_t)vlr_launch_realign_kernel(&b, d_lnp, (void*)st);
+    if (e != hipSuccess) return vlr_bam::bfail(VLR_ERR_HIP, "realign kernel launch: %s", hipGetErrorString(e));
+    return VLR_OK;
+}
+
 }  // namespace vlr_ip

@@ -28,7 +28,7 @@ EXPORTS = sorted(abi.SIGNATURES)  # every function include/vlr.h declares
 SOURCES = tuple("csrc/" + f for f in (
     "vlr_kernels.hip", "vlr_kernels_lean.hip", "vlr_kernels_deep.hip", "vlr_kernels_wide.hip", "vlr_kernels_widedeep.hip", "vlr_realign.hip",
     "vlr_fdr.hip", "vlr_contam.hip", "vlr_callstats.hip", "vlr_bamstats.hip", "vlr_basepileup.hip", "vlr_indelpileup.hip", "vlr_fragpileup.hip", "vlr_inflate.hip", "vlr_decode.hip", "vlr_host.cpp", "vlr_bgzf.cpp", "vlr_ingest.cpp", "vlr_callsfile.cpp",
-    "vlr_plan.h", "vlr_gpuio.h", "vlr_callstats.h", "vlr_bamstream.h", "vlr_bamsession.h", "vlr_basepileup.h", "vlr_indelpileup.h", "vlr_fragpileup.h", "vlr_methylation.h", "vlr_pairscore.h", "vlr_hostio.h")) + ("../include/vlr.h", "../include/vlr_detmath.h")
+    "vlr_plan.h", "vlr_gpuio.h", "vlr_callstats.h", "vlr_bamstream.h", "vlr_bamsession.h", "vlr_basepileup.h", "vlr_indelpileup.h", "vlr_fragpileup.h", "vlr_methylation.h", "vlr_pairscore.h", "vlr_altvariants.h", "vlr_hostio.h")) + ("../include/vlr.h", "../include/vlr_detmath.h")
 
 
 class EngineError(RuntimeError):

@@ -31,12 +31,14 @@ alt allele window = readwindows.substitution_locus, edit distance / band / pair 
 strand = the record's when the supports differ, else none; no read position, no third-allele evidence.  device="cpu" scores the windows
 with the CPU restatement of the pair HMMs under oracle/, a device number with the kernels (vlr_fragpileup_open_realign in one pass over
 the BAM; loci finished on the host through realign.best_hits / prob_related*).  NOT mirrored there: the read-inferred third allele
-(mod.rs:317-348: needs the Myers traceback of the `bio` crate, which the reference does not vendor), `alt_variants`
-(--atomic-candidate-variants stays required, so an MNV is realigned only for an indel operation), `homopolymer_indel_len`.  Refused,
+(mod.rs:317-348: needs the Myers traceback of the `bio` crate, which the reference does not vendor), `homopolymer_indel_len`.  The
+other alleles of a locus (`alt_variants`) are scored against on request (`alt_variants=True`, --alt-variants: the section "the other
+alleles of a locus" below); --atomic-candidate-variants has nothing to do with them: in the reference that flag only switches off the
+realignment of SNV / MNV candidates (preprocessing/mod.rs:511, 535), the other alleles are collected either way (587-613).  Refused,
 with the record's ordinal: a CIGAR that begins with N (read_pos fails) and a record that needs realignment and carries an SI:Z tag
 (strand information over an interval, mod.rs:381-387).
 
-NOT mirrored (callers must know): `alt_variants`; without a RealignSpec the realignment (with realign_indel_reads=True such
+NOT mirrored (callers must know): without a RealignSpec the realignment (with realign_indel_reads=True such
 observations come back flagged NEEDS_REALIGN and `observations` raises), `max_depth` subsampling (the `rand` crate's StdRng),
 `report_fragment_ids` (None), replacement / SV / breakend candidates, haplotype blocks.  Deletion and insertion candidates
 are built on request (`indel_candidates`, --indel-candidates): the section "deletion and insertion candidates" below has their rule
@@ -272,6 +274,8 @@ def is_member(rec: BamRecord, loc: Locus, window: int) -> bool:
 def _support(rec: BamRecord, loc: Locus, li: int, ordinal: int, t: Tables, realign_indel_reads: bool, realigned: Optional[Dict] = None) -> Optional[Hit]:
     """allele_support_per_read; what the reference raises comes back as the hit's status.  `realigned`: {(ordinal, locus): Hit} of the
     records that were realigned"""
+    if realigned is not None and (ordinal, li) in realigned and not basecalls.contains_indel_op(rec):
+        return realigned[(ordinal, li)]        # mnv.rs:83: an MNV with other alleles at its locus realigns every enclosing record
     try:
         h = basecalls.allele_support(rec, loc, li, ordinal, t, realign_indel_reads)
         if h is not None and h.status & NEEDS_REALIGN and realigned is not None:
@@ -378,6 +382,9 @@ class RealignEvidence:
     ln_alt: float = -math.inf
     dist_ref: int = -1
     dist_alt: int = -1
+    winner: int = 0                  # with competitors (alt_variants): the reference-side allele that gave ln_ref, 0 = the reference
+    n_tied: int = 0                  # reference-side alleles at the minimum edit distance
+    n_ref_side_hits: int = 0         # reference-side alleles with a hit
 
     def key(self):
         return (self.locus,) + self.ev.key()
@@ -453,6 +460,144 @@ def score_pairs(pb, spec: RealignSpec, device="cpu"):
     return dist, lnp
 
 
+# ---------------------------------------------------------------------------------------------- the other alleles of a locus
+# `alt_variants` of the reference (csrc/vlr_altvariants.h states the rule for the kernels; this is the same in Python):
+#   the competitors of a candidate      utils/variant_buffer.rs:203-222: the other variants at its (CHROM, POS), the ones before it in
+#                                       the file, then the ones after it (`alt_variant_groups`); they are collected with or without
+#                                       --atomic-candidate-variants (preprocessing/mod.rs:587-613)
+#   a competitor's allele window        its own alt allele window (`competitor_window`): alt_emission_params of snv.rs:158-178,
+#                                       mnv.rs:213-234, deletion.rs:121-141 and insertion.rs:74-98 all ignore the region interval they
+#                                       are handed, so the window does not depend on the evidence
+#   the reference side of an evidence   realignment/mod.rs:250-292 with prob_allele (426-479): edit distances of the reference (i = 0)
+#                                       and the competitors (i = 1 .. K); alleles without a hit are out; the ones at the minimum are
+#                                       the tied set; only they are scored by the pair HMM; the largest score wins, the lowest i on
+#                                       equal scores (`p > prob`) (`score_alt_evidences`)
+#   which reads are realigned           every member of an indel candidate; under a RealignSpec the reads of an SNV with an I / D
+#                                       operation (snv.rs:76) and the reads of an MNV with one OR any enclosing read when the MNV
+#                                       has a competitor (mnv.rs:83)
+MAX_ALT_VARIANTS = abi.FRAGPILEUP_MAX_ALT_VARIANTS
+
+
+def alt_variant_groups(rows) -> List[List[int]]:
+    """Per row of `rows` ((CHROM, POS, ...) tuples in file order, as read_candidates gives them) the indices of its competitors: the
+    other rows of its run of consecutive rows with equal (CHROM, POS), the ones before it, then the ones after it.  More than
+    MAX_ALT_VARIANTS competitors are refused, the locus named."""
+    out: List[List[int]] = []
+    k, n = 0, len(rows)
+    while k < n:
+        j = k
+        while j < n and (rows[j][0], rows[j][1]) == (rows[k][0], rows[k][1]):
+            j += 1
+        if j - k - 1 > MAX_ALT_VARIANTS:
+            raise PreprocessError("locus %s:%s has %d candidate alleles: at most %d other alleles of a locus are scored against (alt_variants)"
+                                  % (rows[k][0], rows[k][1], j - k, MAX_ALT_VARIANTS))
+        for i in range(k, j):
+            out.append(list(range(k, i)) + list(range(i + 1, j)))
+        k = j
+    return out
+
+
+def competitor_window(seq: bytes, pos: int, ref: bytes, alt: bytes, window: int) -> bytes:
+    """the alt allele window of the candidate `ref` > `alt` at 0-based `pos` of the contig `seq` as a session builds it for that
+    candidate itself: readwindows.substitution_locus (SNV / MNV) or readwindows.indel_locus (deletion / insertion)"""
+    from . import readwindows as rw
+    loc = rw.substitution_locus(seq.upper(), pos, ref, alt, window) if len(ref) == len(alt) else rw.indel_locus(seq.upper(), pos, ref, alt, window)
+    if loc.kind == "replacement":
+        raise PreprocessError("a replacement allele (%s>%s at position %d) cannot compete: replacements are not built" % (bytes(ref).decode(), bytes(alt).decode(), pos + 1))
+    return bytes(loc.alt_allele)
+
+
+def select_alleles(dist: Sequence[int]):
+    """prob_allele's first loop over the reference side: dist[i] of the reference (i = 0) and the competitors, -1 = no hit.
+    (minimum distance or -1, the tied alleles ascending, the number of alleles with a hit)"""
+    hits = [d for d in dist if d >= 0]
+    if not hits:
+        return -1, [], 0
+    m = min(hits)
+    return m, [i for i, d in enumerate(dist) if d == m], len(hits)
+
+
+def pair_edit_distances(pb, device="cpu") -> np.ndarray:
+    """the edit distance of every pair of a realign.PairBatch (-1: an empty window, no hit)"""
+    from . import realign
+    if len(pb) == 0:
+        return np.zeros(0, np.int32)
+    if device != "cpu":
+        return np.asarray(realign.best_hits(pb, int(device))[0], np.int32)
+    from oracle import oracle
+    oracle.build()
+    return np.array([oracle.edit_distance(x, y)[0] if x and y else -1 for x, y in zip(pb.x, pb.y)], np.int32)
+
+
+def pair_hmm(pb, dist: Sequence[int], spec: RealignSpec, device="cpu") -> np.ndarray:
+    """ln P of every pair of a realign.PairBatch whose edit distances are `dist`, in the spec's mode, with the bands score_pairs sets"""
+    from . import realign
+    gap = spec.gap or realign.GapParams()
+    n = len(pb)
+    if n == 0:
+        return np.zeros(0)
+    if spec.mode != "fast":
+        pb.band = [int(x) + realign.EDIT_BAND if x >= 0 else -1 for x in dist]
+    if device != "cpu":
+        if spec.mode == "fast":
+            return realign.prob_best_path(pb, gap, int(device))
+        if spec.mode == "homopolymer":
+            return realign.prob_related_homopolymer(pb, gap, spec.hop or realign.HopParams(), int(device))
+        return realign.prob_related(pb, gap, int(device))
+    from oracle import oracle
+    oracle.build()
+    g = [gap.prob_insertion_artifact, gap.prob_deletion_artifact, gap.prob_insertion_extend_artifact, gap.prob_deletion_extend_artifact]
+    lnp = np.full(n, -math.inf)
+    for k in range(n):
+        x, y, q = pb.x[k], pb.y[k], pb.q[k]
+        if not x or not y:
+            continue
+        if spec.mode == "fast":
+            lnp[k] = oracle.pathhmm_best(x, y, q, g)
+        elif spec.mode == "homopolymer":
+            lnp[k] = oracle.homopoly_prob_related(x, y, q, g, (spec.hop or realign.HopParams()).as_list(), pb.band[k])
+        else:
+            lnp[k] = oracle.pairhmm_prob_related(x, y, q, g, pb.band[k])
+    return lnp
+
+
+def score_alt_evidences(evs: Sequence[RealignEvidence], competitors: Sequence[Sequence[bytes]], spec: RealignSpec, device="cpu") -> Tuple[int, int]:
+    """Scores `evs` in place against the reference, their alt allele and the competitor windows of their loci (competitors[locus]):
+    ln_ref / dist_ref from the winner of the tied set, ln_alt / dist_alt as ever, winner, n_tied, n_ref_side_hits.  Returns (pairs
+    through the edit distance, pairs through the pair HMM): only the tied set and the alt pair are scored by the pair HMM."""
+    from .realign import PairBatch
+    pb, first = PairBatch(), []
+    for e in evs:            # pair 0 = ref, pair 1 = alt, pair 1 + i = competitor i (an evidence with a status: empty windows)
+        first.append(len(pb))
+        pb.add(e.ev.ref_allele, e.ev.read_window, e.ev.quals, -1)
+        pb.add(e.alt_allele, e.ev.read_window, e.ev.quals, -1)
+        for w in competitors[e.locus]:
+            pb.add(w if not e.ev.status else b"", e.ev.read_window, e.ev.quals, -1)
+    dist = pair_edit_distances(pb, device)
+    kept, kb, sel = [], PairBatch(), []
+    for e, p0 in zip(evs, first):
+        k = len(competitors[e.locus])
+        m, tied, n_hits = select_alleles([int(dist[p0])] + [int(dist[p0 + 1 + i]) for i in range(1, k + 1)])
+        pairs = [p0 if i == 0 else p0 + 1 + i for i in (tied or [0])]           # (no hit at all: the reference's pair, as without competitors)
+        sel.append((m, tied, n_hits, len(kept), pairs))
+        for p in sorted(pairs + [p0 + 1]):
+            kept.append(p)
+            kb.add(pb.x[p], pb.y[p], pb.q[p], -1)
+    lnp = pair_hmm(kb, [int(dist[p]) for p in kept], spec, device)
+    at = {}
+    for c, p in enumerate(kept):
+        at[p] = c
+    for e, p0, (m, tied, n_hits, _, pairs) in zip(evs, first, sel):
+        best, winner = None, 0
+        for i, p in zip(tied or [0], pairs):
+            v = float(lnp[at[p]])
+            if best is None or v > best:
+                best, winner = v, i
+        e.ln_ref, e.dist_ref, e.ln_alt, e.dist_alt = best, m, float(lnp[at[p0 + 1]]), int(dist[p0 + 1])
+        e.winner, e.n_tied, e.n_ref_side_hits = winner, len(tied), n_hits
+    return len(pb), len(kept)
+
+
 def realigned_hit(e: RealignEvidence, rec: BamRecord) -> Hit:
     """the member support of a realigned evidence (csrc/vlr_fragpileup.h `apply_realigned`)"""
     from . import readwindows as rw
@@ -468,19 +613,23 @@ def realigned_hit(e: RealignEvidence, rec: BamRecord) -> Hit:
 
 
 def realign_members(good: Sequence[Tuple[int, BamRecord]], loci: Sequence[Locus], which: Sequence[int], props: Props, spec: RealignSpec, ref_seqs: Dict[int, bytes],
-                    device="cpu"):
+                    device="cpu", competitors: Optional[Sequence[Sequence[bytes]]] = None):
     """(evidences record-major, loci ascending within a record; {(ordinal, locus): Hit}) of the members of the loci `which` (ascending)
-    that need realignment"""
+    that need realignment.  `competitors`: per locus the allele windows of the other candidates at its position (alt_variants)."""
     evs: List[RealignEvidence] = []
     recs: List[BamRecord] = []
     for o, rec in good:
-        if not basecalls.contains_indel_op(rec):
-            continue
+        indel = basecalls.contains_indel_op(rec)
         for li in which:
             loc = loci[li]
+            if not indel and not (competitors is not None and len(loc.ref) > 1 and competitors[li]):      # snv.rs:76, mnv.rs:83
+                continue
             if is_member(rec, loc, props.window) and basecalls.enclosing(rec, loc):
                 evs.append(realign_evidence(rec, loc, li, o, ref_seqs[loc.ref_id], spec.window))
                 recs.append(rec)
+    if competitors is not None:
+        score_alt_evidences(evs, competitors, spec, device)
+        return evs, {(e.ev.record, e.locus): realigned_hit(e, rec) for e, rec in zip(evs, recs)}
     dist, lnp = score_pairs(evidence_pair_batch(evs), spec, device)
     hits = {}
     for k, (e, rec) in enumerate(zip(evs, recs)):
@@ -491,10 +640,11 @@ def realign_members(good: Sequence[Tuple[int, BamRecord]], loci: Sequence[Locus]
 
 def restate(records: Sequence[BamRecord], loci: Sequence[Locus], props: Props, t: Tables = basecalls.TABLES, realign_indel_reads: bool = False,
             first_ordinal: int = 0, only: Optional[Sequence[int]] = None, realign: Optional[RealignSpec] = None, ref_seqs: Optional[Dict[int, bytes]] = None,
-            device="cpu", rule=None) -> Restated:
+            device="cpu", rule=None, competitors: Optional[Sequence[Sequence[bytes]]] = None) -> Restated:
     """The observations of every locus (`only`: of these loci) from `records` in file order.  `realign`: indel-bearing reads are
     realigned (realign_indel_reads is implied) against `ref_seqs` {ref_id: contig, upper case}, scored on `device`.  `rule`: the loci
-    are of another candidate kind (methylation.Rule with methylation.MethLocus)."""
+    are of another candidate kind (methylation.Rule with methylation.MethLocus).  `competitors` (with `realign`): per locus the allele
+    windows of the other candidates at its position (alt_variants)."""
     out = Restated([[] for _ in loci], [0] * len(loci), len(records), props.max_read_len)
     good = []
     for k, rec in enumerate(records):
@@ -510,7 +660,7 @@ def restate(records: Sequence[BamRecord], loci: Sequence[Locus], props: Props, t
         if ref_seqs is None:
             raise ValueError("realignment needs the contigs of the loci (ref_seqs)")
         realign_indel_reads = True
-        out.evidences, realigned = realign_members(good, loci, sorted(which), props, realign, ref_seqs, device)
+        out.evidences, realigned = realign_members(good, loci, sorted(which), props, realign, ref_seqs, device, competitors)
     for li in which:
         loc = loci[li]
         members = [(o, r) for o, r in good if is_member(r, loc, props.window)]
@@ -525,11 +675,45 @@ def _capacities(n: int, member_capacity, name_capacity, key_capacity):
             int(key_capacity) if key_capacity is not None else max(1 << 16, 256 * n))
 
 
-def _session(L, open_call, args_of, caps, bams, retry: bool, realigning: bool, read):
+def competitor_arrays(competitors: Sequence[Sequence[bytes]]):
+    """(comp_offset u64[n_loci + 1], comp_base_offset u64[n_comp + 1], the window bytes) of per-locus competitor windows, as
+    vlr_fragpileup_set_alt_variants takes them"""
+    off = np.zeros(len(competitors) + 1, np.uint64)
+    off[1:] = np.cumsum([len(c) for c in competitors])
+    flat = [bytes(w) for c in competitors for w in c]
+    boff = np.zeros(len(flat) + 1, np.uint64)
+    boff[1:] = np.cumsum([len(w) for w in flat])
+    return off, boff, np.frombuffer(b"".join(flat) or b"\0", np.uint8).copy()
+
+
+def _set_alt_variants(L, competitors):
+    """the after_open of a session with competitors"""
+    from . import engine
+    arrays = competitor_arrays(competitors)
+
+    def after_open(h):
+        engine._check(L.vlr_fragpileup_set_alt_variants(h, *(a.ctypes.data for a in arrays)))
+    return after_open
+
+
+def _read_alt(L, h, n_evidences: int):
+    """(abi.FRAGPILEUP_ALT_HIT_DTYPE per evidence, abi.FragPileupAltCounts) of a collected session with competitors"""
+    import ctypes as C
+    from . import engine
+    ah = np.zeros(n_evidences, abi.FRAGPILEUP_ALT_HIT_DTYPE)
+    ac = abi.FragPileupAltCounts()
+    engine._check(L.vlr_fragpileup_alt_result(h, C.byref(ac)))
+    if n_evidences:
+        engine._check(L.vlr_fragpileup_read_alt_variants(h, ah.ctypes.data, n_evidences))
+    return ah, ac
+
+
+def _session(L, open_call, args_of, caps, bams, retry: bool, realigning: bool, read, after_open=None):
     """One fragment session run to its result: open_call(*args_of(member, name, key, evidence capacity), the handle), every BAM added,
     abi.FragPileupCounts (and abi.FragPileupRealignCounts of a `realigning` session) read, FragPileupError for damaged guards; an
     overflow of a capacity is retried once with the needed ones while `retry`; then what read(handle, counts, realign counts, fits)
-    returns — fits: no capacity overflowed.  The session is closed whatever happens."""
+    returns — fits: no capacity overflowed.  `after_open(handle)` runs before the first BAM is added.  The session is closed whatever
+    happens."""
     import ctypes as C
     from . import engine
     mcap, ncap, kcap, ecap = caps
@@ -537,6 +721,8 @@ def _session(L, open_call, args_of, caps, bams, retry: bool, realigning: bool, r
         h = C.c_void_p()
         engine._check(open_call(*args_of(mcap, ncap, kcap, ecap), C.byref(h)))
         try:
+            if after_open is not None:
+                after_open(h)
             for b in [bams] if isinstance(bams, str) else bams:
                 engine._check(L.vlr_fragpileup_add_bam(h, b.encode()))
             res = abi.FragPileupCounts()
@@ -560,16 +746,20 @@ def _session(L, open_call, args_of, caps, bams, retry: bool, realigning: bool, r
 def device_observations(bams, loci: Sequence[Locus], props: Props, device: int = 0, realign_indel_reads: bool = False, member_capacity: Optional[int] = None,
                         name_capacity: Optional[int] = None, window_bytes: int = 0, retry: bool = True, key_capacity: Optional[int] = None,
                         realign: Optional[RealignSpec] = None, fasta: Optional[str] = None, evidence_capacity: Optional[int] = None, pair_byte_limit: int = 0,
-                        evidences: bool = False):
+                        evidences: bool = False, competitors: Optional[Sequence[Sequence[bytes]]] = None):
     """(observations as abi.FRAGPILEUP_OBS_DTYPE, locus records as abi.FRAGPILEUP_LOCUS_DTYPE, abi.FragPileupCounts) from the kernels.
     `bams`: a path or several (one record stream: a pair may straddle two files); `loci` sorted by (ref_id, start), MNVs of at most
     basecalls.MAX_LEN bases.  An overflow of a capacity is retried once with the needed ones unless retry=False.
     `realign` (with `fasta`): indel-bearing reads are realigned in the same pass (vlr_fragpileup_open_realign; realign_indel_reads is
     implied); evidences=True adds (the realigned evidences as abi.INDELPILEUP_HIT_DTYPE, record-major; abi.FragPileupRealignCounts) to
-    the result."""
+    the result.  `competitors` (with `realign`): per locus the allele windows of the other candidates at its position
+    (vlr_fragpileup_set_alt_variants); with evidences=True the result then also has (abi.FRAGPILEUP_ALT_HIT_DTYPE per evidence,
+    abi.FragPileupAltCounts)."""
     from . import engine
     L = engine.lib()
     n = len(loci)
+    if competitors is not None and realign is None:
+        raise ValueError("competitors need a RealignSpec: without realignment the other alleles of a locus have no effect")
     arrays = basecalls.locus_arrays(loci)
     head = (int(device), n) + tuple(a.ctypes.data for a in arrays) + (int(bool(realign_indel_reads or realign is not None)), int(props.window), int(props.max_mapq),
                                                                      int(props.max_read_len))
@@ -597,8 +787,11 @@ def device_observations(bams, loci: Sequence[Locus], props: Props, device: int =
         ev = np.zeros(int(rres.n_evidences), abi.INDELPILEUP_HIT_DTYPE)
         if realign is not None and len(ev):    # (not under `fits`, unlike the indel session's: after an overflow a session reports no evidences)
             engine._check(L.vlr_fragpileup_read_realigned(h, ev.ctypes.data, len(ev)))
+        if competitors is not None:
+            return (obs, loc, res, ev, rres) + _read_alt(L, h, len(ev))
         return obs, loc, res, ev, rres
-    return _session(L, L.vlr_fragpileup_open if realign is None else L.vlr_fragpileup_open_realign, args_of, caps, bams, retry, realign is not None, read)
+    return _session(L, L.vlr_fragpileup_open if realign is None else L.vlr_fragpileup_open_realign, args_of, caps, bams, retry, realign is not None, read,
+                    _set_alt_variants(L, competitors) if competitors is not None else None)
 
 
 def _locus_slices(bam: str, res, lrec):
@@ -740,17 +933,31 @@ class _Inputs:
 def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, bytes]], props, device=0, omit_mapq_adjustment: bool = False,
                  realign_indel_reads: bool = False, window_bytes: int = 0, realign: Optional[RealignSpec] = None,
                  indel_candidates: Optional[RealignSpec] = None, indel_props: Optional[IndelProps] = None, _inputs: Optional["_Inputs"] = None,
-                 methylation_readtype: Optional[str] = None) -> List[ObsTable]:
+                 methylation_readtype: Optional[str] = None, alt_variants: bool = False, _competitors=None) -> List[ObsTable]:
     """Per candidate (contig, 0-based position, REF, ALT), in the order given, its processed pileup.  device="cpu": the restatement; a
     device number: the kernels, finished as the module header says.  `realign`: indel-bearing reads are realigned (module header);
     realign_indel_reads=True without it raises NeedsRealign for such a read.  `indel_candidates`: deletion / insertion candidates
     (REF and ALT of different lengths) are built, every member realigned with this spec, through the indel session (`indel_tables`;
     `indel_props`: what they need of the alignment properties, default: read from `props`); the SNV / MNV candidates of the same call
     go the way they always went.  `methylation_readtype` ("converted" / "annotated"): candidates with ALT <METH> are built through the
-    methylation session (methylation.tables); the other candidates of the same call go the way they always went."""
+    methylation session (methylation.tables); the other candidates of the same call go the way they always went.  `alt_variants`: every
+    realigned read is scored against the other candidates at its candidate's position too (the section "the other alleles of a locus"
+    above): consecutive candidates with equal (contig, position) form a group."""
     bams = [bam] if isinstance(bam, str) else list(bam)
     inp = _inputs if _inputs is not None else _Inputs(bams, fasta)      # (read once, shared by the SNV / MNV and the indel part of a mixed call)
     seqs, tid = inp.seqs, inp.tid
+    comp = _competitors             # per candidate the (contig, position, REF, ALT) of its competitors; None: no alt_variants
+    if alt_variants and comp is None:
+        comp = [[candidates[j] for j in g] for g in alt_variant_groups(candidates)]
+        for c, g in zip(candidates, comp):
+            if g and any(bytes(x[3]).startswith(b"<") for x in [c] + g):
+                raise PreprocessError("locus %s:%d has a symbolic allele beside other candidates: symbolic alleles do not compete (alt_variants)" % (c[0], c[1] + 1))
+
+    def windows(ks, window):
+        """the competitor windows of the candidates `ks`, for a session that realigns with `window`"""
+        if comp is None:
+            return None
+        return [[competitor_window(seqs[c], int(pos), ref, alt, window) for c, pos, ref, alt in comp[k]] for k in ks]
     meth = [k for k, c in enumerate(candidates) if bytes(c[3]) == b"<METH>"]
     if meth:
         from . import methylation
@@ -761,7 +968,7 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
         out: List[Optional[ObsTable]] = [None] * len(candidates)
         if rest:
             for k, tab in zip(rest, observations(bam, fasta, [candidates[k] for k in rest], props, device, omit_mapq_adjustment, realign_indel_reads, window_bytes, realign,
-                                                 indel_candidates, indel_props, _inputs=inp)):
+                                                 indel_candidates, indel_props, _inputs=inp, _competitors=[comp[k] for k in rest] if comp is not None else None)):
                 out[k] = tab
         loci = []
         for k in meth:
@@ -782,7 +989,7 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
         out: List[Optional[ObsTable]] = [None] * len(candidates)
         if rest:
             for k, tab in zip(rest, observations(bam, fasta, [candidates[k] for k in rest], props, device, omit_mapq_adjustment, realign_indel_reads, window_bytes, realign,
-                                                 _inputs=inp)):
+                                                 _inputs=inp, _competitors=[comp[k] for k in rest] if comp is not None else None)):
                 out[k] = tab
         sites, what = [], []
         for k in ind:
@@ -793,7 +1000,7 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
             sites.append(indel_site(seqs[c], tid[c], int(pos), ref, alt, indel_candidates.window, what[-1]))
         ref_seqs = {tid[c]: seqs[c].upper() for c in set(candidates[k][0] for k in ind)}
         for k, tab in zip(ind, indel_tables(bams, fasta, sites, what, props_of(props), ip, indel_candidates, device, omit_mapq_adjustment, window_bytes, ref_seqs,
-                                           records=inp.records)):
+                                           records=inp.records, competitors=windows(ind, indel_candidates.window))):
             out[k] = tab
         return out
     props = props_of(props)
@@ -806,9 +1013,12 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
     order = sorted(range(len(loci)), key=lambda k: (loci[k].ref_id, loci[k].start))
     records = inp.records
     out: List[Optional[ObsTable]] = [None] * len(loci)
+    # (without a RealignSpec the other alleles of an SNV / MNV locus have no effect: snv.rs:87-143 never looks at them)
+    cw = windows(range(len(loci)), realign.window) if realign is not None else None
     if device == "cpu":
         t = basecalls.TABLES
-        rs = restate(records(), [loci[k] for k in order], props, t, realign_indel_reads, realign=realign, ref_seqs=ref_seqs)
+        rs = restate(records(), [loci[k] for k in order], props, t, realign_indel_reads, realign=realign, ref_seqs=ref_seqs,
+                     competitors=[cw[k] for k in order] if cw is not None else None)
         if rs.bad_records:
             raise FragPileupError("%s: record %d is malformed" % (bams[0], rs.bad_records[0]))
         for j, k in enumerate(order):
@@ -816,14 +1026,16 @@ def observations(bam, fasta: str, candidates: Sequence[Tuple[str, int, bytes, by
         return out
     t = basecalls.library_tables()
     short = [k for k in order if len(loci[k].ref) <= basecalls.MAX_LEN]
-    arr, lrec, res = device_observations(bams, [loci[k] for k in short], props, int(device), realign_indel_reads, window_bytes=window_bytes, realign=realign, fasta=fasta)
+    arr, lrec, res = device_observations(bams, [loci[k] for k in short], props, int(device), realign_indel_reads, window_bytes=window_bytes, realign=realign, fasta=fasta,
+                                         competitors=[cw[k] for k in short] if cw is not None else None)[:3]
     flagged, slices = _locus_slices(bams[0], res, lrec)
     host = [k for k in order if len(loci[k].ref) > basecalls.MAX_LEN] + [short[j] for j in flagged]
     for j, sl in slices:
         mj = int(lrec[j]["major_read_position"])
         out[short[j]] = table_of(obs_from_array(arr[sl]), props, t, omit_mapq_adjustment, None if mj == abi.BASEPILEUP_NO_READ_POSITION else mj)
     if host:
-        rs = restate(records(), [loci[k] for k in host], props, t, realign_indel_reads, realign=realign, ref_seqs=ref_seqs, device=int(device))
+        rs = restate(records(), [loci[k] for k in host], props, t, realign_indel_reads, realign=realign, ref_seqs=ref_seqs, device=int(device),
+                     competitors=[cw[k] for k in host] if cw is not None else None)
         for j, k in enumerate(host):
             out[k] = table_of(rs.per_locus[j], props, t, omit_mapq_adjustment)
     return out
@@ -896,7 +1108,8 @@ def pileup(tables: Sequence[ObsTable], candidates: Sequence[Tuple[str, int, byte
 # The kernels (vlr_fragpileup_open_indel) give members, evidences, fragments with the validity rule, insert sizes, read lengths and
 # the per-locus CIGAR maxima; `isize_support`, `prob_sample_alt` and the running maxima need libm and are these functions on both
 # paths, so the two agree with ==.  Phi is 0.5 erfc(-x / sqrt 2) from libm where the reference calls GSL's ugaussian_P: unpinned.
-# NOT mirrored: the read-inferred third allele, alt_variants, homopolymer_indel_len and the two prob_observable_at_homopolymer_*
+# The other alleles of a locus (alt_variants): on request, the section "the other alleles of a locus" above.
+# NOT mirrored: the read-inferred third allele, homopolymer_indel_len and the two prob_observable_at_homopolymer_*
 # fields (none: the Myers traceback of the `bio` crate), max_depth subsampling, report_fragment_ids, replacements, SVs, breakends,
 # deletions with more than one fetch, and — in a file that mixes candidates — what records that are members of SNV / MNV candidates
 # only would add to the running maxima.
@@ -1211,9 +1424,10 @@ class IndelRestated:
 
 
 def restate_indel(records: Sequence[BamRecord], sites: Sequence[IndelSite], props: Props, has_insert_size: bool, spec: RealignSpec, ref_seqs: Dict[int, bytes],
-                  device="cpu", first_ordinal: int = 0) -> IndelRestated:
+                  device="cpu", first_ordinal: int = 0, competitors: Optional[Sequence[Sequence[bytes]]] = None) -> IndelRestated:
     """The fragment observations of deletion / insertion loci (sorted by (ref_id, start)) from `records` in file order, before the
-    host-side terms: what the indel session of the kernels computes, restated."""
+    host-side terms: what the indel session of the kernels computes, restated.  `competitors`: per site the allele windows of the
+    other candidates at its position (alt_variants)."""
     out = IndelRestated([[] for _ in sites], [0] * len(sites), [(0, 0, (0, 0))] * len(sites), [], len(records))
     good = []
     for k, rec in enumerate(records):
@@ -1229,11 +1443,15 @@ def restate_indel(records: Sequence[BamRecord], sites: Sequence[IndelSite], prop
             if is_member(rec, site, props.window):
                 out.evidences.append(indel_evidence(rec, site, li, o, ref_seqs[site.ref_id], spec.window))
                 recs_of.append(rec)
-    dist, lnp = score_pairs(evidence_pair_batch(out.evidences), spec, device)
     hits = {}
-    for k, (e, rec) in enumerate(zip(out.evidences, recs_of)):
-        e.ln_ref, e.ln_alt, e.dist_ref, e.dist_alt = float(lnp[2 * k]), float(lnp[2 * k + 1]), int(dist[2 * k]), int(dist[2 * k + 1])
-        hits[(e.ev.record, e.locus)] = realigned_hit(e, rec)
+    if competitors is not None:
+        score_alt_evidences(out.evidences, competitors, spec, device)
+        hits = {(e.ev.record, e.locus): realigned_hit(e, rec) for e, rec in zip(out.evidences, recs_of)}
+    else:
+        dist, lnp = score_pairs(evidence_pair_batch(out.evidences), spec, device)
+        for k, (e, rec) in enumerate(zip(out.evidences, recs_of)):
+            e.ln_ref, e.ln_alt, e.dist_ref, e.dist_alt = float(lnp[2 * k]), float(lnp[2 * k + 1]), int(dist[2 * k]), int(dist[2 * k + 1])
+            hits[(e.ev.record, e.locus)] = realigned_hit(e, rec)
     for li, site in enumerate(sites):
         members = [(o, r) for o, r in good if is_member(r, site, props.window)]
         out.n_members[li] = len(members)
@@ -1263,11 +1481,14 @@ def restate_indel(records: Sequence[BamRecord], sites: Sequence[IndelSite], prop
 
 def device_indel_observations(bams, sites: Sequence[IndelSite], props: Props, has_insert_size: bool, spec: RealignSpec, fasta: str, device: int = 0,
                               member_capacity: Optional[int] = None, name_capacity: Optional[int] = None, key_capacity: Optional[int] = None,
-                              evidence_capacity: Optional[int] = None, window_bytes: int = 0, pair_byte_limit: int = 0, retry: bool = True):
+                              evidence_capacity: Optional[int] = None, window_bytes: int = 0, pair_byte_limit: int = 0, retry: bool = True,
+                              competitors: Optional[Sequence[Sequence[bytes]]] = None):
     """(observations abi.FRAGPILEUP_OBS_DTYPE, their side records abi.FRAGPILEUP_INDEL_OBS_DTYPE, locus records abi.FRAGPILEUP_LOCUS_DTYPE,
     per-locus maxima abi.FRAGPILEUP_INDEL_LOCUS_DTYPE, abi.FragPileupCounts, evidences abi.INDELPILEUP_HIT_DTYPE record-major,
     abi.FragPileupRealignCounts) from the kernels (vlr_fragpileup_open_indel).  `sites` sorted by (ref_id, start).  An overflow of a
-    capacity is retried once with the needed ones unless retry=False."""
+    capacity is retried once with the needed ones unless retry=False.  `competitors`: per site the allele windows of the other
+    candidates at its position (vlr_fragpileup_set_alt_variants); the result then also has (abi.FRAGPILEUP_ALT_HIT_DTYPE per evidence,
+    abi.FragPileupAltCounts)."""
     from . import engine
     from . import realign as rl
     from .readwindows import MODES, locus_arrays
@@ -1295,8 +1516,10 @@ def device_indel_observations(bams, sites: Sequence[IndelSite], props: Props, ha
             engine._check(L.vlr_fragpileup_read_indel(h, obx.ctypes.data, len(obx), lox.ctypes.data, n))
             if len(ev):
                 engine._check(L.vlr_fragpileup_read_realigned(h, ev.ctypes.data, len(ev)))
+        if competitors is not None:
+            return (obs, obx, loc, lox, res, ev, rres) + _read_alt(L, h, len(ev) if fits else 0)
         return obs, obx, loc, lox, res, ev, rres
-    return _session(L, L.vlr_fragpileup_open_indel, args_of, caps, bams, retry, True, read)
+    return _session(L, L.vlr_fragpileup_open_indel, args_of, caps, bams, retry, True, read, _set_alt_variants(L, competitors) if competitors is not None else None)
 
 
 def indel_obs_from_arrays(a: np.ndarray, x: np.ndarray) -> List[IndelObs]:
@@ -1339,22 +1562,26 @@ def indel_site(seq: bytes, ref_id: int, pos: int, ref: bytes, alt: bytes, window
 
 
 def indel_tables(bams, fasta: str, sites: Sequence[IndelSite], what: Sequence[str], props: Props, ip: IndelProps, spec: RealignSpec, device=0,
-                 omit_mapq_adjustment: bool = False, window_bytes: int = 0, ref_seqs: Optional[Dict[int, bytes]] = None, records=None) -> List[ObsTable]:
+                 omit_mapq_adjustment: bool = False, window_bytes: int = 0, ref_seqs: Optional[Dict[int, bytes]] = None, records=None,
+                 competitors: Optional[Sequence[Sequence[bytes]]] = None) -> List[ObsTable]:
     """Per deletion / insertion candidate, in the order given (the order of the candidate file: the running maxima follow it), its
-    processed pileup.  device="cpu": the restatement with the CPU pair HMMs; a device number: the kernels."""
+    processed pileup.  device="cpu": the restatement with the CPU pair HMMs; a device number: the kernels.  `competitors`: per site, in
+    the order given, the allele windows of the other candidates at its position (alt_variants)."""
     for s, w in zip(sites, what):
         if s.kind == "deletion" and not fetches_merge(s.start, s.end, props.window):
             raise PreprocessError("candidate %s: the three fetch loci of the deletion (start, centerpoint, end - 1) do not merge into one fetch with a window of %d; "
                                   "deletions with more than one fetch are not built" % (w, props.window))
     order = sorted(range(len(sites)), key=lambda k: (sites[k].ref_id, sites[k].start))
     sorted_sites = [sites[k] for k in order]
+    sorted_comp = [competitors[k] for k in order] if competitors is not None else None
     has_isize = ip.insert_size is not None
     per: List[Optional[List[IndelObs]]] = [None] * len(sites)
     maxima: List = [None] * len(sites)
     t = basecalls.TABLES if device == "cpu" else basecalls.library_tables()
     host = list(range(len(order)))
     if device != "cpu":
-        obs, obx, loc, lox, res, _, _ = device_indel_observations(bams, sorted_sites, props, has_isize, spec, fasta, int(device), window_bytes=window_bytes)
+        obs, obx, loc, lox, res = device_indel_observations(bams, sorted_sites, props, has_isize, spec, fasta, int(device), window_bytes=window_bytes,
+                                                            competitors=sorted_comp)[:5]
         blist = [bams] if isinstance(bams, str) else list(bams)
         host, slices = _locus_slices(blist[0], res, loc)
         if res.status & (abi.FRAGPILEUP_ANY_OVERFLOW | abi.FRAGPILEUP_EVIDENCE_OVERFLOW):
@@ -1368,7 +1595,8 @@ def indel_tables(bams, fasta: str, sites: Sequence[IndelSite], what: Sequence[st
         recs = records() if records is not None else [r for b in blist for r in read_bam(b)[1]]      # (`records`: the caller's, read once)
         if ref_seqs is None:
             raise ValueError("the restatement needs the contigs of the loci (ref_seqs)")
-        rs = restate_indel(recs, [sorted_sites[j] for j in host], props, has_isize, spec, ref_seqs, device)
+        rs = restate_indel(recs, [sorted_sites[j] for j in host], props, has_isize, spec, ref_seqs, device,
+                           competitors=[sorted_comp[j] for j in host] if sorted_comp is not None else None)
         if rs.bad_records:
             raise FragPileupError("%s: record %d is malformed" % (blist[0], rs.bad_records[0]))
         for i, j in enumerate(host):
@@ -1419,20 +1647,24 @@ def read_candidates(path: str) -> List[Tuple[str, int, str, str, str]]:
 def preprocess_variants(reference: str, candidates: str, bam: str, output: str, alignment_properties: Optional[str] = None, device=0,
                         atomic_candidate_variants: bool = False, omit_mapq_adjustment: bool = False, max_depth: int = 200,
                         score_indel_reads_from_alignment: bool = False, warn=None, realign: Optional[RealignSpec] = None,
-                        indel_candidates: Optional[RealignSpec] = None, methylation_readtype: Optional[str] = None) -> int:
+                        indel_candidates: Optional[RealignSpec] = None, methylation_readtype: Optional[str] = None, alt_variants: bool = False) -> int:
     """`preprocess variants` for SNV / MNV candidates of one sample: the observation BCF `output` (format v15) that `call variants`
     reads.  Returns the number of records written.  `realign` (--realign-indel-reads): indel-bearing reads over a candidate are
     realigned as the reference does by default; its gap / hop parameters default to those of the alignment properties.
     `indel_candidates` (--indel-candidates): deletion and insertion candidates are built too, one observation per fragment (the
     section "deletion and insertion candidates" above); the file may mix them with SNVs / MNVs, records keep the candidate order.
     `methylation_readtype` (--methylation-read-type converted|annotated): candidates with ALT <METH> are built too (methylation.py);
-    without it such a candidate is refused as every symbolic allele is."""
+    without it such a candidate is refused as every symbolic allele is.
+    `alt_variants` (--alt-variants): a realigned read is scored against the other ALT alleles at its candidate's (CHROM, POS) as well
+    (the section "the other alleles of a locus" above); without it every candidate is scored as if it were alone at its position."""
     import json
     from . import ingest
     if not atomic_candidate_variants:
-        raise PreprocessError("--atomic-candidate-variants is required: candidates are scored one by one from the read's own alignment; "
-                              "realignment against the other candidates at a locus (alt_variants) is not built")
+        raise PreprocessError("--atomic-candidate-variants is required: SNV / MNV candidates are scored from the read's own alignment, as that flag of the "
+                              "reference makes it (preprocessing/mod.rs:511, 535); scoring against the other candidates at a locus does not depend on it: --alt-variants")
     sites = read_candidates(candidates)
+    if alt_variants:
+        alt_variant_groups(sites)         # (a locus with too many alleles is refused before anything is read)
     cands = []
     if methylation_readtype is not None:
         from . import methylation
@@ -1463,7 +1695,8 @@ def preprocess_variants(reference: str, candidates: str, bam: str, output: str, 
     try:
         tabs = observations(bam, reference, cands, props, device=device, omit_mapq_adjustment=omit_mapq_adjustment,
                             realign_indel_reads=not score_indel_reads_from_alignment, realign=realign, indel_candidates=indel_candidates,
-                            indel_props=indel_props_of(pj) if indel_candidates is not None else None, methylation_readtype=methylation_readtype)
+                            indel_props=indel_props_of(pj) if indel_candidates is not None else None, methylation_readtype=methylation_readtype,
+                            alt_variants=alt_variants)
     except NeedsRealign as e:
         raise PreprocessError(str(e) + "; --score-indel-reads-from-alignment scores such reads as they are aligned, --realign-indel-reads realigns them") from e
     deep = sum(1 for t in tabs if len(t) > max_depth)
